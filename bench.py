@@ -98,6 +98,61 @@ def seq05_quality(scvod_py, qmod, orc, x, offs, poses, gt, device):
     return {k: q[k] for k in ("device", "reference_chain", "delta_PR", "delta_RR", "labels_equal_fraction")} | {"preset": "semantickitti_seq05 (doc/note.txt:36)"}
 
 
+ATTRIBUTION_STEPS = 3  # untimed steps with per-kernel events after the timed ones (the `kernels` table)
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_LABEL_BYTES = 24 << 20  # of which per-point labels of the sampled scans
+DUMP_MAP_CELLS = 1 << 20  # of which map cells (key + point: 48 B each)
+
+
+def dump_outputs(outdir, ctx, smap, offs, seed=0):
+    """What the last step handed its caller, as float32 / float64 .npy files under outdir (at most DUMP_BYTES in all), so that
+    two builds run with the same arguments (same seeded input) can be compared array by array:
+      scan_counts   [S, 8] f64   per scan: scvod_batch_counts (points, ground, non-ground, dropped, binned, rejected, voxels, 0)
+      scan_tracking [S, 4] f64   per scan: clusters, car points, dynamic clusters, dynamic points
+      label_scans   [K]    f64   a fixed seeded sample of the scans, ascending
+      point_labels  [n]    f32   per INPUT point of those scans, scan after scan: 0 static, 1 dynamic, 2 in no cluster, 3 dropped
+      map_cells     [1]    f64   cells of the static map
+      map_key       [M, 2] f64   cell keys (high, low 32-bit halves), ascending: the cells whose key falls under a fixed hash threshold
+      map_xyzi      [M, 4] f32   the point each of those cells keeps"""
+    import numpy as np
+    import quality as qmod
+    os.makedirs(outdir, exist_ok=True)
+    n_sc = len(offs) - 1
+    files = {"scan_counts": ctx.batch_counts().astype(np.float64)}
+    trk = [ctx.batch_fetch_track(s) for s in range(n_sc)]
+    files["scan_tracking"] = np.array([[t["n_clusters"], t["n_car_points"], t["n_dynamic_clusters"], t["n_dynamic_points"]] for t in trk], np.float64)
+    del trk
+    pick, nbytes = [], 0
+    for s in np.random.default_rng(seed).permutation(n_sc):
+        n = int(offs[s + 1] - offs[s])
+        if nbytes + 4 * n > DUMP_LABEL_BYTES:
+            break
+        pick.append(int(s))
+        nbytes += 4 * n
+    pick.sort()
+    files["label_scans"] = np.array(pick, np.float64)
+    files["point_labels"] = np.concatenate([qmod.device_point_labels(ctx, s, int(offs[s + 1] - offs[s])) for s in pick] or [np.zeros(0, np.uint8)]).astype(np.float32)
+    if smap is not None:
+        xyzi, rec = smap.points()
+        key = rec[:, 0].cpu().numpy()
+        xyzi = xyzi.cpu().numpy()
+        files["map_cells"] = np.array([len(key)], np.float64)
+        # a cell is kept when the top `shift` bits of its hashed key are zero: the same cells in any build that has them
+        shift = 0
+        while (len(key) >> shift) > DUMP_MAP_CELLS // 2:
+            shift += 1
+        h = key.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        sel = np.nonzero((h >> np.uint64(64 - shift)) == 0)[0] if shift else np.arange(len(key))
+        sel = sel[np.argsort(key[sel], kind="stable")][:DUMP_MAP_CELLS]
+        files["map_key"] = np.stack([key[sel] >> 32, key[sel] & 0xFFFFFFFF], 1).astype(np.float64)
+        files["map_xyzi"] = xyzi[sel].astype(np.float32)
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes over the {DUMP_BYTES} budget"
+    for name, a in files.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": outdir, "bytes": total, "label_scans": len(pick), "map_cells_dumped": len(files.get("map_key", ()))}
+
+
 def other_configs():
     """configs[2] (parking lot, one chain of 1999 steps) and configs[4] (128 beams, 2x finer grid) as sub-runs of this script"""
     res = {}
@@ -158,7 +213,11 @@ def main():
                     help="chain states at the cuts: device = shard.DeviceBoundary (padded rows, compare kernel, verdict word read one step late; on RCCL the rows travel device to device, "
                          "on gloo they are staged through the host: the dry run of the nccl path's step logic with real neighbours on one GPU); host = the host-driven protocol every step; auto = device on nccl, host on gloo")
     ap.add_argument("--dump-map", default="", help="rank 0 writes the merged static map (records sorted by cell key) and the per-scan dynamic counts to this .npz")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last of them computed (per-scan counts, per-point labels "
+                    "of a seeded sample of scans, a fixed hash-selected part of the static map) as DIR/<name>.npy, float32 / float64, at most 64 MB (one rank only)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     # `python bench.py --gpus N` outside a launcher: start the N ranks ourselves (one process per GPU, RCCL)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -417,10 +476,12 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
-    # the same steps again with hipEvents around every kernel of the ctx (attribution only) and around the map stage
+    dumped = dump_outputs(args.dump_outputs, ctx, pmap if multi else smap, offs) if args.dump_outputs else None
+    # a few more steps with hipEvents around every kernel of the ctx (attribution only) and around the map stage: at most
+    # ATTRIBUTION_STEPS whatever --steps is, so that only the timed steps grow with --steps
     ctx.set_timing(True)
     barrier()
-    for _ in range(args.steps):
+    for _ in range(min(args.steps, ATTRIBUTION_STEPS)):
         step(timed=True)
     barrier()
     ctx.set_timing(False)
@@ -609,6 +670,8 @@ def main():
                           "split": ({"scans_loaded_by_rank0": n_sc, "own": own_count, "pieces_rank0": [list(map(int, pc)) for pc in split["pieces"]], "chains_rewalked_at_boundary_rank0": info.get("chains_rewalked_at_boundary"), "chains_rewalked_at_boundary_all_ranks": info.get("chains_rewalked_all_ranks"), "boundary_exchange_ms_rank0_last_step": info.get("boundary_ms"), "boundary": info.get("boundary"), "boundary_slow_path_steps_rank0": info.get("boundary_slow_path_steps", 0)} if split else None)},
                "mpts_per_s": all_pts * args.steps / dt / 1e6, "gen_seconds": gen_s,
                "roofline": roof, "cpu_baseline": cpu, "quality": quality, "kernels": kernels, "extras": extras}
+        if dumped:
+            out["dump_outputs"] = dumped
         if multi:
             out["config"]["map_records_sent_per_rank"] = info.get("map_records_sent")
             out["config"]["map_slot_records"] = info.get("map_slot_records")

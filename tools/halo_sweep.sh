@@ -1,10 +1,13 @@
 #!/bin/bash
+set -o pipefail
 # How short can the halo in front of a rank's block be before the chain states at the cuts stop being reproduced by the warm-up?
-# Eight gloo ranks on ONE device (the driver's `bench.py --gpus 8` job at 240 and 690 scans), halo = 12 ... 2 steps.
+# Four gloo ranks on ONE device (the driver's `bench.py --gpus N` job at 240 and 690 scans), halo = 12 ... 2 steps.  Four is
+# as many as one shared device takes next to the launcher; the sweep stops at the first run that fails.
 # usage (GPU box): bash tools/halo_sweep.sh > gpurun_out/r06_halo_sweep.txt
 for scans in 240 690; do
   for halo in 12 10 8 6 5 4 3 2; do
-    out=$(timeout 300 python bench.py --gpus 8 --same-device --backend gloo --scans $scans --split-halo $halo --steps 1 --warmup 1 --no-cpu --no-extras 2>/dev/null | grep '^{' | tail -1)
+    out=$(timeout -k 10 300 python bench.py --gpus 4 --same-device --backend gloo --scans $scans --split-halo $halo --steps 1 --warmup 1 --no-cpu --no-extras 2>/dev/null | grep '^{' | tail -1) \
+      || { echo "scans $scans halo $halo: bench.py failed (exit $?), sweep stopped"; exit 1; }
     python - "$scans" "$halo" <<PY
 import json, sys
 try:
