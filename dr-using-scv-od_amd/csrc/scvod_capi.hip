@@ -120,6 +120,15 @@ struct scvod_ctx {
     bool chain_ws_clean = false;
     int chain_ws_layout_pts = -1;
     bool tables_valid = false;   // successor tables (vox_track) built for the current clustering
+    // intensity merge (scvod_set_intensity_merge, scvod_k_merge.inc): setting, scratch (own allocation, first merged clustering)
+    int32_t im_iterations = 0, im_search_c = 2;
+    float im_diff = 50.f, im_cov = 20.f;
+    void* im_buf = nullptr;
+    size_t im_bytes = 0;
+    MergeJob im{};
+    bool merged = false;         // the last clustering applied the merge: A.pt_cluster points at the fused partition (im.pt_merged)
+    int32_t* pt_cluster_own = nullptr;  // the arena's own pt_cluster (the clustering's output and scratch, the max_name pass's input)
+    int im_overflow = -1;        // scans of the last merged clustering whose neighbour pairs outgrew their scratch (-1: not read yet)
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -440,10 +449,61 @@ int ensure_side(scvod_ctx* c, int which) {
     return rc;
 }
 
+// scratch of the intensity merge: one allocation carved like the arena, made the first time a clustering merges
+int ensure_merge(scvod_ctx* c) {
+    if (c->im_buf) return SCVOD_OK;
+    const size_t N = (size_t)c->cap_pts, B = (size_t)c->cap_scans;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver k{(unsigned char*)c->im_buf};
+        MergeJob& M = c->im;
+        M.vlab = k.take<int32_t>(N);
+        M.key0 = k.take<int32_t>(N);
+        M.nxt = k.take<int32_t>(N);
+        M.own = k.take<uint8_t>(N);
+        M.fz = k.take<uint8_t>(N);
+        M.qv = k.take<int32_t>(N);
+        M.qk = k.take<int32_t>(N);
+        M.box = k.take<uint32_t>(7 * N);
+        M.pair = k.take<uint64_t>(kImPairsPerPt * N + kImPairsPerScan * B);
+        M.cand = k.take<uint64_t>(N);
+        M.pt_merged = k.take<int32_t>(N);
+        M.stats = k.take<int32_t>(8);
+        if (pass == 0) {
+            c->im_bytes = align_up(k.off, 256);
+            HIPCHK(c, hipMalloc(&c->im_buf, c->im_bytes));
+            c->side_bytes += c->im_bytes;
+        }
+    }
+    return SCVOD_OK;
+}
+
+// everything after the clustering reads the partition through A.pt_cluster: the fused one after a merged clustering.  A new batch
+// or clustering starts from the arena's own array again.
+void unmerge_view(scvod_ctx* c) {
+    if (c->pt_cluster_own) c->A.pt_cluster = c->pt_cluster_own;
+    c->merged = false;
+    c->im_overflow = -1;
+}
+
+// a merged clustering whose neighbour pairs outgrew their scratch left some scans unmerged: every reader of the result fails
+int merge_check(scvod_ctx* c) {
+    if (!c->merged) return SCVOD_OK;
+    if (c->im_overflow < 0) {
+        HIPCHK(c, hipStreamSynchronize(c->last_stream));
+        int32_t st[8];
+        HIPCHK(c, hipMemcpy(st, c->im.stats, sizeof(st), hipMemcpyDeviceToHost));
+        c->im_overflow = st[4];
+    }
+    if (c->im_overflow > 0)
+        return fail(c, SCVOD_ERR_CAPACITY, "intensity merge: the neighbour pairs of %d scans outgrew their scratch (%d per point)", c->im_overflow, kImPairsPerPt);
+    return SCVOD_OK;
+}
+
 int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_scans, hipStream_t st,
               int do_patchwork, int apply_filter, int do_voxels, int sync, bool off_pinned = false) {
     if (!c) return SCVOD_ERR_INVALID;
     if (n_scans <= 0 || !h_off || (!d_xyzi && do_patchwork != 2)) return fail(c, SCVOD_ERR_INVALID, "empty batch");
+    unmerge_view(c);
     if (n_scans > c->cap_scans) return fail(c, SCVOD_ERR_CAPACITY, "n_scans %d > capacity %d", n_scans, c->cap_scans);
     int64_t total = (int64_t)h_off[n_scans] - h_off[0];
     if (h_off[0] != 0) return fail(c, SCVOD_ERR_INVALID, "scan_offsets[0] must be 0");
@@ -633,6 +693,7 @@ int run_voxelgrid(scvod_ctx* c, const void* d_xyzi, const uint32_t* d_labels, co
                   const float leaf[3], float max_intensity, void* d_out, int64_t out_cap, int32_t* h_out_off, hipStream_t st) {
     if (!c) return SCVOD_ERR_INVALID;
     if (n_scans <= 0 || !h_off || !d_xyzi || !leaf || !d_out || !h_out_off) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    unmerge_view(c);
     if (!(leaf[0] > 0.f) || !(leaf[1] > 0.f) || !(leaf[2] > 0.f)) return fail(c, SCVOD_ERR_INVALID, "leaf size must be positive");
     if (n_scans > c->cap_scans) return fail(c, SCVOD_ERR_CAPACITY, "n_scans %d > capacity %d", n_scans, c->cap_scans);
     if (h_off[0] != 0) return fail(c, SCVOD_ERR_INVALID, "scan_offsets[0] must be 0");
@@ -1125,6 +1186,7 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->t_pts) hipFree(c->t_pts);
     if (c->d_labels) hipFree(c->d_labels);
     if (c->d_apri) hipFree(c->d_apri);
+    if (c->im_buf) hipFree(c->im_buf);
     if (c->chain_ws) hipFree(c->chain_ws);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
@@ -1300,7 +1362,26 @@ int scvod_batch_cluster(scvod_ctx* c, void* stream, int32_t sync) {
     // and its tracking left per input point would otherwise survive on points that are no car members any more
     if (c->clustered_this_batch && c->A.total_pts > 0) HIPCHK(c, hipMemsetAsync(c->A.pt_mapcls, 0, (size_t)c->A.total_pts, st));
     c->clustered_this_batch = true;
+    unmerge_view(c);
+    if (!c->pt_cluster_own) c->pt_cluster_own = c->A.pt_cluster;
+    if (c->im_iterations > 0) {
+        const size_t lds = merge_lds_bytes(c->dev, c->A.max_scan_pts);
+        if (lds > 160 * 1024 - 256)
+            return fail(c, SCVOD_ERR_INVALID, "intensity merge: %zu bytes of LDS for a %d x %d row table and scans of %d points (160 KB per workgroup)",
+                        lds, c->dev.bin.range_num, c->dev.bin.azimuth_num, c->A.max_scan_pts);
+        int rc = ensure_merge(c);
+        if (rc) return rc;
+    }
     launch_cluster(c->dev, c->A, c->batch_mode == 2 ? 1 : 0, st, timer_hook, c);
+    if (c->im_iterations > 0) {  // (before the max_name passes: they read pt_cluster, left as it was, and the post-merge pt_type)
+        c->im.iterations = c->im_iterations;
+        c->im.search_c = c->im_search_c;
+        c->im.diff = c->im_diff;
+        c->im.cov = c->im_cov;
+        launch_merge(c->dev, c->A, c->im, c->batch_mode == 2 ? 1 : 0, st, timer_hook, c);
+        c->merged = true;
+    }
+    // (the max_name passes below still read the pre-merge partition: they take c->A by value before the view switches)
     c->last_name_valid = false;
     // Frame::max_name of every scan (scvod_lastname.hip): launches of its own beside the tracking kernels.  (Run by the clustering
     // workgroup itself -- 1024 threads, one workgroup per CU -- the pass is a chain of dependent look-ups nobody hides: measured
@@ -1323,16 +1404,19 @@ int scvod_batch_cluster(scvod_ctx* c, void* stream, int32_t sync) {
         }
         if (c->timing) {  // attribution runs: one stream, one pair of events per pass
             launch_lastname(c->dev, c->A, st, nullptr, nullptr, nullptr, nullptr, nullptr, timer_hook, c);
+            if (c->merged) launch_merge_lastname(c->A, c->im, st, timer_hook, c);
         } else {
             HIPCHK(c, hipEventRecord(c->ln_fork, st));
             HIPCHK(c, hipStreamWaitEvent(c->ln_stream, c->ln_fork, 0));
             launch_lastname(c->dev, c->A, c->ln_stream, c->ln_stream2, c->ln_stream3, c->ln_fork2, c->ln_join2, c->ln_join3, nullptr, c);
+            if (c->merged) launch_merge_lastname(c->A, c->im, c->ln_stream, nullptr, c);
             HIPCHK(c, hipEventRecord(c->ln_done, c->ln_stream));
             c->ln_pending = true;
         }
         c->last_name_valid = true;
         if (sync) join_lastname(c, st);
     }
+    if (c->merged) c->A.pt_cluster = c->im.pt_merged;
     HIPCHK(c, hipGetLastError());
     c->clusters_valid = true;
     c->types_valid = false;  // scvod_batch_cluster_types publishes them
@@ -1351,6 +1435,7 @@ int scvod_batch_fetch_clusters(scvod_ctx* c, int32_t s, int32_t* h_pt_cluster, i
     const int32_t n = c->h_counts[(size_t)s * 8 + 4];
     if (n > cap) return fail(c, SCVOD_ERR_CAPACITY, "output buffer too small (%d < %d)", cap, n);
     HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    if ((rc = merge_check(c))) return rc;
     if (n) HIPCHK(c, hipMemcpy(h_pt_cluster, c->A.pt_cluster + c->h_scan_off[s], sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     return n;
 }
@@ -1381,6 +1466,7 @@ int scvod_batch_fetch_cluster_types(scvod_ctx* c, int32_t s, int32_t car_label, 
     const int32_t n = c->h_counts[(size_t)s * 8 + 4];
     if (n > cap) return fail(c, SCVOD_ERR_CAPACITY, "output buffer too small (%d < %d)", cap, n);
     HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    if ((rc = merge_check(c))) return rc;
     std::vector<uint8_t> t(n ? n : 1);
     if (n) HIPCHK(c, hipMemcpy(t.data(), c->A.pt_type + c->h_scan_off[s], (size_t)n, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) h_type[i] = t[i] == 0 ? -1 : (t[i] == 2 ? car_label : other_label);
@@ -1402,6 +1488,7 @@ int scvod_batch_track(scvod_ctx* c, const float* h_T, const int32_t* h_next_scan
     if (!c || !h_T || n_ext < 0 || (n_ext > 0 && !h_ext_tables)) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
     if (!c->batch_valid || !c->voxels_valid || !c->clusters_valid || !c->types_valid)
         return fail(c, SCVOD_ERR_STATE, "scvod_batch_track needs scvod_batch_process, scvod_batch_cluster and scvod_batch_cluster_types first");
+    if (int rc = merge_check(c)) return rc;
     if (c->batch_mode == 3) return fail(c, SCVOD_ERR_STATE, "the last batch was a VoxelGrid run");
     const int B = c->A.n_scans;
     if (n_ext > c->cap_scans) return fail(c, SCVOD_ERR_CAPACITY, "too many external tables");
@@ -1698,6 +1785,32 @@ int scvod_batch_cluster_help_stats(scvod_ctx* c, int32_t* h_out2) {
     return SCVOD_OK;
 }
 
+int scvod_set_intensity_merge(scvod_ctx* c, int32_t iterations, int32_t search_c, float intensity_diff, float intensity_cov) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (iterations < 0 || !(intensity_diff >= 0.f) || !(intensity_cov >= 0.f))
+        return fail(c, SCVOD_ERR_INVALID, "intensity merge: negative parameter");
+    if (search_c < 1 || search_c > 3)
+        return fail(c, SCVOD_ERR_INVALID, "intensity merge: search_c %d outside 1..3", search_c);
+    c->im_iterations = iterations;
+    c->im_search_c = search_c;
+    c->im_diff = intensity_diff;
+    c->im_cov = intensity_cov;
+    c->clusters_valid = c->types_valid = c->tables_valid = c->track_valid = false;
+    return SCVOD_OK;
+}
+
+int scvod_batch_cluster_merge_stats(scvod_ctx* c, int32_t* h_out4) {
+    if (!c || !h_out4) return SCVOD_ERR_INVALID;
+    if (!c->clusters_valid) return fail(c, SCVOD_ERR_STATE, "no clustering of the last batch");
+    for (int k = 0; k < 4; ++k) h_out4[k] = 0;
+    if (!c->merged) return SCVOD_OK;
+    HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    int32_t st[8];
+    HIPCHK(c, hipMemcpy(st, c->im.stats, sizeof(st), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; ++k) h_out4[k] = st[k];
+    return merge_check(c);
+}
+
 int scvod_set_max_name_literal(scvod_ctx* c, int32_t literal) {
     if (!c) return SCVOD_ERR_INVALID;
     c->max_name_literal = literal != 0;
@@ -1801,6 +1914,7 @@ int scvod_batch_track_tables(scvod_ctx* c, void* stream) {
     if (!c) return SCVOD_ERR_INVALID;
     if (!c->batch_valid || !c->voxels_valid || !c->clusters_valid || !c->types_valid)
         return fail(c, SCVOD_ERR_STATE, "scvod_batch_track_tables needs scvod_batch_process, scvod_batch_cluster and scvod_batch_cluster_types first");
+    if (int rc = merge_check(c)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     c->last_stream = st;

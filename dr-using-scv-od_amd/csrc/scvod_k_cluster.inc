@@ -474,6 +474,16 @@ __device__ __forceinline__ bool cc_search_windows(const CcKeys<TabT>& K, int* pa
     return true;
 }
 
+// type of a cluster from its box and member count: refineClusterByBoundingBox (ssc.cpp:437-467) + the box part of recognize
+// (ssc.cpp:849-872).  0 erased, 1 other, 2 car.  Shared by the clustering and the intensity merge (scvod_k_merge.inc).
+__device__ __forceinline__ uint32_t cc_type_rule(const DevParams& P, float mnx, float mny, float mnz, float mxx, float mxy, float mxz, int cnt) {
+    const float diff_zf = mxz - mnz;
+    if (mnz > 0.f || cnt < P.to_be_class || diff_zf < 0.2f) return 0;
+    const double square = (double)(mxx - mnx) * (double)(mxy - mny);
+    if (square > (double)P.car_square) return 1;
+    if ((double)mnz < (double)P.min_z && square < (double)P.car_square && (double)mxz < (double)P.max_z) return 2;
+    return 1;
+}
 __device__ __forceinline__ uint32_t f2ord(float f) { return float_sort_key(f); }
 __device__ __forceinline__ float ord2f(uint32_t u) { return u2f((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
@@ -2460,19 +2470,7 @@ __device__ __forceinline__ bool cc_scan_impl(const DevParams& P, const Arena& A,
         const float mnx = ord2f(r[0]), mny = ord2f(r[1]), mnz = ord2f(r[2]);
         const float mxx = ord2f(r[3]), mxy = ord2f(r[4]), mxz = ord2f(r[5]);
         const int cnt = (int)r[6];
-        const float diff_zf = mxz - mnz;
-        uint32_t t;
-        if (mnz > 0.f || cnt < P.to_be_class || diff_zf < 0.2f) {
-            t = 0;
-        } else {
-            const double square = (double)(mxx - mnx) * (double)(mxy - mny);
-            if (square > (double)P.car_square)
-                t = 1;
-            else if ((double)mnz < (double)P.min_z && square < (double)P.car_square && (double)mxz < (double)P.max_z)
-                t = 2;
-            else
-                t = 1;
-        }
+        const uint32_t t = cc_type_rule(P, mnx, mny, mnz, mxx, mxy, mxz, cnt);
         r[0] = t;
         r[1] = 0;  // (the box is used up: the word counts the cluster's voxels below)
         r[4] = 0xffffffffu;  // ... and this one takes the lowest voxel slot carrying the cluster's label (its id in the tracking chain)

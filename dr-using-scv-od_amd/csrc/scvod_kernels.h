@@ -203,6 +203,26 @@ struct TrackBatch {            // scvod_batch_track: every scan of the batch aga
     float occupancy;               // ssc/occupancy_
 };
 
+// intensity merge of the clusters (SSC::refineClusterByIntensity, ssc.cpp:571-635; scvod_k_merge.inc).  Scratch of its own, allocated
+// when a ctx turns the merge on: per-point arrays indexed base + i (names and voxel slots are scan-local and < n).
+struct MergeJob {
+    int32_t iterations, search_c;
+    float diff, cov;             // ssc/intensity_diff_, ssc/intensity_cov_
+    int32_t* vlab;               // [N] label (cluster name) of every voxel: that of its first point
+    int32_t* key0;               // [N] per name: smallest voxel key of the cluster (sort1's key)
+    int32_t* nxt;                // [N] per name: the cluster it was fused into (-1: never a member of a fusion)
+    uint8_t* own;                // [N] per name: the cluster's own label is in its neighbour set S
+    uint8_t* fz;                 // [N] per name: took part in a fusion as its target
+    int32_t* qv;                 // [N] voxels with cov <= intensity_cov in key order ...
+    int32_t* qk;                 // [N] ... and their keys
+    uint32_t* box;               // [7 N] per fused name: box (order-preserving encoding) + member count
+    uint64_t* pair;              // [kImPairsPerPt N + kImPairsPerScan B] (cluster << 32 | neighbour label) per scan
+    uint64_t* cand;              // [N] clusters to visit: (~key << 32 | first pair)
+    int32_t* pt_merged;          // [N] post-merge canonical name per apri point
+    int32_t* stats;              // [8] clusters before, fusions, clusters after, scans with a fusion, scans whose pairs overflowed
+};
+constexpr int kImPairsPerPt = 4, kImPairsPerScan = 256;
+
 typedef void (*TimerHook)(void* user, const char* name, int begin);
 
 // Launches.  `th`/`tu` optional per-kernel timing hook (called before and after each launch).
@@ -222,6 +242,9 @@ void launch_voxelgrid_lut(const Arena& A, hipStream_t st);
 void launch_voxelgrid_gather(const DevParams& P, const Arena& A, const VgJob& J, long long out_capacity, hipStream_t st);
 void launch_cls(const Arena& A, int s, size_t scan_base, int n_points, hipStream_t st);
 void launch_cluster(const DevParams& P, const Arena& A, int from_apri, hipStream_t st, TimerHook th, void* tu);
+size_t merge_lds_bytes(const DevParams& P, int max_scan_pts);  // dynamic LDS of k_im_merge: row starts + invalid bitmap
+void launch_merge(const DevParams& P, const Arena& A, const MergeJob& M, int from_apri, hipStream_t st, TimerHook th, void* tu);
+void launch_merge_lastname(const Arena& A, const MergeJob& M, hipStream_t st, TimerHook th, void* tu);  // carrier of max_name -> its fusion
 void launch_lastname(const DevParams& P, const Arena& A, hipStream_t st, hipStream_t st2, hipStream_t st3, hipEvent_t ev_fork, hipEvent_t ev_join2,
                      hipEvent_t ev_join3, TimerHook th, void* tu);
 void launch_track(const DevParams& P, const Arena& A, const TrackJob& J, int batch_mode, hipStream_t st,

@@ -359,6 +359,7 @@ __device__ __forceinline__ void block_bitonic_merge_stages(T* a, int np2) {
 #include "scvod_k_voxelgrid.inc"  // loader-side label filter + pcl::VoxelGrid
 #include "scvod_k_voxels.inc"  // PointAPRI expansion, direct binning, the voxel stage: buckets, LDS sort, per-voxel descriptors (A4-A5)
 #include "scvod_k_cluster.inc"  // curved-voxel clustering, boxes, type rules, successor tables: k_cc_scan
+#include "scvod_k_merge.inc"  // intensity merge of the clusters (ssc.cpp:571-635), opt-in: k_im_merge
 #include "scvod_k_probe_nn.inc"  // per-pair tracking probe of the facade path (A6 bulk part) and the brute-force correspondence search (A7)
 // ------------------------------------------------------------------------------------------
 // host-side launch sequences
@@ -597,6 +598,31 @@ void launch_cluster(const DevParams& P, const Arena& A0, int from_apri, hipStrea
     TH_BEGIN("cc_exact");
     hipLaunchKernelGGL(k_cc_exact, dim3(kCcExactBlocks), dim3(kCcThreads), kCcLdsBytes, st, P, A, from_apri);
     TH_END("cc_exact");
+}
+
+size_t merge_lds_bytes(const DevParams& P, int max_scan_pts) {
+    return 4 * ((size_t)P.bin.range_num * P.bin.azimuth_num + 1 + ((size_t)max_scan_pts + 31) / 32);
+}
+
+void launch_merge(const DevParams& P, const Arena& A, const MergeJob& M, int from_apri, hipStream_t st, TimerHook th, void* tu) {
+    hipMemsetAsync(M.stats, 0, 8 * sizeof(int32_t), st);
+    const int B = A.n_scans;
+    if (B <= 0 || A.max_scan_pts <= 0) return;
+    const size_t lds = merge_lds_bytes(P, A.max_scan_pts);
+    hipFuncSetAttribute((const void*)k_im_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    TH_BEGIN("im_merge");
+    hipLaunchKernelGGL(k_im_merge, dim3(B), dim3(kImThreads), lds, st, P, A, M, from_apri);
+    TH_END("im_merge");
+    TH_BEGIN("im_tables");
+    hipLaunchKernelGGL(k_im_tables, dim3(B), dim3(kImThreads), 0, st, P, A, M, from_apri);
+    TH_END("im_tables");
+}
+
+void launch_merge_lastname(const Arena& A, const MergeJob& M, hipStream_t st, TimerHook th, void* tu) {
+    if (A.n_scans <= 0) return;
+    TH_BEGIN("im_lastname");
+    hipLaunchKernelGGL(k_im_lastname, dim3((A.n_scans + 255) / 256), dim3(256), 0, st, A, M);
+    TH_END("im_lastname");
 }
 
 void launch_track(const DevParams& P, const Arena& A, const TrackJob& J, int batch_mode, hipStream_t st,

@@ -35,6 +35,8 @@ SSC::SSC(const std::string& yaml_path, int device, int max_points) {
     scvod_grid_dims(&p, &range_num, &sector_num, &azimuth_num, &bin_num);  // ssc.cpp:36-39
     int rc = scvod_create(&p, nullptr, device, max_points, 1, &ctx_);
     if (rc != SCVOD_OK) throw std::runtime_error("scvod_create failed (status " + std::to_string(rc) + "): the SCV-OD hot path is GPU-only");
+    // ssc.cpp:644 (refineClusterByIntensity between the clustering and the box refine): on request, with the four YAML keys
+    if (device_intensity_merge) chk(ctx_, scvod_set_intensity_merge(ctx_, iteration, search_c, intensity_diff, intensity_cov), "scvod_set_intensity_merge");
     PatchworkGroundSeg->attach(ctx_);
 }
 

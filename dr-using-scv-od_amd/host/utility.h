@@ -73,6 +73,7 @@ class Utility {
           refine_height = -1.0f, max_z = 1.0f, min_z = -1.0f, car_angle = 120.0f, car_height = 2.0f, car_square = 2.0f;
     float max_intensity = 200.0f, correct_ratio = 0.5f, correct_radius = 0.5f;
     int search_num = 10, iteration = 3, toBeClass = 1, search_c = 2;
+    int device_intensity_merge = 0;  // facade-only key ssc/device_intensity_merge_: 1 runs refineClusterByIntensity on the device
     float intensity_diff = 50, intensity_cov = 20, occupancy = 0.6f;
     int building = 0, tree = 1, car = 2;
     std::vector<float> tr_v;
@@ -315,6 +316,7 @@ class Utility {
         y.param<int>("ssc/search_c_", search_c, 2);
         y.param<float>("ssc/intensity_diff_", intensity_diff, 50.f);
         y.param<float>("ssc/intensity_cov_", intensity_cov, 20.f);
+        y.param<int>("ssc/device_intensity_merge_", device_intensity_merge, 0);
         y.param<float>("ssc/occupancy_", occupancy, 0.6f);
         y.param<int>("ssc/building_", building, 0);
         y.param<int>("ssc/tree_", tree, 1);

@@ -432,12 +432,32 @@ int scvod_batch_fetch_clusters(scvod_ctx* ctx, int32_t s, int32_t* h_pt_cluster,
  * per apri point of scan s, h_type[i] = -1 when its cluster is erased (min z > 0, fewer than toBeClass
  * points, z extent < 0.2 m), `car_label` when bbox area <= car_square && min z < min_z && max z < max_z,
  * otherwise `other_label` (the reference separates building / tree with PCL region growing, which stays
- * on the host).  No intensity merge (ssc.cpp:571-635) is applied.  Returns the count or a negative status. */
+ * on the host).  The intensity merge (ssc.cpp:571-635) is applied only when scvod_set_intensity_merge turned it on: the types are
+ * then those of the fused clusters.  Returns the count or a negative status. */
 int scvod_batch_cluster_types(scvod_ctx* ctx, void* stream, int32_t sync);
 int scvod_batch_fetch_cluster_types(scvod_ctx* ctx, int32_t s, int32_t car_label, int32_t other_label, int32_t* h_type,
                                     int32_t cap);
-/* one-shot host version on an apri_vec the caller holds (voxelises it first) */
+/* one-shot host version on an apri_vec the caller holds (voxelises it first; applies the ctx's intensity merge setting) */
 int scvod_cluster(scvod_ctx* ctx, const scvod_apri* h_apri, int32_t n, int32_t* h_pt_cluster);
+/* Intensity merge of the clusters, SSC::refineClusterByIntensity (ssc.cpp:571-635), run by scvod_batch_cluster when iterations
+ * > 0.  The clustering kernel has evaluated the bounding-box rules already; the merge re-evaluates them (same rule) for the fused
+ * clusters only, which gives what the reference's order -- merge, then box refine -- gives (ssc/iteration_, ssc/search_c_, ssc/intensity_diff_,
+ * ssc/intensity_cov_).  Off by default (iterations = 0): nothing is launched and every output stays as it was.  With it on,
+ * scvod_batch_fetch_clusters / scvod_batch_fetch_cluster_types / scvod_cluster return the fused partition (canonical names: the
+ * smallest apri index of the fused cluster) and its types, and everything downstream reads it: the successor tables, the car lists,
+ * the tracking chain, the per-point dynamic bytes, the static map; scvod_batch_cluster_last_name reports the fused cluster that
+ * contains the carrier of max_name.  The visiting order of the stage is fixed as DESIGN.md section 2 states.
+ * search_c must lie in 1..3: the neighbour walk looks up (2 search_c + 1)^2 grid rows per voxel, and the packed index triples
+ * (clamped at -2 below the grid) reproduce findVoxelNeighbors up to that radius for every triple the range / FOV filter keeps.
+ * The grid's range x azimuth row table and a bit per point of the largest scan share the LDS of one workgroup (160 KB): larger
+ * grids are refused by scvod_batch_cluster.  A scan whose neighbour pairs outgrow their scratch (4 per point) keeps its partition and
+ * every reader of the clustering (fetches, scvod_cluster, tracking, merge stats) then fails with SCVOD_ERR_CAPACITY.
+ * SCVOD_ERR_INVALID for negative values or search_c outside 1..3.  Scratch of about 100 bytes per point of the ctx's capacity is allocated on the first merged
+ * clustering (counted by scvod_arena_bytes). */
+int scvod_set_intensity_merge(scvod_ctx* ctx, int32_t iterations, int32_t search_c, float intensity_diff, float intensity_cov);
+/* h_out4 = {clusters before the merge, fusions recorded (all iterations), clusters after, scans with at least one fusion} of the
+ * last clustering (zeros when the merge was off).  SCVOD_ERR_CAPACITY as above.  Synchronises. */
+int scvod_batch_cluster_merge_stats(scvod_ctx* ctx, int32_t* h_out4);
 
 /* Streaming ingest of a sequence held in HOST memory (the reference reads one .bin per scan, SSC::getCloud
  * src/ssc.cpp:1040-1125): chunks of `chunk_scans` scans travel host -> device on a copy stream into one of two device
