@@ -129,6 +129,21 @@ struct scvod_ctx {
     bool merged = false;         // the last clustering applied the merge: A.pt_cluster points at the fused partition (im.pt_merged)
     int32_t* pt_cluster_own = nullptr;  // the arena's own pt_cluster (the clustering's output and scratch, the max_name pass's input)
     int im_overflow = -1;        // scans of the last merged clustering whose neighbour pairs outgrew their scratch (-1: not read yet)
+    // region growing of the large clusters (scvod_set_region_growing, scvod_k_rgrow.inc): setting, chunk scratch, batch-wide outputs
+    bool rg_on = false;
+    int32_t rg_k = 10, rg_min_seg = 20;
+    float rg_cos = 0.f, rg_curv = 1.2f;
+    double rg_frac = 0.2;
+    void* rg_buf = nullptr;      // chunk scratch (capacity rg_cap points), grown when a chunk needs more
+    size_t rg_buf_bytes = 0;
+    int64_t rg_cap = 0;
+    void* rg_out = nullptr;      // per apri point: class byte, normal + curvature, segment (the ctx's capacity)
+    size_t rg_out_bytes = 0;
+    RgJob rg{};
+    void* rg_sort_tmp = nullptr;
+    size_t rg_sort_bytes = 0;
+    hipEvent_t rg_ev = nullptr;
+    bool rg_done = false;        // the region growing ran on the current clustering (scvod_batch_cluster_types)
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -477,9 +492,110 @@ int ensure_merge(scvod_ctx* c) {
     return SCVOD_OK;
 }
 
+// scratch of the region growing for chunks of up to `chunk` points, and its outputs over the ctx's capacity: allocated on first use
+constexpr int64_t kRgChunkPts = 1 << 23;  // points of the scans of one chunk (more only when a single scan is larger)
+int ensure_rgrow(scvod_ctx* c, int64_t chunk) {
+    const size_t N = (size_t)c->cap_pts;
+    RgJob& J = c->rg;
+    if (!c->rg_out) {
+        Carver k{nullptr};
+        for (int pass = 0; pass < 2; ++pass) {
+            k = Carver{(unsigned char*)c->rg_out};
+            J.cls = k.take<uint8_t>(N);
+            J.out_nc = k.take<float4>(N);
+            J.out_seg = k.take<int32_t>(N);
+            J.stats = k.take<int32_t>(8);
+            J.cnt = k.take<int32_t>(2);
+            if (pass == 0) {
+                c->rg_out_bytes = align_up(k.off, 256);
+                HIPCHK(c, hipMalloc(&c->rg_out, c->rg_out_bytes));
+                c->side_bytes += c->rg_out_bytes;
+            }
+        }
+        HIPCHK(c, hipEventCreateWithFlags(&c->rg_ev, hipEventDisableTiming));
+    }
+    if (c->rg_cap >= chunk) return SCVOD_OK;
+    if (c->rg_buf) {
+        HIPCHK(c, hipStreamSynchronize(c->last_stream));
+        HIPCHK(c, hipFree(c->rg_buf));
+        HIPCHK(c, hipFree(c->rg_sort_tmp));
+        c->side_bytes -= c->rg_buf_bytes + c->rg_sort_bytes;
+        c->rg_buf = c->rg_sort_tmp = nullptr;
+    }
+    const size_t C = (size_t)chunk;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver k{(unsigned char*)c->rg_buf};
+        J.bmin = k.take<uint32_t>(3 * C);
+        J.bmax = k.take<uint32_t>(3 * C);
+        J.bcnt = k.take<int32_t>(C);
+        J.key_in = k.take<uint64_t>(C);
+        J.key_out = k.take<uint64_t>(C);
+        J.cl = k.take<int2>(C);
+        J.cl_name = k.take<int32_t>(C);
+        J.grid = k.take<float4>(2 * C);
+        J.cell = k.take<int32_t>(3 * C);
+        J.pcell = k.take<int32_t>(C);
+        J.cell_pts = k.take<int32_t>(C);
+        J.pos_cl = k.take<int32_t>(C);
+        J.pl = k.take<int2>(C);
+        J.cxyz = k.take<float4>(C);
+        J.nbr = k.take<int32_t>(16 * C);
+        J.nrm = k.take<float4>(C);
+        J.emask = k.take<uint16_t>(C);
+        J.lab = k.take<uint64_t>(C);
+        J.segc = k.take<int32_t>(C);
+        J.tail = k.take<int32_t>(C);
+        if (pass == 0) {
+            c->rg_buf_bytes = align_up(k.off, 256);
+            HIPCHK(c, hipMalloc(&c->rg_buf, c->rg_buf_bytes));
+            c->rg_sort_bytes = rg_sort_bytes((int)chunk);
+            HIPCHK(c, hipMalloc(&c->rg_sort_tmp, c->rg_sort_bytes));
+            c->side_bytes += c->rg_buf_bytes + c->rg_sort_bytes;
+        }
+    }
+    c->rg_cap = chunk;
+    return SCVOD_OK;
+}
+
+// the region growing over the batch, chunk by chunk of scans, on stream st
+int run_rgrow(scvod_ctx* c, hipStream_t st) {
+    const int B = c->A.n_scans;
+    const std::vector<int32_t>& off = c->h_scan_off;
+    int64_t need = 1;
+    for (int s0 = 0; s0 < B;) {
+        int s1 = s0 + 1;
+        while (s1 < B && s1 - s0 < 65535 && (int64_t)off[s1 + 1] - off[s0] <= kRgChunkPts) ++s1;
+        need = std::max(need, (int64_t)off[s1] - off[s0]);
+        s0 = s1;
+    }
+    int rc = ensure_rgrow(c, need);
+    if (rc) return rc;
+    RgJob& J = c->rg;
+    J.k = c->rg_k;
+    J.min_seg = c->rg_min_seg;
+    J.max_seg = 1000000;  // setMaxClusterSize (ssc.cpp:808)
+    J.cos_t = c->rg_cos;
+    J.curv_thr = c->rg_curv;
+    J.frac = c->rg_frac;
+    J.from_apri = c->batch_mode == 2 ? 1 : 0;
+    HIPCHK(c, hipMemsetAsync(J.stats, 0, 8 * sizeof(int32_t), st));
+    for (int s0 = 0; s0 < B;) {
+        int s1 = s0 + 1;
+        while (s1 < B && s1 - s0 < 65535 && (int64_t)off[s1 + 1] - off[s0] <= kRgChunkPts) ++s1;
+        J.s0 = s0;
+        J.ns = s1 - s0;
+        J.off0 = off[s0];
+        launch_rgrow(c->dev, c->A, J, (int)(off[s1] - off[s0]), c->rg_sort_tmp, c->rg_sort_bytes, st, timer_hook, c);
+        s0 = s1;
+    }
+    HIPCHK(c, hipGetLastError());
+    return SCVOD_OK;
+}
+
 // everything after the clustering reads the partition through A.pt_cluster: the fused one after a merged clustering.  A new batch
 // or clustering starts from the arena's own array again.
 void unmerge_view(scvod_ctx* c) {
+    c->rg_done = false;  // (the region growing's outputs belong to the clustering they were computed on)
     if (c->pt_cluster_own) c->A.pt_cluster = c->pt_cluster_own;
     c->merged = false;
     c->im_overflow = -1;
@@ -1187,6 +1303,10 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->d_labels) hipFree(c->d_labels);
     if (c->d_apri) hipFree(c->d_apri);
     if (c->im_buf) hipFree(c->im_buf);
+    if (c->rg_buf) hipFree(c->rg_buf);
+    if (c->rg_sort_tmp) hipFree(c->rg_sort_tmp);
+    if (c->rg_out) hipFree(c->rg_out);
+    if (c->rg_ev) hipEventDestroy(c->rg_ev);
     if (c->chain_ws) hipFree(c->chain_ws);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
@@ -1445,10 +1565,24 @@ int scvod_batch_cluster_types(scvod_ctx* c, void* stream, int32_t sync) {
     if (!c->clusters_valid) return fail(c, SCVOD_ERR_STATE, "scvod_batch_cluster_types needs scvod_batch_cluster first");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t prev = c->last_stream;
     c->last_stream = st;
     // (nothing is launched here: the max_name pass keeps running beside what follows)
     c->tim_used = 0;
-    // the boxes and the type rules are evaluated by the clustering kernel itself (same workgroup, boxes in LDS): nothing to launch
+    // the boxes and the type rules are evaluated by the clustering kernel itself (same workgroup, boxes in LDS): nothing to launch,
+    // unless the region growing is on (scvod_k_rgrow.inc)
+    c->rg_done = false;
+    if (c->rg_on) {
+        if (int rc = merge_check(c)) return rc;
+        int rc = ensure_rgrow(c, 1);
+        if (rc) return rc;
+        if (prev && prev != st) {  // the clustering ran on another stream
+            HIPCHK(c, hipEventRecord(c->rg_ev, prev));
+            HIPCHK(c, hipStreamWaitEvent(st, c->rg_ev, 0));
+        }
+        if ((rc = run_rgrow(c, st))) return rc;
+        c->rg_done = true;
+    }
     c->types_valid = true;
     c->track_valid = false;
     c->tables_valid = false;
@@ -1471,6 +1605,69 @@ int scvod_batch_fetch_cluster_types(scvod_ctx* c, int32_t s, int32_t car_label, 
     if (n) HIPCHK(c, hipMemcpy(t.data(), c->A.pt_type + c->h_scan_off[s], (size_t)n, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) h_type[i] = t[i] == 0 ? -1 : (t[i] == 2 ? car_label : other_label);
     return n;
+}
+
+int scvod_batch_fetch_cluster_classes(scvod_ctx* c, int32_t s, int32_t car_label, int32_t building_label, int32_t tree_label,
+                                      int32_t* h_type, int32_t cap) {
+    if (!c || !h_type) return SCVOD_ERR_INVALID;
+    if (!c->types_valid) return fail(c, SCVOD_ERR_STATE, "no cluster types computed for the last batch");
+    int rc = ensure_counts(c);
+    if (rc) return rc;
+    if (s < 0 || s >= c->A.n_scans) return fail(c, SCVOD_ERR_INVALID, "scan %d out of range", s);
+    const int32_t n = c->h_counts[(size_t)s * 8 + 4];
+    if (n > cap) return fail(c, SCVOD_ERR_CAPACITY, "output buffer too small (%d < %d)", cap, n);
+    HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    if ((rc = merge_check(c))) return rc;
+    std::vector<uint8_t> t(n ? n : 1);
+    const uint8_t* src = c->rg_done ? c->rg.cls : c->A.pt_type;  // (without the stage: pt_type, whose `other` is tree)
+    if (n) HIPCHK(c, hipMemcpy(t.data(), src + c->h_scan_off[s], (size_t)n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) h_type[i] = t[i] == 0 ? -1 : (t[i] == 2 ? car_label : (t[i] == 3 ? building_label : tree_label));
+    return n;
+}
+
+int scvod_batch_fetch_region_growing(scvod_ctx* c, int32_t s, float* h_normal_curv, int32_t* h_segment, int32_t cap) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!c->types_valid || !c->rg_done)
+        return fail(c, SCVOD_ERR_STATE, "no region growing ran on the last clustering (scvod_set_region_growing, scvod_batch_cluster_types)");
+    int rc = ensure_counts(c);
+    if (rc) return rc;
+    if (s < 0 || s >= c->A.n_scans) return fail(c, SCVOD_ERR_INVALID, "scan %d out of range", s);
+    const int32_t n = c->h_counts[(size_t)s * 8 + 4];
+    if (n > cap) return fail(c, SCVOD_ERR_CAPACITY, "output buffer too small (%d < %d)", cap, n);
+    HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    const size_t o = (size_t)c->h_scan_off[s];
+    if (n && h_normal_curv) HIPCHK(c, hipMemcpy(h_normal_curv, c->rg.out_nc + o, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    if (n && h_segment) HIPCHK(c, hipMemcpy(h_segment, c->rg.out_seg + o, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return n;
+}
+
+int scvod_batch_region_growing_stats(scvod_ctx* c, int32_t* h_out8) {
+    if (!c || !h_out8) return SCVOD_ERR_INVALID;
+    if (!c->types_valid) return fail(c, SCVOD_ERR_STATE, "no cluster types computed for the last batch");
+    for (int k = 0; k < 8; ++k) h_out8[k] = 0;
+    if (!c->rg_done) return SCVOD_OK;
+    HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    HIPCHK(c, hipMemcpy(h_out8, c->rg.stats, 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    h_out8[7] = 0;
+    return SCVOD_OK;
+}
+
+int scvod_set_region_growing(scvod_ctx* c, int32_t on, int32_t k, int32_t min_segment, double smoothness_deg, float curvature_threshold,
+                             double plane_fraction) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (k < 1 || k > 16) return fail(c, SCVOD_ERR_INVALID, "region growing: k %d outside 1..16", k);
+    if (min_segment < 1) return fail(c, SCVOD_ERR_INVALID, "region growing: min_segment %d < 1", min_segment);
+    if (!(smoothness_deg > 0.0 && smoothness_deg <= 90.0)) return fail(c, SCVOD_ERR_INVALID, "region growing: smoothness outside (0, 90] degrees");
+    if (!(plane_fraction >= 0.0 && plane_fraction <= 1.0)) return fail(c, SCVOD_ERR_INVALID, "region growing: plane fraction outside [0, 1]");
+    if (curvature_threshold != curvature_threshold) return fail(c, SCVOD_ERR_INVALID, "region growing: NaN curvature threshold");
+    c->rg_on = on != 0;
+    c->rg_k = k;
+    c->rg_min_seg = min_segment;
+    c->rg_cos = cosf((float)(smoothness_deg / 180.0 * M_PI));  // setSmoothnessThreshold(float) and validatePoint's cosf, on the host
+    c->rg_curv = curvature_threshold;
+    c->rg_frac = plane_fraction;
+    c->rg_done = false;
+    return SCVOD_OK;
 }
 
 int scvod_cluster(scvod_ctx* c, const scvod_apri* h_apri, int32_t n, int32_t* h_pt_cluster) {

@@ -474,15 +474,21 @@ __device__ __forceinline__ bool cc_search_windows(const CcKeys<TabT>& K, int* pa
     return true;
 }
 
+// box area of a cluster (getDescriptorByEigenValue's f_11(0, 7)): float extents, double product
+__device__ __forceinline__ double cc_box_square(float mnx, float mny, float mxx, float mxy) { return (double)(mxx - mnx) * (double)(mxy - mny); }
 // type of a cluster from its box and member count: refineClusterByBoundingBox (ssc.cpp:437-467) + the box part of recognize
 // (ssc.cpp:849-872).  0 erased, 1 other, 2 car.  Shared by the clustering and the intensity merge (scvod_k_merge.inc).
 __device__ __forceinline__ uint32_t cc_type_rule(const DevParams& P, float mnx, float mny, float mnz, float mxx, float mxy, float mxz, int cnt) {
     const float diff_zf = mxz - mnz;
     if (mnz > 0.f || cnt < P.to_be_class || diff_zf < 0.2f) return 0;
-    const double square = (double)(mxx - mnx) * (double)(mxy - mny);
+    const double square = cc_box_square(mnx, mny, mxx, mxy);
     if (square > (double)P.car_square) return 1;
     if ((double)mnz < (double)P.min_z && square < (double)P.car_square && (double)mxz < (double)P.max_z) return 2;
     return 1;
+}
+// a cluster of type 1 that recognize hands to regionGrowing (ssc.cpp:849): the `square > car_square` branch of cc_type_rule
+__device__ __forceinline__ bool cc_rg_candidate(const DevParams& P, float mnx, float mny, float mxx, float mxy) {
+    return cc_box_square(mnx, mny, mxx, mxy) > (double)P.car_square;
 }
 __device__ __forceinline__ uint32_t f2ord(float f) { return float_sort_key(f); }
 __device__ __forceinline__ float ord2f(uint32_t u) { return u2f((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }

@@ -223,6 +223,42 @@ struct MergeJob {
 };
 constexpr int kImPairsPerPt = 4, kImPairsPerScan = 256;
 
+// region growing of the large clusters (SSC::recognize / regionGrowing, ssc.cpp:797-860; scvod_k_rgrow.inc), opt-in.  One job per
+// chunk of scans [s0, s0 + ns): chunk points are numbered g = scan_off[s] - off0 + i, stage positions p are the candidates' points
+// in (scan, cluster, apri index) order.  Scratch (chunk capacity C points) and batch-wide outputs (indexed scan_off[s] + i).
+struct RgJob {
+    int32_t k, min_seg, max_seg;   // neighbours (<= 16), kept segment sizes
+    float cos_t, curv_thr;         // cosf(smoothness), curvature threshold
+    double frac;                   // building iff kept points >= n * frac
+    int32_t s0, ns, from_apri;
+    int64_t off0;                  // scan_off[s0]
+    uint32_t* bmin;                // [3 C] per chunk point (as a cluster name): box minimum (order-preserving encoding)
+    uint32_t* bmax;                // [3 C] ... maximum
+    int32_t* bcnt;                 // [C] ... member count
+    uint64_t* key_in;              // [C] (name << 32 | g) of the candidates' points, unused slots ~0
+    uint64_t* key_out;             // [C] sorted
+    int32_t* cnt;                  // [2] candidate points, candidate clusters of the chunk
+    int2* cl;                      // [C] per cluster: first position, points
+    int32_t* cl_name;              // [C] per cluster: its name (chunk point)
+    float4* grid;                  // [2 C] per cluster: origin, cell size; cells per axis
+    int32_t* cell;                 // [3 C] per cluster at 3 p0: CSR cell ends
+    int32_t* pcell;                // [C] per position: its cell
+    int32_t* cell_pts;             // [C] positions in cell order
+    int32_t* pos_cl;               // [C] per position: cluster
+    int2* pl;                      // [C] per position: scan, apri index
+    float4* cxyz;                  // [C] per position: coordinates
+    int32_t* nbr;                  // [k C] per position: the k_eff nearest positions of its cluster
+    float4* nrm;                   // [C] per position: normal, curvature
+    uint16_t* emask;               // [C] per position: valid edges to its neighbours
+    uint64_t* lab;                 // [C] labels of the clusters on the HBM path
+    int32_t* segc;                 // [C] per owner position: its segment's size
+    int32_t* tail;                 // [C] per cluster: its tail points
+    uint8_t* cls;                  // [N] per apri point: 0 erased, 1 tree, 2 car, 3 building
+    float4* out_nc;                // [N] per apri point: normal, curvature (NaN for non-candidates)
+    int32_t* out_seg;              // [N] per apri point: apri index of its segment's seed, -1 for non-candidates
+    int32_t* stats;                // [8] see scvod_batch_region_growing_stats
+};
+
 typedef void (*TimerHook)(void* user, const char* name, int begin);
 
 // Launches.  `th`/`tu` optional per-kernel timing hook (called before and after each launch).
@@ -244,6 +280,9 @@ void launch_cls(const Arena& A, int s, size_t scan_base, int n_points, hipStream
 void launch_cluster(const DevParams& P, const Arena& A, int from_apri, hipStream_t st, TimerHook th, void* tu);
 size_t merge_lds_bytes(const DevParams& P, int max_scan_pts);  // dynamic LDS of k_im_merge: row starts + invalid bitmap
 void launch_merge(const DevParams& P, const Arena& A, const MergeJob& M, int from_apri, hipStream_t st, TimerHook th, void* tu);
+size_t rg_sort_bytes(int chunk_pts);  // temporary storage of the radix sort of a chunk's keys
+void launch_rgrow(const DevParams& P, const Arena& A, const RgJob& J, int chunk_pts, void* sort_tmp, size_t sort_bytes, hipStream_t st,
+                  TimerHook th, void* tu);
 void launch_merge_lastname(const Arena& A, const MergeJob& M, hipStream_t st, TimerHook th, void* tu);  // carrier of max_name -> its fusion
 void launch_lastname(const DevParams& P, const Arena& A, hipStream_t st, hipStream_t st2, hipStream_t st3, hipEvent_t ev_fork, hipEvent_t ev_join2,
                      hipEvent_t ev_join3, TimerHook th, void* tu);

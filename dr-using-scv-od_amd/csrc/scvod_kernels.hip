@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "scvod_dev.h"
+#include <rocprim/device/device_radix_sort.hpp>
 
 namespace scvod {
 
@@ -360,6 +361,7 @@ __device__ __forceinline__ void block_bitonic_merge_stages(T* a, int np2) {
 #include "scvod_k_voxels.inc"  // PointAPRI expansion, direct binning, the voxel stage: buckets, LDS sort, per-voxel descriptors (A4-A5)
 #include "scvod_k_cluster.inc"  // curved-voxel clustering, boxes, type rules, successor tables: k_cc_scan
 #include "scvod_k_merge.inc"  // intensity merge of the clusters (ssc.cpp:571-635), opt-in: k_im_merge
+#include "scvod_k_rgrow.inc"  // building / tree of the large clusters by region growing (ssc.cpp:797-860), opt-in: k_rg_*
 #include "scvod_k_probe_nn.inc"  // per-pair tracking probe of the facade path (A6 bulk part) and the brute-force correspondence search (A7)
 // ------------------------------------------------------------------------------------------
 // host-side launch sequences
@@ -616,6 +618,50 @@ void launch_merge(const DevParams& P, const Arena& A, const MergeJob& M, int fro
     TH_BEGIN("im_tables");
     hipLaunchKernelGGL(k_im_tables, dim3(B), dim3(kImThreads), 0, st, P, A, M, from_apri);
     TH_END("im_tables");
+}
+
+size_t rg_sort_bytes(int chunk_pts) {
+    size_t bytes = 0;
+    rocprim::radix_sort_keys(nullptr, bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)chunk_pts, 0, 64, (hipStream_t)0);
+    return bytes;
+}
+
+void launch_rgrow(const DevParams& P, const Arena& A, const RgJob& J, int chunk_pts, void* sort_tmp, size_t sort_bytes, hipStream_t st,
+                  TimerHook th, void* tu) {
+    if (J.ns <= 0 || chunk_pts <= 0 || A.max_scan_pts <= 0) return;
+    int bits = 1;
+    while (bits < 31 && (1ll << bits) < chunk_pts) ++bits;
+    hipMemsetAsync(J.bmin, 0xff, sizeof(uint32_t) * 3 * (size_t)chunk_pts, st);
+    hipMemsetAsync(J.bmax, 0, sizeof(uint32_t) * 3 * (size_t)chunk_pts, st);
+    hipMemsetAsync(J.bcnt, 0, sizeof(int32_t) * (size_t)chunk_pts, st);
+    hipMemsetAsync(J.key_in, 0xff, sizeof(uint64_t) * (size_t)chunk_pts, st);
+    hipMemsetAsync(J.cnt, 0, 2 * sizeof(int32_t), st);
+    const dim3 gs((A.max_scan_pts + kRgThreads - 1) / kRgThreads, J.ns);
+    const int gp = (chunk_pts + kRgThreads - 1) / kRgThreads;
+    TH_BEGIN("rg_select");
+    hipLaunchKernelGGL(k_rg_box, gs, dim3(kRgThreads), 0, st, A, J);
+    hipLaunchKernelGGL(k_rg_select, gs, dim3(kRgThreads), 0, st, P, A, J);
+    TH_END("rg_select");
+    TH_BEGIN("rg_sort");
+    size_t b = sort_bytes;
+    rocprim::radix_sort_keys(sort_tmp, b, J.key_in, J.key_out, (size_t)chunk_pts, 0, 32 + bits + 1, st);
+    hipLaunchKernelGGL(k_rg_group, dim3(gp), dim3(kRgThreads), 0, st, A, J);
+    TH_END("rg_sort");
+    TH_BEGIN("rg_grid");
+    hipLaunchKernelGGL(k_rg_grid, dim3(2048), dim3(kRgThreads), 0, st, J);
+    TH_END("rg_grid");
+    TH_BEGIN("rg_knn");
+    hipLaunchKernelGGL(k_rg_knn, dim3(gp), dim3(kRgThreads), 0, st, J);
+    TH_END("rg_knn");
+    TH_BEGIN("rg_normal");
+    hipLaunchKernelGGL(k_rg_normal, dim3(gp), dim3(kRgThreads), 0, st, A, J);
+    hipLaunchKernelGGL(k_rg_edges, dim3(gp), dim3(kRgThreads), 0, st, J);
+    TH_END("rg_normal");
+    TH_BEGIN("rg_grow");
+    const size_t lds = sizeof(unsigned long long) * kRgLdsPts;
+    hipFuncSetAttribute((const void*)k_rg_grow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_rg_grow, dim3(2048), dim3(kRgThreads), lds, st, A, J);
+    TH_END("rg_grow");
 }
 
 void launch_merge_lastname(const Arena& A, const MergeJob& M, hipStream_t st, TimerHook th, void* tu) {

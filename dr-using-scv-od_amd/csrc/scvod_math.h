@@ -776,5 +776,187 @@ SCVOD_HD void svd3_jacobi(const float cov[9], Svd3& out) {
     for (int i = 0; i < 9; ++i) out.U[i] = U[i];
 }
 
+// ---- fp32 sin / cos (the closed-form cubic of pcl::computeRoots).  The reference calls glibc's sinf / cosf; they are restated
+// here by a double evaluation rounded once to float, the same on the host and on the device: argument reduction by the nearest
+// multiple of pi/2 (fdlibm's two-part pi/2, exact for |x| < 2^20), then Taylor series to x^17 / x^16 on |r| <= pi/4 (truncation
+// below 1e-18 relative).  Almost always the correctly rounded result; glibc's are within 0.56 ulp, so a few results differ from
+// glibc in the last bit (DESIGN section 2 gives the count over [0, pi/3], tests/test_region_growing_ref.py checks it). ----------
+SCVOD_HD double sin_poly_d(double r) {
+    const double z = r * r;
+    double p = 1.0 / 355687428096000.0;                   // 1/17!
+    p = p * z - 1.0 / 1307674368000.0;                    // 1/15!
+    p = p * z + 1.0 / 6227020800.0;                       // 1/13!
+    p = p * z - 1.0 / 39916800.0;                         // 1/11!
+    p = p * z + 1.0 / 362880.0;                           // 1/9!
+    p = p * z - 1.0 / 5040.0;                             // 1/7!
+    p = p * z + 1.0 / 120.0;                              // 1/5!
+    p = p * z - 1.0 / 6.0;                                // 1/3!
+    return r + r * (z * p);
+}
+SCVOD_HD double cos_poly_d(double r) {
+    const double z = r * r;
+    double p = 1.0 / 20922789888000.0;                    // 1/16!
+    p = p * z - 1.0 / 87178291200.0;                      // 1/14!
+    p = p * z + 1.0 / 479001600.0;                        // 1/12!
+    p = p * z - 1.0 / 3628800.0;                          // 1/10!
+    p = p * z + 1.0 / 40320.0;                            // 1/8!
+    p = p * z - 1.0 / 720.0;                              // 1/6!
+    p = p * z + 1.0 / 24.0;                               // 1/4!
+    p = p * z - 0.5;                                      // 1/2!
+    return 1.0 + z * p;
+}
+// quadrant q of x and the reduced argument r = x - q pi/2
+SCVOD_HD double trig_reduce(float x, int* q) {
+    const double xd = (double)x;
+    const double k = __builtin_rint(xd * 6.36619772367581382433e-01);  // 2/pi
+    *q = (int)((long long)k & 3);
+    return (xd - k * 1.57079632673412561417e+00) - k * 6.07710050650619224932e-11;
+}
+SCVOD_HD float sin_f32(float x) {
+    if (!(fabs_f(x) < 1048576.f)) return x - x;  // NaN / inf -> NaN; |x| >= 2^20 is outside the domain (never met here)
+    int q;
+    const double r = trig_reduce(x, &q);
+    const double v = (q & 1) ? cos_poly_d(r) : sin_poly_d(r);
+    return (float)((q & 2) ? -v : v);
+}
+SCVOD_HD float cos_f32(float x) {
+    if (!(fabs_f(x) < 1048576.f)) return x - x;
+    int q;
+    const double r = trig_reduce(x, &q);
+    const double v = (q & 1) ? sin_poly_d(r) : cos_poly_d(r);
+    return (float)(((q + 1) & 2) ? -v : v);
+}
+
+// ---- smallest eigenpair of a symmetric 3x3 float matrix: pcl::eigen33(mat, eigenvalue, eigenvector) of PCL 1.8
+// (common/include/pcl/common/impl/eigen.hpp) with pcl::computeRoots / computeRoots2, in pure fp32 (row-major m[9]).  Eigen's
+// reductions over three terms (squaredNorm, dot) add as a + (b + c); std::sin / std::cos / std::atan2 are sin_f32 / cos_f32 /
+// atan2_f32.  Returns the eigenvalue scaled back; v is the normalised largest row cross product (NaN for a zero matrix). ----------
+SCVOD_HD void eig_roots2_f32(float b, float c, float r[3]) {
+    r[0] = 0.f;
+    float d = (float)((double)(b * b) - 4.0 * (double)c);  // Scalar(b * b - 4.0 * c): the 4.0 is a double
+    if ((double)d < 0.0) d = 0.f;
+    const float sd = sqrt_f(d);
+    r[2] = 0.5f * (b + sd);
+    r[1] = 0.5f * (b - sd);
+}
+SCVOD_HD void eig_roots_f32(const float m[9], float r[3]) {
+    const float m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[4], m12 = m[5], m22 = m[8];
+    const float c0 = m00 * m11 * m22 + 2.f * m01 * m02 * m12 - m00 * m12 * m12 - m11 * m02 * m02 - m22 * m01 * m01;
+    const float c1 = m00 * m11 - m01 * m01 + m00 * m22 - m02 * m02 + m11 * m22 - m12 * m12;
+    const float c2 = m00 + m11 + m22;
+    if (fabs_f(c0) < 1.1920928955078125e-07f) {  // Eigen::NumTraits<float>::epsilon()
+        eig_roots2_f32(c2, c1, r);
+        return;
+    }
+    const float s_inv3 = (float)(1.0 / 3.0);
+    const float s_sqrt3 = sqrt_f(3.f);
+    const float c2_over_3 = c2 * s_inv3;
+    float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
+    if (a_over_3 > 0.f) a_over_3 = 0.f;
+    const float half_b = 0.5f * (c0 + c2_over_3 * (2.f * c2_over_3 * c2_over_3 - c1));
+    float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
+    if (q > 0.f) q = 0.f;
+    const float rho = sqrt_f(-a_over_3);
+    const float theta = atan2_f32(sqrt_f(-q), half_b) * s_inv3;
+    const float cos_theta = cos_f32(theta);
+    const float sin_theta = sin_f32(theta);
+    r[0] = c2_over_3 + 2.f * rho * cos_theta;
+    r[1] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
+    r[2] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
+    float t;
+    if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
+    if (r[1] >= r[2]) {
+        t = r[1]; r[1] = r[2]; r[2] = t;
+        if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
+    }
+    if (r[0] <= 0.f) eig_roots2_f32(c2, c1, r);
+}
+SCVOD_HD void eigen33_min_f32(const float mat[9], float* eigenvalue, float v[3]) {
+    float scale = 0.f;
+    for (int i = 0; i < 9; ++i) {
+        const float a = fabs_f(mat[i]);
+        if (a > scale) scale = a;  // (Eigen's maxCoeff: the first of equal maxima; NaN never replaces)
+    }
+    if (scale <= 1.17549435082228750797e-38f) scale = 1.f;  // std::numeric_limits<float>::min()
+    float m[9];
+    for (int i = 0; i < 9; ++i) m[i] = mat[i] / scale;
+    float r[3];
+    eig_roots_f32(m, r);
+    *eigenvalue = r[0] * scale;
+    m[0] -= r[0];
+    m[4] -= r[0];
+    m[8] -= r[0];
+    float c[3][3];
+    const int ra[3] = {0, 0, 1}, rb[3] = {1, 2, 2};  // rows (0,1), (0,2), (1,2)
+    float len[3];
+    for (int k = 0; k < 3; ++k) {
+        const float* a = m + 3 * ra[k];
+        const float* b = m + 3 * rb[k];
+        c[k][0] = a[1] * b[2] - a[2] * b[1];
+        c[k][1] = a[2] * b[0] - a[0] * b[2];
+        c[k][2] = a[0] * b[1] - a[1] * b[0];
+        len[k] = c[k][0] * c[k][0] + (c[k][1] * c[k][1] + c[k][2] * c[k][2]);
+    }
+    const int k = (len[0] >= len[1] && len[0] >= len[2]) ? 0 : ((len[1] >= len[0] && len[1] >= len[2]) ? 1 : 2);
+    const float n = sqrt_f(len[k]);
+    v[0] = c[k][0] / n;
+    v[1] = c[k][1] / n;
+    v[2] = c[k][2] / n;
+}
+
+// ---- normal and curvature of one point from its neighbours, NormalEstimation::computePointNormal (PCL 1.8): the covariance of
+// computeMeanAndCovarianceMatrix in its indices form (Scalar = float; nine sums in list order, divided by the count, diagonal
+// E[xx] - mean^2), then solvePlaneParameters.  xyz: the cnt neighbours' coordinates in list order.  out = {nx, ny, nz, curvature};
+// NaN everywhere for fewer than 3 neighbours. ---------------------------------------------------------------------------------
+template <typename GetXyz>
+SCVOD_HD void point_normal_f32(int cnt, GetXyz xyz, float out[4]) {
+    if (cnt < 3) {
+        const float nan = u2f(0x7fc00000u);
+        out[0] = out[1] = out[2] = out[3] = nan;
+        return;
+    }
+    float a[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < cnt; ++j) {
+        float x, y, z;
+        xyz(j, x, y, z);
+        a[0] += x * x;
+        a[1] += x * y;
+        a[2] += x * z;
+        a[3] += y * y;
+        a[4] += y * z;
+        a[5] += z * z;
+        a[6] += x;
+        a[7] += y;
+        a[8] += z;
+    }
+    const float fc = (float)cnt;
+    for (int i = 0; i < 9; ++i) a[i] = a[i] / fc;
+    float cov[9];
+    cov[0] = a[0] - a[6] * a[6];
+    cov[1] = a[1] - a[6] * a[7];
+    cov[2] = a[2] - a[6] * a[8];
+    cov[4] = a[3] - a[7] * a[7];
+    cov[5] = a[4] - a[7] * a[8];
+    cov[8] = a[5] - a[8] * a[8];
+    cov[3] = cov[1];
+    cov[6] = cov[2];
+    cov[7] = cov[5];
+    float ev, v[3];
+    eigen33_min_f32(cov, &ev, v);
+    out[0] = v[0];
+    out[1] = v[1];
+    out[2] = v[2];
+    const float eig_sum = cov[0] + cov[4] + cov[8];
+    out[3] = eig_sum != 0.f ? fabs_f(ev / eig_sum) : 0.f;
+}
+
+// RegionGrowing::validatePoint in smooth mode: q joins p's segment unless |n_q . n_p| < cos(theta) (NaN passes)
+SCVOD_HD bool rg_smooth_ok(const float* nq, const float* np, float cos_t) {
+    const float d = nq[0] * np[0] + (nq[1] * np[1] + nq[2] * np[2]);
+    return !(fabs_f(d) < cos_t);
+}
+// seed rank of a curvature: ascending, NaN before every finite value
+SCVOD_HD uint32_t rg_curv_key(float c) { return c != c ? 0u : float_sort_key(c); }
+
 }  // namespace scvod
 #endif  // SCVOD_MATH_H_

@@ -104,7 +104,13 @@ int main(int argc, char** argv) {
             }
             dyn_total += dyn;
             std::cout << "frame " << ssc.frame_set[i].id << " points " << ssc.cloud_vec[i]->points.size() << " clusters " << ssc.frame_set[i].cluster_set.size()
-                      << " tracked " << cars << " dynamic " << dyn << "\n";
+                      << " tracked " << cars << " dynamic " << dyn;
+            if (ssc.device_region_growing) {  // (only with the key: the line stays as it was otherwise)
+                int buildings = 0;
+                for (auto& kv : ssc.frame_set[i].cluster_set) buildings += kv.second.type == ssc.building;
+                std::cout << " buildings " << buildings;
+            }
+            std::cout << "\n";
         }
         std::cout << "frames " << n << " dynamic_total " << dyn_total << "\n";
     } catch (const std::exception& e) {

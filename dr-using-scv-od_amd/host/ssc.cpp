@@ -37,6 +37,8 @@ SSC::SSC(const std::string& yaml_path, int device, int max_points) {
     if (rc != SCVOD_OK) throw std::runtime_error("scvod_create failed (status " + std::to_string(rc) + "): the SCV-OD hot path is GPU-only");
     // ssc.cpp:644 (refineClusterByIntensity between the clustering and the box refine): on request, with the four YAML keys
     if (device_intensity_merge) chk(ctx_, scvod_set_intensity_merge(ctx_, iteration, search_c, intensity_diff, intensity_cov), "scvod_set_intensity_merge");
+    // ssc.cpp:797-860 (regionGrowing inside recognize): on request, with the reference's hard-coded values
+    chk(ctx_, scvod_set_region_growing(ctx_, device_region_growing, 10, 20, 10.0, 1.2f, 0.2), "scvod_set_region_growing");
     PatchworkGroundSeg->attach(ctx_);
 }
 
@@ -166,7 +168,8 @@ void SSC::segmentGpu() {
     std::vector<int> names(n ? n : 1), types(n ? n : 1);
     chk(ctx_, scvod_cluster(ctx_, apri_vec.data(), n, names.data()), "scvod_cluster");
     chk(ctx_, scvod_batch_cluster_types(ctx_, nullptr, 1), "scvod_batch_cluster_types");
-    int rc = scvod_batch_fetch_cluster_types(ctx_, 0, car, tree, types.data(), n);
+    int rc = device_region_growing ? scvod_batch_fetch_cluster_classes(ctx_, 0, car, building, tree, types.data(), n)
+                                   : scvod_batch_fetch_cluster_types(ctx_, 0, car, tree, types.data(), n);
     if (rc < 0) chk(ctx_, rc, "scvod_batch_fetch_cluster_types");
     frame_ssc.cluster_set.clear();
     int max_name = 4;

@@ -52,7 +52,8 @@ class SSC : public Utility {
     void segDF();
     // GPU stand-in for segment() + recognize() when the reference's PCL host code is not linked: curved-voxel
     // clustering (ssc.cpp:299-393) + bounding-box refine / recognise rules (ssc.cpp:437-467, 849-872);
-    // no intensity merge, no region growing (building and tree both become `tree`).
+    // the intensity merge and the region growing of recognize (building / tree) run on the device when the facade-only keys
+    // ssc/device_intensity_merge_ / ssc/device_region_growing_ ask for them; without the latter building and tree both become `tree`.
     void segmentGpu();
     // The per-scan body of getCloud (ssc.cpp:1063-1106) without the file I/O: label filter (label & 0xFFFF in {0, 1}
     // skipped), intensity * max_intensity, pcl::VoxelGrid 0.08 m -- the cloud that cloud_vec receives.

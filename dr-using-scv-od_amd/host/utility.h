@@ -74,6 +74,7 @@ class Utility {
     float max_intensity = 200.0f, correct_ratio = 0.5f, correct_radius = 0.5f;
     int search_num = 10, iteration = 3, toBeClass = 1, search_c = 2;
     int device_intensity_merge = 0;  // facade-only key ssc/device_intensity_merge_: 1 runs refineClusterByIntensity on the device
+    int device_region_growing = 0;   // facade-only key ssc/device_region_growing_: 1 separates building / tree by region growing on the device
     float intensity_diff = 50, intensity_cov = 20, occupancy = 0.6f;
     int building = 0, tree = 1, car = 2;
     std::vector<float> tr_v;
@@ -317,6 +318,7 @@ class Utility {
         y.param<float>("ssc/intensity_diff_", intensity_diff, 50.f);
         y.param<float>("ssc/intensity_cov_", intensity_cov, 20.f);
         y.param<int>("ssc/device_intensity_merge_", device_intensity_merge, 0);
+        y.param<int>("ssc/device_region_growing_", device_region_growing, 0);
         y.param<float>("ssc/occupancy_", occupancy, 0.6f);
         y.param<int>("ssc/building_", building, 0);
         y.param<int>("ssc/tree_", tree, 1);

@@ -137,6 +137,10 @@ def load_lib():
         "scvod_set_max_name_literal": (C.c_int, [vp, i32]),
         "scvod_set_intensity_merge": (C.c_int, [vp, i32, i32, f32, f32]),
         "scvod_batch_cluster_merge_stats": (C.c_int, [vp, vp]),
+        "scvod_set_region_growing": (C.c_int, [vp, i32, i32, i32, C.c_double, f32, C.c_double]),
+        "scvod_batch_fetch_cluster_classes": (C.c_int, [vp, i32, i32, i32, i32, vp, i32]),
+        "scvod_batch_fetch_region_growing": (C.c_int, [vp, i32, vp, vp, i32]),
+        "scvod_batch_region_growing_stats": (C.c_int, [vp, vp]),
         "scvod_batch_cluster_last_name": (C.c_int, [vp, vp, i32, vp]),
         "scvod_set_chain_capacity": (C.c_int, [vp, i64]),
         "scvod_chain_workspace_bytes": (i64, [vp]),
@@ -185,7 +189,7 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_bin_scan", "scvod_voxelize", "scvod_pose_delta", "scvod_track_probe", "scvod_batch_process",
                     "scvod_batch_counts", "scvod_batch_fetch", "scvod_batch_cluster", "scvod_batch_fetch_clusters", "scvod_cluster",
                     "scvod_batch_cluster_types", "scvod_batch_fetch_cluster_types",
-                    "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
+                    "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_set_region_growing", "scvod_batch_fetch_cluster_classes", "scvod_batch_fetch_region_growing", "scvod_batch_region_growing_stats", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
                     "scvod_map_create", "scvod_map_destroy", "scvod_map_last_error", "scvod_map_capacity", "scvod_map_clear",
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
                     "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid"]
@@ -510,6 +514,36 @@ class Ctx:
         out = np.zeros(4, np.int32)
         self._chk(self.lib.scvod_batch_cluster_merge_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return dict(clusters_before=int(out[0]), fusions=int(out[1]), clusters_after=int(out[2]), scans_fused=int(out[3]))
+
+    def set_region_growing(self, on=True, k=10, min_segment=20, smoothness_deg=10.0, curvature_threshold=1.2, plane_fraction=0.2):
+        """SSC::recognize's region growing (ssc.cpp:797-860) in scvod_batch_cluster_types: building / tree of the clusters above
+        car_square.  The defaults are the reference's values; off until called"""
+        self._chk(self.lib.scvod_set_region_growing(self.h, 1 if on else 0, int(k), int(min_segment), float(smoothness_deg),
+                                                    float(curvature_threshold), float(plane_fraction)))
+
+    def batch_fetch_cluster_classes(self, s, cap, car_label=2, building_label=0, tree_label=1):
+        """per apri point: -1 erased, car / building / tree label (utility.h's building 0, tree 1, car 2 by default)"""
+        out = np.zeros(max(cap, 1), np.int32)
+        n = self.lib.scvod_batch_fetch_cluster_classes(self.h, int(s), int(car_label), int(building_label), int(tree_label),
+                                                       out.ctypes.data_as(C.c_void_p), int(cap))
+        if n < 0:
+            self._chk(n)
+        return out[:n]
+
+    def batch_fetch_region_growing(self, s, cap):
+        """(normal_curv [n, 4] float32, NaN off the candidates; segment [n] int32: apri index of the segment's seed or -1)"""
+        nc = np.zeros((max(cap, 1), 4), np.float32)
+        seg = np.zeros(max(cap, 1), np.int32)
+        n = self.lib.scvod_batch_fetch_region_growing(self.h, int(s), nc.ctypes.data_as(C.c_void_p), seg.ctypes.data_as(C.c_void_p), int(cap))
+        if n < 0:
+            self._chk(n)
+        return nc[:n], seg[:n]
+
+    def batch_region_growing_stats(self):
+        out = np.zeros(8, np.int32)
+        self._chk(self.lib.scvod_batch_region_growing_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(candidate_clusters=int(out[0]), building_clusters=int(out[1]), candidate_points=int(out[2]), kept_edges=int(out[3]),
+                    max_rounds=int(out[4]), hbm_clusters=int(out[5]), tail_points=int(out[6]))
 
     def set_max_name_literal(self, literal=True):
         """ssc.cpp:354 keeps the LAST USED running number in Frame::max_name; False = fresh numbers (rounds 1-3)"""

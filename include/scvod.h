@@ -431,8 +431,8 @@ int scvod_batch_fetch_clusters(scvod_ctx* ctx, int32_t s, int32_t* h_pt_cluster,
  * (SSC::refineClusterByBoundingBox ssc.cpp:437-467, SSC::recognize ssc.cpp:849-872):
  * per apri point of scan s, h_type[i] = -1 when its cluster is erased (min z > 0, fewer than toBeClass
  * points, z extent < 0.2 m), `car_label` when bbox area <= car_square && min z < min_z && max z < max_z,
- * otherwise `other_label` (the reference separates building / tree with PCL region growing, which stays
- * on the host).  The intensity merge (ssc.cpp:571-635) is applied only when scvod_set_intensity_merge turned it on: the types are
+ * otherwise `other_label`: building and tree both (the reference separates them with PCL region growing;
+ * scvod_batch_fetch_cluster_classes returns that split when scvod_set_region_growing turned the stage on).  The intensity merge (ssc.cpp:571-635) is applied only when scvod_set_intensity_merge turned it on: the types are
  * then those of the fused clusters.  Returns the count or a negative status. */
 int scvod_batch_cluster_types(scvod_ctx* ctx, void* stream, int32_t sync);
 int scvod_batch_fetch_cluster_types(scvod_ctx* ctx, int32_t s, int32_t car_label, int32_t other_label, int32_t* h_type,
@@ -458,6 +458,29 @@ int scvod_set_intensity_merge(scvod_ctx* ctx, int32_t iterations, int32_t search
 /* h_out4 = {clusters before the merge, fusions recorded (all iterations), clusters after, scans with at least one fusion} of the
  * last clustering (zeros when the merge was off).  SCVOD_ERR_CAPACITY as above.  Synchronises. */
 int scvod_batch_cluster_merge_stats(scvod_ctx* ctx, int32_t* h_out4);
+/* Region growing of the large clusters, SSC::recognize / SSC::regionGrowing (ssc.cpp:797-860), run by scvod_batch_cluster_types on
+ * its stream when `on`.  Candidates are the clusters that the box rule sends down its `square > car_square` branch.  Per candidate
+ * (n points in apri index order): exact k nearest points (k_eff = min(k, n), the point itself included), PCA normal and curvature
+ * (NormalEstimation), smooth-mode region growing (smoothness_deg, curvature_threshold, segments of min_segment .. 10^6 points kept),
+ * building iff the kept points >= n * plane_fraction (in double), tree otherwise.  The reference's values are (1, 10, 20, 10, 1.2, 0.2).
+ * Off by default: nothing is launched and every output stays as it was; with it on, no other output changes either.  The
+ * conventions where PCL leaves the order open are fixed as DESIGN.md section 2 states.  SCVOD_ERR_INVALID for k outside 1..16,
+ * min_segment < 1, an angle outside (0, 90] or a fraction outside [0, 1].  Chunk scratch (about 240 bytes per point of up to 2^23
+ * points of scans) and outputs (21 bytes per point of the ctx's capacity) are allocated on first use (counted by scvod_arena_bytes). */
+int scvod_set_region_growing(scvod_ctx* ctx, int32_t on, int32_t k, int32_t min_segment, double smoothness_deg,
+                             float curvature_threshold, double plane_fraction);
+/* per apri point of scan s: -1 erased, car_label, building_label or tree_label.  Without the stage (off, or not run on the last
+ * clustering) every non-car cluster is tree_label.  Returns the count or a negative status. */
+int scvod_batch_fetch_cluster_classes(scvod_ctx* ctx, int32_t s, int32_t car_label, int32_t building_label, int32_t tree_label,
+                                      int32_t* h_type, int32_t cap);
+/* the stage's per-point results for scan s: h_normal_curv (4 floats per apri point: normal, curvature; NaN for the points of
+ * non-candidates) and h_segment (apri index of the seed that owns the point's segment, -1 for non-candidates); either may be NULL.
+ * SCVOD_ERR_STATE unless the stage ran on the last clustering.  Returns the count or a negative status. */
+int scvod_batch_fetch_region_growing(scvod_ctx* ctx, int32_t s, float* h_normal_curv, int32_t* h_segment, int32_t cap);
+/* h_out8 = {candidate clusters, building clusters, candidate points, kept edges (p -> q, q != p), largest number of propagation
+ * sweeps of a cluster, clusters on the HBM path (more than 8192 points), tail points, 0} of the last scvod_batch_cluster_types
+ * (zeros when the stage did not run).  Synchronises. */
+int scvod_batch_region_growing_stats(scvod_ctx* ctx, int32_t* h_out8);
 
 /* Streaming ingest of a sequence held in HOST memory (the reference reads one .bin per scan, SSC::getCloud
  * src/ssc.cpp:1040-1125): chunks of `chunk_scans` scans travel host -> device on a copy stream into one of two device
