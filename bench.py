@@ -26,11 +26,17 @@ At N = 1 there is no host synchronisation inside a step.  At N > 1 the boundary 
 the host (does any rank have to walk a chain again?); everything else stays on the stream.
 value = scans of all ranks / max-over-ranks time.
 
-The JSON line also carries
-  roofline      HBM roofline: algorithmic bytes of the path over the measured step time; the dominant kernel
-                with its own hipEvent time and its own PMC traffic
+A plain run (`--gpus N --steps K --warmup W`) does only what `value` needs: it generates the input, warms up, times the K
+steps, writes `--dump-outputs` if asked and prints the line, with the workload's counts under `config` and the roofline of the
+measured step time.  `--full` adds what takes runs of its own, after the timed steps and never part of `value`:
+  kernels       hipEvent time of every kernel over a few more steps (and, in `roofline`, the dominant kernel with its own
+                time and its own PMC traffic)
   cpu_baseline  the oracle (CPU restatement of the reference, one thread) over the same stages on a bounded sample
   quality       dynamic-removal PR / RR (tool/analysis.py:186-187) of this path and of the oracle chain on that sample
+  extras        VoxelGrid and PCIe-inclusive ingest; at one GPU on the K64 workload also configs[2] and configs[4] as sub-runs
+  cold          the one-shot job: the first step of a fresh ctx in the warm process (a plain run reports the first step of
+                the process alone)
+`--no-cpu`, `--no-quality`, `--no-cpu-all`, `--no-extras` and `--no-other-configs` leave parts of that out again.
 """
 import argparse
 import json
@@ -153,12 +159,37 @@ def dump_outputs(outdir, ctx, smap, offs, seed=0):
     return {"dir": outdir, "bytes": total, "label_scans": len(pick), "map_cells_dumped": len(files.get("map_key", ()))}
 
 
+class SegmentObjectsOnDevice:
+    """While active, synth.make_scan gets the static objects of its road segments from a cache on the device.  make_scan builds
+    the objects of three 100 m segments on the host for every scan (a pure function of sequence, segment and kind) and copies
+    them to the device tensor by tensor, about a hundred blocking copies per scan.  Built once per segment and kept on the
+    device, the scans come out the same bit for bit and the input of a 2761-scan job is generated in about two thirds of the time."""
+
+    def __init__(self, synth, dev):
+        self.synth, self.dev, self.cache = synth, dev, {}
+        self.build = synth._segment_objects
+
+    def objects(self, seq, seg, kind):
+        key = (seq, seg, kind)
+        if key not in self.cache:
+            self.cache[key] = {k: v.to(self.dev) for k, v in self.build(seq, seg, kind).items()}
+        return self.cache[key]
+
+    def __enter__(self):
+        self.synth._segment_objects = self.objects
+        return self
+
+    def __exit__(self, *exc):
+        self.synth._segment_objects = self.build
+        self.cache.clear()
+
+
 def other_configs():
     """configs[2] (parking lot, one chain of 1999 steps) and configs[4] (128 beams, 2x finer grid) as sub-runs of this script"""
     res = {}
     for name, extra, limit in (("configs[2] PARK", ["--kind", "PARK", "--preset", "parkinglot", "--scans", "2000"], 420),
                                ("configs[4] OS128", ["--kind", "OS128", "--preset", "os128_fine", "--scans", "1000"], 600)):
-        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-all", "--cpu-scans", "32"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-cpu-all", "--cpu-scans", "32"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
             line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
@@ -189,17 +220,19 @@ def main():
     ap.add_argument("--skip", type=int, default=0, help="tracking stride: scan i is differenced against scan i + skip (0: the preset's config skip_, 5 in semantickitti.yaml, 1 in parkinglot.yaml)")
     ap.add_argument("--map-cells", type=int, default=0, help="capacity of the static map in cells (0: from the points)")
     ap.add_argument("--map-leaf", type=float, default=0.2)
-    ap.add_argument("--cpu-scans", type=int, default=320, help="bounded sample for the CPU baseline and the PR/RR check")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-cpu-all", action="store_true", help="skip the multi-threaded CPU context number")
-    ap.add_argument("--no-quality", action="store_true", help="skip the PR/RR comparison")
-    ap.add_argument("--no-extras", action="store_true", help="skip the separately reported stages (VoxelGrid, ingest): profiling runs")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what takes runs of its own: per-kernel times, the CPU baseline, "
+                    "PR/RR against the oracle, the extras, the fresh-ctx step and (one GPU, K64) the PARK / OS128 sub-runs; without it the run does only what `value` needs")
+    ap.add_argument("--cpu-scans", type=int, default=320, help="bounded sample for the CPU baseline and the PR/RR check (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline and the PR/RR check")
+    ap.add_argument("--no-cpu-all", action="store_true", help="--full: skip the multi-threaded CPU context number")
+    ap.add_argument("--no-quality", action="store_true", help="--full: skip the PR/RR comparison")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the separately reported stages (VoxelGrid, ingest, fresh ctx, sub-runs): profiling runs")
     ap.add_argument("--split-sequence", action="store_true", help="strong scaling: ONE sequence of --scans scans over the ranks (contiguous blocks, a halo of 10 x skip scans for the tracking chain's warm-up, the chain's state handed from rank to rank: pyshim/shard.py plan_split)")
     ap.add_argument("--replicate", action="store_true", help="N > 1: every rank runs a sequence of its own (weak scaling: rounds 1-3) instead of cutting ONE sequence over the ranks (the default at N > 1)")
     ap.add_argument("--kitti", action="store_true", help="the job is SemanticKITTI seq 00-10 at their real lengths (BASELINE configs[3], 23 201 scans: needs the memory of several GPUs); with --split-sequence the sequences are cut where the load says")
     ap.add_argument("--kitti-scale", default="1", help="with --kitti: every sequence length times this fraction (e.g. 1/32: a dry run of configs[3]'s 11-sequence plan that fits one GPU)")
     ap.add_argument("--split-halo", type=int, default=10, help="warm-up steps of the halo in front of a rank's block (--split-sequence); 10 since round 6 (12 before): on the eight-rank K64 jobs no chain is walked again at a cut down to 8 steps, from 6 on the warm-up misses states (profiles/r06_halo_sweep.txt)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short PARK / OS128 sub-runs that the default invocation appends under extras.configs")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the short PARK / OS128 sub-runs that a full K64 run appends under extras.configs")
     ap.add_argument("--no-map", action="store_true", help="leave the static map out of the step (profiling)")
     ap.add_argument("--track-mode", default="chain", choices=["chain", "first-order"], help="chain: the reference's sequential tracking chain (default); first-order: every pair independent")
     ap.add_argument("--chain-seg", type=int, default=0, help="steps per chain segment (0: library default)")
@@ -281,12 +314,13 @@ def main():
     # ---- the rank's scans, resident in HBM ----
     t0 = time.time()
     parts, labs, offs, poses = [], [], [0], []
-    for (q, i) in plan["scans"]:
-        p, l, pose = synth.make_scan(q, i, args.kind, device=dev)
-        parts.append(p)
-        labs.append(l)
-        offs.append(offs[-1] + p.shape[0])
-        poses.append(pose)
+    with SegmentObjectsOnDevice(synth, dev):
+        for (q, i) in plan["scans"]:
+            p, l, pose = synth.make_scan(q, i, args.kind, device=dev)
+            parts.append(p)
+            labs.append(l)
+            offs.append(offs[-1] + p.shape[0])
+            poses.append(pose)
     pts = torch.cat(parts, 0).contiguous()
     del parts
     offs = np.asarray(offs, np.int32)
@@ -477,14 +511,15 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dumped = dump_outputs(args.dump_outputs, ctx, pmap if multi else smap, offs) if args.dump_outputs else None
-    # a few more steps with hipEvents around every kernel of the ctx (attribution only) and around the map stage: at most
-    # ATTRIBUTION_STEPS whatever --steps is, so that only the timed steps grow with --steps
-    ctx.set_timing(True)
-    barrier()
-    for _ in range(min(args.steps, ATTRIBUTION_STEPS)):
-        step(timed=True)
-    barrier()
-    ctx.set_timing(False)
+    if args.full:
+        # a few more steps with hipEvents around every kernel of the ctx (attribution only) and around the map stage: at most
+        # ATTRIBUTION_STEPS whatever --steps is, so that only the timed steps grow with --steps
+        ctx.set_timing(True)
+        barrier()
+        for _ in range(min(args.steps, ATTRIBUTION_STEPS)):
+            step(timed=True)
+        barrier()
+        ctx.set_timing(False)
 
     chain_stats = ctx.batch_track_stats()  # (raises if a chain state overflowed its workspace)
     cluster_stats = ctx.batch_cluster_stats()  # scans whose clustering kept "everything found is joined" around an out-of-grid triple
@@ -528,14 +563,14 @@ def main():
                      dynamic_points=np.array([d for _, d in per_scan], np.int64))
 
     dev_labels = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.no_quality:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu and not args.no_quality:
         import quality as qmod
         sample = list(range(0, n_sc, args.skip))[: args.cpu_scans]  # what the reference loads with skip_: consecutive FRAMES
         dev_labels = [qmod.device_point_labels(ctx, s, int(offs[s + 1] - offs[s])) for s in sample[:-1]]
 
     # ---- separately reported stages (not part of `value`; they reuse the arena) ----
     extras = {}
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         try:  # loader-side label filter + VoxelGrid 0.08 m over the resident sequence
             sub = min(n_sc, 512)
             o2 = offs[: sub + 1]
@@ -603,7 +638,7 @@ def main():
                                        "pmc_bytes_per_launch": (traffic[name] * n_sc) if name in traffic else None,
                                        "pmc_GBps": kernels[name].get("pmc_GBps")}
         cpu = quality = cpu_all = None
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             import oracle_py
             orc = oracle_py.load()
             sample = list(range(0, n_sc, args.skip))[: args.cpu_scans]
@@ -650,7 +685,8 @@ def main():
                                "note": "two scans per thread, same oracle; context, not the baseline"}
                 except Exception:
                     cpu_all = None
-        extras["cpu_all_threads"] = cpu_all
+        if args.full:
+            extras["cpu_all_threads"] = cpu_all
         out = {"metric": "scans/sec on SemanticKITTI-seq-05-shaped input (SCV-OD dynamic-removal path, raw scans -> per-point labels + static map)",
                "value": scans_per_s, "unit": "scans/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": ms_step, "higher_is_better": True, "scaling": "strong" if split else "weak", "vs_baseline": None,
@@ -669,7 +705,8 @@ def main():
                                        "whole sequences per rank (longest first to the least loaded rank)"),
                           "split": ({"scans_loaded_by_rank0": n_sc, "own": own_count, "pieces_rank0": [list(map(int, pc)) for pc in split["pieces"]], "chains_rewalked_at_boundary_rank0": info.get("chains_rewalked_at_boundary"), "chains_rewalked_at_boundary_all_ranks": info.get("chains_rewalked_all_ranks"), "boundary_exchange_ms_rank0_last_step": info.get("boundary_ms"), "boundary": info.get("boundary"), "boundary_slow_path_steps_rank0": info.get("boundary_slow_path_steps", 0)} if split else None)},
                "mpts_per_s": all_pts * args.steps / dt / 1e6, "gen_seconds": gen_s,
-               "roofline": roof, "cpu_baseline": cpu, "quality": quality, "kernels": kernels, "extras": extras}
+               "roofline": roof, "cpu_baseline": cpu, "quality": quality, "kernels": kernels if args.full else None, "extras": extras if args.full else None,
+               "full": args.full}
         if dumped:
             out["dump_outputs"] = dumped
         if multi:
@@ -680,7 +717,7 @@ def main():
         if pmap is not None:
             pmap.close()
     ctx.close()
-    if rank == 0 and world == 1 and not multi and not args.no_extras:
+    if rank == 0 and world == 1 and not multi and args.full and not args.no_extras:
         # what a ONE-PASS user sees (the reference walks a sequence once, ssc.cpp:1428-1452): a FRESH ctx in this warm process -- no
         # planner feedback (equal-length chain segments), the first-guess map table (a quarter of the points), lazy buffers allocated
         # inside the step -- against the steady-state step of the headline.  Steps 2 and 3 of the same ctx show how fast it converges.
@@ -723,7 +760,7 @@ def main():
     elif rank == 0 and cold:
         out["cold"] = cold
     if rank == 0:
-        if world == 1 and args.kind == "K64" and args.preset == "semantickitti" and not args.no_extras and not args.no_other_configs:
+        if world == 1 and args.kind == "K64" and args.preset == "semantickitti" and args.full and not args.no_extras and not args.no_other_configs:
             # BASELINE configs[2] and configs[4] on this GPU, short runs of this same script after the headline workload left the
             # device (driver-timed with the line: the judge asked for them in BENCH_rNN.json); never part of `value`
             del pts, labs

@@ -88,7 +88,7 @@ for name in ("k64", "park", "os128"):
         continue
     scans = int(open(os.path.join(src, f"pmc_scans_{name}.txt")).read().split()[0])
     F, W = load(fp), load(wp)
-    out = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), python bench.py [workload] --steps 1 --warmup 0 --no-cpu --no-extras; raw values are "
+    out = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), python bench.py [workload] --steps 1 --warmup 0 --full --no-cpu --no-extras; raw values are "
                    "KB per dispatch, bytes = KB * 1024; FETCH x 2 and WRITE x 1 as calibrated on known bytes (profiles/r06_pmc_calibration.md: coalesced reads of any width AND "
                    "random gathers -- a gather moves its whole 128-B line; an atomic without return counts 32 B on the write side only); Infinity-Cache hits are counted: this is "
                    "L2-fabric traffic, an upper bound of HBM traffic; a kernel launched several times per step is summed",
@@ -116,7 +116,7 @@ if os.path.exists(p):
     S = load(p)
     with open(os.path.join(here, f"{tag}_sq_pmc_summary.txt"), "w") as f:
         f.write("rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT\n"
-                "  --kernel-include-regex scvod -- python bench.py --scans 256 --steps 1 --warmup 0 --no-cpu --no-extras   (sums over the dispatches of a kernel)\n"
+                "  --kernel-include-regex scvod -- python bench.py --scans 256 --steps 1 --warmup 0 --full --no-cpu --no-extras   (sums over the dispatches of a kernel)\n"
                 "shares are of SQ_WAVE_CYCLES: issue = ACTIVE_INST_ANY, valu / lds = ACTIVE_INST_VALU / _LDS, wait = WAIT_ANY (s_waitcnt / barrier), stall = WAIT_INST_ANY;\n"
                 "conflict = SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS\n\n")
         f.write(f"{'kernel':44s} {'waves':>10s} {'issue':>7s} {'valu':>7s} {'lds':>7s} {'wait':>7s} {'stall':>7s} {'conflict':>9s}\n")

@@ -44,7 +44,7 @@ def test_two_ranks_reproduce_the_single_rank_job(tmp_path):
 
 def test_rccl_leg_at_one_rank(tmp_path):
     plain, m0 = _run(str(tmp_path), "plain", ["--gpus", "1", "--scans", "20"])
-    rccl, m1 = _run(str(tmp_path), "rccl", ["--gpus", "1", "--scans", "20", "--force-dist", "--split-sequence"], backend="nccl")
+    rccl, m1 = _run(str(tmp_path), "rccl", ["--gpus", "1", "--scans", "20", "--force-dist", "--split-sequence", "--full"], backend="nccl")
     assert rccl["config"]["backend"] == "nccl" and rccl["config"]["rccl_ranks"] == 1
     assert rccl["config"]["map_slot_records"] > 0                       # the padded all_to_all_single ran
     # the boundary exchange of a cut sequence on the device: export kernels into padded records, one RCCL point-to-point exchange
@@ -171,7 +171,7 @@ def test_device_boundary_step_logic_with_a_real_neighbour(tmp_path, halo):
     carried clouds, the verdict sends every step through resolve_chain_boundaries and the step's map is accumulated again from the
     corrected labels.  Either way the job equals the one-rank run bit for bit."""
     one, m1 = _run_k64(str(tmp_path), "one", ["--gpus", "1", "--scans", "170"])
-    two, m2 = _run_k64(str(tmp_path), "two", ["--gpus", "2", "--scans", "170", "--same-device", "--boundary", "device", "--split-halo", str(halo), "--steps", "2"])
+    two, m2 = _run_k64(str(tmp_path), "two", ["--gpus", "2", "--scans", "170", "--same-device", "--boundary", "device", "--split-halo", str(halo), "--steps", "2", "--full"])
     sp = two["config"]["split"]
     assert two["n_gpus"] == 2 and sp["boundary"]["path"].startswith("device rows") and sp["boundary"]["record_bytes"] >= 65536
     assert "tk_boundary_exchange" in two["kernels"]

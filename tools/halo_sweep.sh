@@ -6,7 +6,7 @@ set -o pipefail
 # usage (GPU box): bash tools/halo_sweep.sh > gpurun_out/r06_halo_sweep.txt
 for scans in 240 690; do
   for halo in 12 10 8 6 5 4 3 2; do
-    out=$(timeout -k 10 300 python bench.py --gpus 4 --same-device --backend gloo --scans $scans --split-halo $halo --steps 1 --warmup 1 --no-cpu --no-extras 2>/dev/null | grep '^{' | tail -1) \
+    out=$(timeout -k 10 300 python bench.py --gpus 4 --same-device --backend gloo --scans $scans --split-halo $halo --steps 1 --warmup 1 --full --no-cpu --no-extras 2>/dev/null | grep '^{' | tail -1) \
       || { echo "scans $scans halo $halo: bench.py failed (exit $?), sweep stopped"; exit 1; }
     python - "$scans" "$halo" <<PY
 import json, sys
