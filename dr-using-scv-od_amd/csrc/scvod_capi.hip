@@ -144,6 +144,19 @@ struct scvod_ctx {
     size_t rg_sort_bytes = 0;
     hipEvent_t rg_ev = nullptr;
     bool rg_done = false;        // the region growing ran on the current clustering (scvod_batch_cluster_types)
+    // intensity calibration by incidence angle (scvod_set_intensity_calibration, scvod_k_calib.inc): setting, chunk scratch, the
+    // buffers of a fetch (one scan)
+    bool cal_on = false;
+    int32_t cal_k = 10;
+    float cal_max = 200.f;
+    void* cal_buf = nullptr;     // chunk scratch (capacity cal_cap points) + counters, grown when a chunk needs more
+    size_t cal_buf_bytes = 0;
+    int64_t cal_cap = 0;
+    void* cal_fetch = nullptr;   // normal + curvature and calibrated intensity of the scan a fetch asked for (cal_fetch_cap points)
+    size_t cal_fetch_bytes = 0;
+    int64_t cal_fetch_cap = 0;
+    CalJob cal{};
+    bool cal_done = false;       // the stage ran on the current batch
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -592,6 +605,75 @@ int run_rgrow(scvod_ctx* c, hipStream_t st) {
     return SCVOD_OK;
 }
 
+// scratch of the intensity calibration for chunks of up to `chunk` points: allocated on first use
+constexpr int64_t kCalChunkPts = 1 << 22;  // points of the scans of one chunk (more only when a single scan is larger)
+int ensure_calib(scvod_ctx* c, int64_t chunk) {
+    if (c->cal_cap >= chunk) return SCVOD_OK;
+    CalJob& J = c->cal;
+    if (c->cal_buf) {
+        HIPCHK(c, hipStreamSynchronize(c->last_stream));
+        HIPCHK(c, hipFree(c->cal_buf));
+        c->side_bytes -= c->cal_buf_bytes;
+        c->cal_buf = nullptr;
+    }
+    const size_t C = (size_t)chunk;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver k{(unsigned char*)c->cal_buf};
+        J.sxyz = k.take<float4>(C);
+        J.pcell = k.take<int32_t>(C);
+        J.cell = k.take<int32_t>(3 * C + 4 * (size_t)kCalChunkScans);
+        J.slot = k.take<int32_t>(C);
+        J.grid = k.take<float4>(2 * (size_t)kCalChunkScans);
+        J.stats = k.take<int32_t>(8);
+        J.cand = k.take<unsigned long long>(1);
+        if (pass == 0) {
+            c->cal_buf_bytes = align_up(k.off, 256);
+            HIPCHK(c, hipMalloc(&c->cal_buf, c->cal_buf_bytes));
+            c->side_bytes += c->cal_buf_bytes;
+        }
+    }
+    c->cal_cap = chunk;
+    return SCVOD_OK;
+}
+
+template <typename F>
+void calib_chunks(const std::vector<int32_t>& off, int B, F f) {
+    for (int s0 = 0; s0 < B;) {
+        int s1 = s0 + 1;
+        while (s1 < B && s1 - s0 < kCalChunkScans && (int64_t)off[s1 + 1] - off[s0] <= kCalChunkPts) ++s1;
+        f(s0, s1);
+        s0 = s1;
+    }
+}
+
+// the intensity calibration over the batch, chunk by chunk of scans, on stream st (between k_emit and the voxel stage)
+int run_calib(scvod_ctx* c, hipStream_t st) {
+    const int B = c->A.n_scans;
+    const std::vector<int32_t>& off = c->h_scan_off;
+    int64_t need = 1;
+    calib_chunks(off, B, [&](int s0, int s1) { need = std::max(need, (int64_t)off[s1] - off[s0]); });
+    int rc = ensure_calib(c, need);
+    if (rc) return rc;
+    CalJob J = c->cal;
+    J.k = c->cal_k;
+    J.max_int = c->cal_max;
+    J.write_apri = 1;
+    J.out_int = nullptr;
+    J.out_nc = nullptr;
+    static const bool force = getenv("SCVOD_CALIB_FORCE_FALLBACK") != nullptr;  // (development: tools/intensity_calibration_cost.py)
+    J.force_fallback = force ? 1 : 0;
+    HIPCHK(c, hipMemsetAsync(J.stats, 0, 8 * sizeof(int32_t), st));
+    HIPCHK(c, hipMemsetAsync(J.cand, 0, sizeof(unsigned long long), st));
+    calib_chunks(off, B, [&](int s0, int s1) {
+        J.s0 = s0;
+        J.ns = s1 - s0;
+        J.off0 = off[s0];
+        launch_calib(c->A, J, (int)(off[s1] - off[s0]), st, timer_hook, c);
+    });
+    HIPCHK(c, hipGetLastError());
+    return SCVOD_OK;
+}
+
 // everything after the clustering reads the partition through A.pt_cluster: the fused one after a merged clustering.  A new batch
 // or clustering starts from the arena's own array again.
 void unmerge_view(scvod_ctx* c) {
@@ -665,7 +747,16 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
     // marks per input point for the static map (car-cluster member / dynamic / list marks): clean for every new batch
     if (mx > 0 && do_patchwork != 2 && do_patchwork != 3) HIPCHK(c, hipMemsetAsync(c->A.pt_mapcls, 0, (size_t)total, st));
     c->clustered_this_batch = false;
-    if (mx > 0) launch_process(c->dev, c->A, st, do_patchwork, apply_filter, do_voxels, timer_hook, c);
+    c->cal_done = false;
+    if (mx > 0 && c->cal_on && do_patchwork == 1) {  // Patchwork + binning, the calibration of apri_int, then the voxel stage on its own
+        launch_process(c->dev, c->A, st, 1, apply_filter, 0, timer_hook, c);
+        const int rc_cal = run_calib(c, st);
+        if (rc_cal) return rc_cal;
+        if (do_voxels) launch_process(c->dev, c->A, st, 4, apply_filter, 1, timer_hook, c);
+    } else if (mx > 0) {
+        launch_process(c->dev, c->A, st, do_patchwork, apply_filter, do_voxels, timer_hook, c);
+    }
+    c->cal_done = c->cal_on && do_patchwork == 1;  // (a batch of empty scans is a calibrated batch of no points)
     HIPCHK(c, hipGetLastError());
     if (mx == 0) {  // every scan empty: no kernel runs (neither here nor in the clustering / tracking launches): clean per-scan words
         HIPCHK(c, hipMemsetAsync(c->A.counts, 0, sizeof(int32_t) * 8 * n_scans, st));
@@ -714,6 +805,8 @@ int fetch_scan(scvod_ctx* c, int32_t s, scvod_scan_result* out) {
     hipStream_t st = c->last_stream;
     if (c->have_patchwork) launch_cls(A, s, base, k[0], st);
     if (c->apri_compact && k[4] > 0) launch_apri_expand(c->dev, A, s, 1, k[4], st);  // PointAPRI records of this scan only
+    if (c->apri_compact && c->cal_done) launch_calib_apri(A, s, k[4], st);             // ... with the calibrated intensity (a second small
+                                                                                       //     kernel per fetch: k_apri_expand stays as it was)
     HIPCHK(c, hipGetLastError());
     // one pinned staging block, twelve asynchronous copies, one synchronisation (the pointers handed out live in it)
     struct Part {
@@ -1307,6 +1400,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->rg_sort_tmp) hipFree(c->rg_sort_tmp);
     if (c->rg_out) hipFree(c->rg_out);
     if (c->rg_ev) hipEventDestroy(c->rg_ev);
+    if (c->cal_buf) hipFree(c->cal_buf);
+    if (c->cal_fetch) hipFree(c->cal_fetch);
     if (c->chain_ws) hipFree(c->chain_ws);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
@@ -1667,6 +1762,84 @@ int scvod_set_region_growing(scvod_ctx* c, int32_t on, int32_t k, int32_t min_se
     c->rg_curv = curvature_threshold;
     c->rg_frac = plane_fraction;
     c->rg_done = false;
+    return SCVOD_OK;
+}
+
+int scvod_set_intensity_calibration(scvod_ctx* c, int32_t on, int32_t search_num, float max_intensity) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (search_num < 3 || search_num > 16) return fail(c, SCVOD_ERR_INVALID, "intensity calibration: search_num %d outside 3..16", search_num);
+    if (!(max_intensity > 0.f)) return fail(c, SCVOD_ERR_INVALID, "intensity calibration: max_intensity must be a positive number");
+    c->cal_on = on != 0;
+    c->cal_k = search_num;
+    c->cal_max = max_intensity;
+    return SCVOD_OK;
+}
+
+int scvod_batch_fetch_intensity_calibration(scvod_ctx* c, int32_t s, float* h_normal_curv, float* h_intensity, int32_t cap) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!c->batch_valid || !c->cal_done)
+        return fail(c, SCVOD_ERR_STATE, "no intensity calibration ran on the last batch (scvod_set_intensity_calibration before scvod_batch_process)");
+    int rc = ensure_counts(c);
+    if (rc) return rc;
+    if (s < 0 || s >= c->A.n_scans) return fail(c, SCVOD_ERR_INVALID, "scan %d out of range", s);
+    const int32_t n = c->h_counts[(size_t)s * 8 + 2];
+    if (n > cap) return fail(c, SCVOD_ERR_CAPACITY, "output buffer too small (%d < %d)", cap, n);
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    if (c->cal_fetch_cap < n) {  // the neighbour lists and normals never reach HBM in a batch: the scan is calibrated again for the fetch
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cal_fetch) {
+            HIPCHK(c, hipFree(c->cal_fetch));
+            c->side_bytes -= c->cal_fetch_bytes;
+            c->cal_fetch = nullptr;
+        }
+        const int64_t want = std::max<int64_t>(n, c->A.max_scan_pts);
+        c->cal_fetch_bytes = align_up(sizeof(float) * 5 * (size_t)want, 256);
+        HIPCHK(c, hipMalloc(&c->cal_fetch, c->cal_fetch_bytes));
+        c->side_bytes += c->cal_fetch_bytes;
+        c->cal_fetch_cap = want;
+    }
+    const int64_t pts = (int64_t)c->h_scan_off[s + 1] - c->h_scan_off[s];
+    rc = ensure_calib(c, pts);
+    if (rc) return rc;
+    CalJob J = c->cal;
+    J.k = c->cal_k;
+    J.max_int = c->cal_max;
+    J.write_apri = 0;
+    J.force_fallback = 0;
+    J.out_nc = (float4*)c->cal_fetch;
+    J.out_int = (float*)((float4*)c->cal_fetch + c->cal_fetch_cap);
+    J.stats = nullptr;
+    J.s0 = s;
+    J.ns = 1;
+    J.off0 = c->h_scan_off[s];
+    launch_calib(c->A, J, (int)pts, st, nullptr, nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (h_normal_curv) HIPCHK(c, hipMemcpy(h_normal_curv, J.out_nc, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    if (h_intensity) HIPCHK(c, hipMemcpy(h_intensity, J.out_int, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return n;
+}
+
+int scvod_batch_intensity_calibration_stats(scvod_ctx* c, int32_t* h_out8) {
+    if (!c || !h_out8) return SCVOD_ERR_INVALID;
+    if (!c->batch_valid) return fail(c, SCVOD_ERR_STATE, "no batch has been run");
+    for (int k = 0; k < 8; ++k) h_out8[k] = 0;
+    if (!c->cal_done || c->A.max_scan_pts <= 0) return SCVOD_OK;
+    HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    HIPCHK(c, hipMemcpy(h_out8, c->cal.stats, 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    h_out8[7] = 0;
+    return SCVOD_OK;
+}
+
+int scvod_batch_intensity_calibration_candidates(scvod_ctx* c, int64_t* h_out) {
+    if (!c || !h_out) return SCVOD_ERR_INVALID;
+    if (!c->batch_valid) return fail(c, SCVOD_ERR_STATE, "no batch has been run");
+    *h_out = 0;
+    if (!c->cal_done || c->A.max_scan_pts <= 0) return SCVOD_OK;
+    HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    HIPCHK(c, hipMemcpy(h_out, c->cal.cand, sizeof(int64_t), hipMemcpyDeviceToHost));
     return SCVOD_OK;
 }
 

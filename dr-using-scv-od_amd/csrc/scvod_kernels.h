@@ -259,11 +259,35 @@ struct RgJob {
     int32_t* stats;                // [8] see scvod_batch_region_growing_stats
 };
 
+// intensity calibration by incidence angle (SSC::intensityCalibrationByCurvature, ssc.cpp:98-153; scvod_k_calib.inc), opt-in.  One job
+// per chunk of scans [s0, s0 + ns): chunk points are numbered g = scan_off[s] - off0 + i; a scan's non-ground cloud (n <= its points)
+// occupies the first n slots of its range.  Scratch only (chunk capacity C points, at most kCalChunkScans scans): the stage's product is
+// the patched Arena::apri_int; the per-point outputs exist for the scan a fetch asks for.
+constexpr int kCalChunkScans = 65535;
+struct CalJob {
+    int32_t k;                     // neighbours (3..16)
+    float max_int;                 // ssc/max_intensity_
+    int32_t s0, ns;
+    int64_t off0;                  // scan_off[s0]
+    int32_t write_apri;            // 1: the calibrated value replaces apri_int of the points that passed the range/FOV test
+    int32_t force_fallback;        // development (tools/intensity_calibration_cost.py): no tile staged, no LDS reserved, every query reads HBM
+    float4* sxyz;                  // [C] per scan: {x, y, z, position} in cell order
+    int32_t* pcell;                // [C] per position: its cell
+    int32_t* cell;                 // [3 C + 4 kCalChunkScans] per scan at 3 g0 + 4 (s - s0): CSR cell ends
+    int32_t* slot;                 // [C] per input point: its apri slot, -1 for the others
+    float4* grid;                  // [2 kCalChunkScans] per scan: origin, cell edge; cells per axis, n
+    float* out_int;                // [C] per position: calibrated intensity, or nullptr
+    float4* out_nc;                // [C] per position: normal, curvature, or nullptr
+    int32_t* stats;                // [8] see scvod_batch_intensity_calibration_stats, or nullptr (a fetch counts nothing)
+    unsigned long long* cand;      // [1] candidates examined (with stats)
+};
+
 typedef void (*TimerHook)(void* user, const char* name, int begin);
 
 // Launches.  `th`/`tu` optional per-kernel timing hook (called before and after each launch).
 // do_patchwork: 1 = Patchwork + fused binning, 0 = binning of the input cloud in input order,
-// 2 = neither (apri / counts already in the arena: voxel stage only).
+// 2 = neither (apri / counts already in the arena: voxel stage only), 4 = the voxel stage alone on the compact arrays a
+// do_patchwork = 1 call without voxels left (the intensity calibration runs between the two).
 void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_patchwork, int apply_filter,
                     int do_voxels, TimerHook th, void* tu);
 void launch_apri_expand(const DevParams& P, const Arena& A, int s0, int n_scans, int max_pts, hipStream_t st);
@@ -283,6 +307,8 @@ void launch_merge(const DevParams& P, const Arena& A, const MergeJob& M, int fro
 size_t rg_sort_bytes(int chunk_pts);  // temporary storage of the radix sort of a chunk's keys
 void launch_rgrow(const DevParams& P, const Arena& A, const RgJob& J, int chunk_pts, void* sort_tmp, size_t sort_bytes, hipStream_t st,
                   TimerHook th, void* tu);
+void launch_calib(const Arena& A, const CalJob& J, int chunk_pts, hipStream_t st, TimerHook th, void* tu);
+void launch_calib_apri(const Arena& A, int s, int n_apri, hipStream_t st);  // the calibrated intensity into scan s's PointAPRI records
 void launch_merge_lastname(const Arena& A, const MergeJob& M, hipStream_t st, TimerHook th, void* tu);  // carrier of max_name -> its fusion
 void launch_lastname(const DevParams& P, const Arena& A, hipStream_t st, hipStream_t st2, hipStream_t st3, hipEvent_t ev_fork, hipEvent_t ev_join2,
                      hipEvent_t ev_join3, TimerHook th, void* tu);

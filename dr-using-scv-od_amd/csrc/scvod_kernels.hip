@@ -362,6 +362,7 @@ __device__ __forceinline__ void block_bitonic_merge_stages(T* a, int np2) {
 #include "scvod_k_cluster.inc"  // curved-voxel clustering, boxes, type rules, successor tables: k_cc_scan
 #include "scvod_k_merge.inc"  // intensity merge of the clusters (ssc.cpp:571-635), opt-in: k_im_merge
 #include "scvod_k_rgrow.inc"  // building / tree of the large clusters by region growing (ssc.cpp:797-860), opt-in: k_rg_*
+#include "scvod_k_calib.inc"  // intensity calibration by incidence angle (ssc.cpp:98-153), opt-in: k_cal_*
 #include "scvod_k_probe_nn.inc"  // per-pair tracking probe of the facade path (A6 bulk part) and the brute-force correspondence search (A7)
 // ------------------------------------------------------------------------------------------
 // host-side launch sequences
@@ -469,7 +470,8 @@ void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_p
         TH_BEGIN("emit");
         hipLaunchKernelGGL(k_emit, dim3(kPersistCUs * 8), dim3(kEmitThreads), 0, st, P, A);
         TH_END("emit");
-    } else if (do_patchwork == 0) {
+    } else if (do_patchwork == 0) {  // (2: a caller's apri_vec, 3: the VoxelGrid run, 4: the compact arrays of an earlier do_patchwork = 1 call
+                                     //  without voxels, the intensity calibration having run in between: nothing to do before the voxel stage)
         TH_BEGIN("bin_direct");
         hipLaunchKernelGGL(k_bin_direct, dim3(B), dim3(1024), 0, st, P, A, apply_filter);
         TH_END("bin_direct");
@@ -662,6 +664,32 @@ void launch_rgrow(const DevParams& P, const Arena& A, const RgJob& J, int chunk_
     hipFuncSetAttribute((const void*)k_rg_grow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_rg_grow, dim3(2048), dim3(kRgThreads), lds, st, A, J);
     TH_END("rg_grow");
+}
+
+void launch_calib(const Arena& A, const CalJob& J, int chunk_pts, hipStream_t st, TimerHook th, void* tu) {
+    if (J.ns <= 0 || chunk_pts <= 0 || A.max_scan_pts <= 0) return;
+    const dim3 gs((A.max_scan_pts + kCalThreads - 1) / kCalThreads, J.ns);
+    if (J.write_apri) {
+        TH_BEGIN("cal_slot");
+        hipMemsetAsync(J.slot, 0xff, sizeof(int32_t) * (size_t)chunk_pts, st);
+        hipLaunchKernelGGL(k_cal_slot, gs, dim3(kCalThreads), 0, st, A, J);
+        TH_END("cal_slot");
+    }
+    TH_BEGIN("cal_grid");
+    hipLaunchKernelGGL(k_cal_grid, dim3(J.ns), dim3(kCalGridThreads), 0, st, A, J);
+    TH_END("cal_grid");
+    TH_BEGIN("cal_knn");
+    // (the development switch force_fallback stages nothing: no dynamic LDS then, so the one-thread-per-query baseline runs at the
+    //  residency its registers allow, 4 waves per SIMD, and not at the 2 workgroups per CU that 64 KB tiles leave)
+    const size_t lds = J.force_fallback ? 0 : sizeof(float4) * kCalLdsPts;
+    hipFuncSetAttribute((const void*)k_cal_knn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float4) * kCalLdsPts));
+    hipLaunchKernelGGL(k_cal_knn, gs, dim3(kCalThreads), lds, st, A, J);
+    TH_END("cal_knn");
+}
+
+void launch_calib_apri(const Arena& A, int s, int n_apri, hipStream_t st) {
+    if (n_apri <= 0) return;
+    hipLaunchKernelGGL(k_cal_apri, dim3((n_apri + 1023) / 1024), dim3(kCalThreads), 0, st, A, s);
 }
 
 void launch_merge_lastname(const Arena& A, const MergeJob& M, hipStream_t st, TimerHook th, void* tu) {

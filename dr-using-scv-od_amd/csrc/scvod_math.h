@@ -958,5 +958,33 @@ SCVOD_HD bool rg_smooth_ok(const float* nq, const float* np, float cos_t) {
 // seed rank of a curvature: ascending, NaN before every finite value
 SCVOD_HD uint32_t rg_curv_key(float c) { return c != c ? 0u : float_sort_key(c); }
 
+// ---- intensity calibration by incidence angle, SSC::intensityCalibrationByCurvature (ssc.cpp:101-105, 140-151) for one point:
+// intensity clamped to max_intensity, divided by |cos| of the angle between the normal n and the point p (floor 0.3), capped again.
+// Eigen's fixed-size 3-vector reductions associate as a0 + (a1 + a2); no FMA.  A NaN normal gives NaN: both
+// comparisons are false, as in the C++.  flags (optional): bit 0 clamped before, bit 1 floored at 0.3, bit 2 capped after. -------
+SCVOD_HD float calibrated_intensity_f32(float intensity, float max_intensity, const float n[3], float px, float py, float pz, int* flags) {
+    int f = 0;
+    float i0 = intensity;
+    if (i0 > max_intensity) {
+        i0 = max_intensity;
+        f |= 1;
+    }
+    const float dot = n[0] * px + (n[1] * py + n[2] * pz);
+    const float nn = sqrt_f(n[0] * n[0] + (n[1] * n[1] + n[2] * n[2]));
+    const float pn = sqrt_f(px * px + (py * py + pz * pz));
+    float c = fabs_f(dot / (nn * pn));
+    if ((double)c < 0.3) {
+        c = (float)0.3;
+        f |= 2;
+    }
+    float v = i0 / c;
+    if (v > max_intensity) {
+        v = max_intensity;
+        f |= 4;
+    }
+    if (flags) *flags = f;
+    return v;
+}
+
 }  // namespace scvod
 #endif  // SCVOD_MATH_H_

@@ -85,6 +85,10 @@ int main(int argc, char** argv) {
                 std::ofstream oc(out + "/" + std::to_string(ssc.frame_set[i].id) + "_cloud.f32", std::ios::binary);
                 for (auto& p : ssc.cloud_vec[i]->points) oc.write((const char*)&p, 16);
             }
+            if (ssc.device_intensity_calibration) {  // (only with the key) cloud_use: the kept non-ground points with their calibrated intensity
+                std::ofstream ou(out + "/" + std::to_string(ssc.frame_set[i].id) + "_cloud_use.f32", std::ios::binary);
+                for (auto& p : ssc.frame_set[i].cloud_use->points) ou.write((const char*)&p, 16);
+            }
             std::ofstream o(out + "/" + std::to_string(ssc.frame_set[i].id) + "_dynamic.f32", std::ios::binary);
             int cars = 0, dyn = 0;
             for (auto& kv : ssc.frame_set[i].cluster_set) {
@@ -112,6 +116,7 @@ int main(int argc, char** argv) {
             }
             std::cout << "\n";
         }
+        if (ssc.device_intensity_calibration) std::cout << "intensity_calibration search_num " << ssc.search_num << " max_intensity " << ssc.max_intensity << "\n";  // (only with the key)
         std::cout << "frames " << n << " dynamic_total " << dyn_total << "\n";
     } catch (const std::exception& e) {
         std::cerr << "scvod_sequence failed: " << e.what() << "\n";

@@ -39,6 +39,9 @@ SSC::SSC(const std::string& yaml_path, int device, int max_points) {
     if (device_intensity_merge) chk(ctx_, scvod_set_intensity_merge(ctx_, iteration, search_c, intensity_diff, intensity_cov), "scvod_set_intensity_merge");
     // ssc.cpp:797-860 (regionGrowing inside recognize): on request, with the reference's hard-coded values
     chk(ctx_, scvod_set_region_growing(ctx_, device_region_growing, 10, 20, 10.0, 1.2f, 0.2), "scvod_set_region_growing");
+    // ssc.cpp:234-235 (intensityCalibrationByCurvature between Patchwork and makeApriVec): on request, with its two YAML keys
+    if (device_intensity_calibration)
+        chk(ctx_, scvod_set_intensity_calibration(ctx_, 1, search_num, max_intensity), "scvod_set_intensity_calibration");
     PatchworkGroundSeg->attach(ctx_);
 }
 
@@ -158,6 +161,8 @@ void SSC::process(const pcl::PointCloud<pcl::PointXYZI>::Ptr& cloudIn_) {
     for (int k = 0; k < r.n_apri; ++k) {
         cloud_use->points.push_back(cloudIn_->points[r.apri_src[k]]);
         frame_ssc.cloud_use->points.push_back(cloudIn_->points[r.apri_src[k]]);
+        if (device_intensity_calibration)  // ssc.h:34: cloud_use is the "noground cloud with intenisty calibrated"
+            cloud_use->points.back().intensity = frame_ssc.cloud_use->points.back().intensity = r.apri[k].intensity;
     }
     apri_vec.assign(r.apri, r.apri + r.n_apri);
     fillHashCloud(r, apri_vec.data());

@@ -54,6 +54,9 @@ class SSC : public Utility {
     // clustering (ssc.cpp:299-393) + bounding-box refine / recognise rules (ssc.cpp:437-467, 849-872);
     // the intensity merge and the region growing of recognize (building / tree) run on the device when the facade-only keys
     // ssc/device_intensity_merge_ / ssc/device_region_growing_ ask for them; without the latter building and tree both become `tree`.
+    // ssc/device_intensity_calibration_: 1 makes process() calibrate the intensities by incidence angle (ssc.cpp:98-153, 234-235) with
+    // ssc/search_num_ and ssc/max_intensity_: apri_vec, cloud_use and hash_cloud then carry the calibrated values (the separate entry
+    // point makeApriVec, which bins a caller's cloud, does not calibrate).
     void segmentGpu();
     // The per-scan body of getCloud (ssc.cpp:1063-1106) without the file I/O: label filter (label & 0xFFFF in {0, 1}
     // skipped), intensity * max_intensity, pcl::VoxelGrid 0.08 m -- the cloud that cloud_vec receives.

@@ -75,6 +75,7 @@ class Utility {
     int search_num = 10, iteration = 3, toBeClass = 1, search_c = 2;
     int device_intensity_merge = 0;  // facade-only key ssc/device_intensity_merge_: 1 runs refineClusterByIntensity on the device
     int device_region_growing = 0;   // facade-only key ssc/device_region_growing_: 1 separates building / tree by region growing on the device
+    int device_intensity_calibration = 0;  // facade-only key ssc/device_intensity_calibration_: 1 runs intensityCalibrationByCurvature on the device
     float intensity_diff = 50, intensity_cov = 20, occupancy = 0.6f;
     int building = 0, tree = 1, car = 2;
     std::vector<float> tr_v;
@@ -319,6 +320,7 @@ class Utility {
         y.param<float>("ssc/intensity_cov_", intensity_cov, 20.f);
         y.param<int>("ssc/device_intensity_merge_", device_intensity_merge, 0);
         y.param<int>("ssc/device_region_growing_", device_region_growing, 0);
+        y.param<int>("ssc/device_intensity_calibration_", device_intensity_calibration, 0);
         y.param<float>("ssc/occupancy_", occupancy, 0.6f);
         y.param<int>("ssc/building_", building, 0);
         y.param<int>("ssc/tree_", tree, 1);

@@ -141,6 +141,10 @@ def load_lib():
         "scvod_batch_fetch_cluster_classes": (C.c_int, [vp, i32, i32, i32, i32, vp, i32]),
         "scvod_batch_fetch_region_growing": (C.c_int, [vp, i32, vp, vp, i32]),
         "scvod_batch_region_growing_stats": (C.c_int, [vp, vp]),
+        "scvod_set_intensity_calibration": (C.c_int, [vp, i32, i32, f32]),
+        "scvod_batch_fetch_intensity_calibration": (C.c_int, [vp, i32, vp, vp, i32]),
+        "scvod_batch_intensity_calibration_stats": (C.c_int, [vp, vp]),
+        "scvod_batch_intensity_calibration_candidates": (C.c_int, [vp, vp]),
         "scvod_batch_cluster_last_name": (C.c_int, [vp, vp, i32, vp]),
         "scvod_set_chain_capacity": (C.c_int, [vp, i64]),
         "scvod_chain_workspace_bytes": (i64, [vp]),
@@ -189,7 +193,7 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_bin_scan", "scvod_voxelize", "scvod_pose_delta", "scvod_track_probe", "scvod_batch_process",
                     "scvod_batch_counts", "scvod_batch_fetch", "scvod_batch_cluster", "scvod_batch_fetch_clusters", "scvod_cluster",
                     "scvod_batch_cluster_types", "scvod_batch_fetch_cluster_types",
-                    "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_set_region_growing", "scvod_batch_fetch_cluster_classes", "scvod_batch_fetch_region_growing", "scvod_batch_region_growing_stats", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
+                    "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_set_region_growing", "scvod_batch_fetch_cluster_classes", "scvod_batch_fetch_region_growing", "scvod_batch_region_growing_stats", "scvod_set_intensity_calibration", "scvod_batch_fetch_intensity_calibration", "scvod_batch_intensity_calibration_stats", "scvod_batch_intensity_calibration_candidates", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
                     "scvod_map_create", "scvod_map_destroy", "scvod_map_last_error", "scvod_map_capacity", "scvod_map_clear",
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
                     "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid"]
@@ -544,6 +548,32 @@ class Ctx:
         self._chk(self.lib.scvod_batch_region_growing_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return dict(candidate_clusters=int(out[0]), building_clusters=int(out[1]), candidate_points=int(out[2]), kept_edges=int(out[3]),
                     max_rounds=int(out[4]), hbm_clusters=int(out[5]), tail_points=int(out[6]))
+
+    def set_intensity_calibration(self, on=True, search_num=10, max_intensity=200.0):
+        """SSC::intensityCalibrationByCurvature (ssc.cpp:98-153) between Patchwork and the voxel stage of every later batch: the
+        intensity of every non-ground point divided by the cosine of its incidence angle (normal from its search_num nearest points,
+        3..16).  The defaults are the reference's; off until called"""
+        self._chk(self.lib.scvod_set_intensity_calibration(self.h, 1 if on else 0, int(search_num), float(max_intensity)))
+
+    def batch_fetch_intensity_calibration(self, s, cap):
+        """(normal_curv [n, 4] float32, calibrated intensity [n] float32) per non-ground point of scan s, in nonground_idx order"""
+        nc = np.zeros((max(cap, 1), 4), np.float32)
+        inten = np.zeros(max(cap, 1), np.float32)
+        n = self.lib.scvod_batch_fetch_intensity_calibration(self.h, int(s), nc.ctypes.data_as(C.c_void_p), inten.ctypes.data_as(C.c_void_p), int(cap))
+        if n < 0:
+            self._chk(n)
+        return nc[:n], inten[:n]
+
+    def batch_intensity_calibration_stats(self):
+        out = np.zeros(8, np.int32)
+        self._chk(self.lib.scvod_batch_intensity_calibration_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(points=int(out[0]), clamped_before=int(out[1]), cos_floored=int(out[2]), capped_after=int(out[3]), nan_normals=int(out[4]),
+                    fallback_queries=int(out[5]), max_ring=int(out[6]))
+
+    def batch_intensity_calibration_candidates(self):
+        out = np.zeros(1, np.int64)
+        self._chk(self.lib.scvod_batch_intensity_calibration_candidates(self.h, out.ctypes.data_as(C.c_void_p)))
+        return int(out[0])
 
     def set_max_name_literal(self, literal=True):
         """ssc.cpp:354 keeps the LAST USED running number in Frame::max_name; False = fresh numbers (rounds 1-3)"""

@@ -482,6 +482,33 @@ int scvod_batch_fetch_region_growing(scvod_ctx* ctx, int32_t s, float* h_normal_
  * (zeros when the stage did not run).  Synchronises. */
 int scvod_batch_region_growing_stats(scvod_ctx* ctx, int32_t* h_out8);
 
+/* Intensity calibration by incidence angle, SSC::intensityCalibrationByCurvature (ssc.cpp:98-153; the call at ssc.cpp:234-235), run
+ * by every Patchwork run (scvod_batch_process, scvod_sequence_ingest, scvod_process_scan, scvod_patchwork) between the emission of
+ * the non-ground cloud and the voxel stage when `on`.  Over the WHOLE non-ground cloud of a scan in emission order (the order of
+ * nonground_idx; the points the range/FOV test rejects are neighbours too), per point: intensity clamped to max_intensity; the exact
+ * k_eff = min(search_num, n) nearest points, itself included, by d^2 = (dx*dx + dy*dy) + dz*dz in fp32, ties by position; PCA
+ * normal (NormalEstimation, NaN for fewer than 3 points); c = |n . p| / (|n| |p|), raised to (float)0.3 when below; the result
+ * I0 / c capped at max_intensity.  A NaN normal gives NaN, as in the reference.  The calibrated value replaces PointAPRI::intensity
+ * of the points that pass the range/FOV test (the apri records, hence vox_av / vox_cov, hence the intensity merge); nothing else
+ * moves.  Limits: search_num 3..16; the static map keeps the RAW intensity of its points (it reads the input cloud);
+ * scvod_bin_scan / scvod_voxelize on caller-supplied points are not calibrated.  Off by default: nothing is launched or allocated
+ * and every output stays as it was.  SCVOD_ERR_INVALID (the setting stays as it was) for search_num outside 3..16 or a
+ * max_intensity that is not a positive number -- also in a call that turns the stage off (on = 0): pass valid values there too.  Chunk scratch (36 bytes per point of up to 2^22 points of scans, plus 3 MB) is
+ * allocated by the first calibrated batch (counted by scvod_arena_bytes).  Conventions: DESIGN.md section 2. */
+int scvod_set_intensity_calibration(scvod_ctx* ctx, int32_t on, int32_t search_num, float max_intensity);
+/* the stage's per-point results for scan s of the last batch, in nonground_idx order: h_normal_curv (4 floats per non-ground
+ * point: normal, curvature) and h_intensity (the calibrated intensity); either may be NULL.  A batch keeps neither normals nor
+ * neighbour lists: the call calibrates scan s again on the batch's stream (the input cloud must still be in place) and
+ * synchronises.  SCVOD_ERR_STATE unless the stage ran on the last batch.  Returns n_nonground or a negative status. */
+int scvod_batch_fetch_intensity_calibration(scvod_ctx* ctx, int32_t s, float* h_normal_curv, float* h_intensity, int32_t cap);
+/* h_out8 = {non-ground points calibrated, intensities clamped before the division, cosines raised to 0.3, results capped at
+ * max_intensity, NaN normals, queries that read candidates outside their workgroup's staged tile (the fallback path), largest
+ * ring of cells a query probed, 0} of the last batch (zeros when the stage did not run).  Synchronises. */
+int scvod_batch_intensity_calibration_stats(scvod_ctx* ctx, int32_t* h_out8);
+/* candidates the kNN of the last batch examined, all queries together: a 64-bit count (1.3 x 10^11 per K64 batch), which is why it
+ * is not the eighth word of the stats; read by tools/intensity_calibration_cost.py.  Synchronises. */
+int scvod_batch_intensity_calibration_candidates(scvod_ctx* ctx, int64_t* h_out);
+
 /* Streaming ingest of a sequence held in HOST memory (the reference reads one .bin per scan, SSC::getCloud
  * src/ssc.cpp:1040-1125): chunks of `chunk_scans` scans travel host -> device on a copy stream into one of two device
  * buffers while the previous chunk runs scvod_batch_process on the ctx's stream; after the launches of a chunk are
