@@ -239,12 +239,17 @@ int scvod_voxelgrid(scvod_ctx* ctx, const float* h_xyzi, const uint32_t* h_label
  * stream: hipStream_t (NULL = the ctx's own stream).  Asynchronous w.r.t. the host
  * unless sync != 0.  d_xyzi must stay valid and unchanged until the next batch call: apri_vec is kept
  * on the device in compact form (source index, voxel key, intensity) and the PointAPRI records,
- * the per-point class array and the tracking probe read the points through it on request. */
+ * the per-point class array and the tracking probe read the points through it on request.
+ * h_scan_offsets is copied into the ctx before the call returns (also with sync == 0): the array is the caller's again at once, and
+ * every later fetch reads the ctx's copy. */
 int scvod_batch_process(scvod_ctx* ctx, const void* d_xyzi, const int32_t* h_scan_offsets,
                         int32_t n_scans, void* stream, int32_t sync);
 
 /* Per-scan counters of the last batch: out[n_scans][8] =
- * {n_points, n_ground, n_nonground, n_dropped, n_apri, n_rejected, n_voxels, 0}. */
+ * {n_points, n_ground, n_nonground, n_dropped, n_apri, n_rejected, n_voxels, 0}.
+ * Exactly the n_scans rows of the LAST batch are written, whatever the ctx's capacity: h_out behind them is left untouched, and
+ * scvod_batch_fetch, scvod_batch_fetch_clusters, scvod_batch_fetch_cluster_types, scvod_batch_fetch_cluster_classes and
+ * scvod_batch_fetch_track refuse a scan index >= that n_scans with SCVOD_ERR_INVALID -- the rows a larger, earlier batch left in the arena are never readable as live data. */
 int scvod_batch_counts(scvod_ctx* ctx, int32_t* h_out);
 
 /* Download the full result of scan `s` of the last batch. */
@@ -572,7 +577,9 @@ int64_t scvod_map_capacity(const scvod_map* map);
 int scvod_map_clear(scvod_map* map, void* stream);
 /* pcl::getTransformation(x, y, z, roll, pitch, yaw) as a row-major 3x4 matrix */
 void scvod_pose_matrix(const float pose[6], float T_out[12]);
-/* adds the static points of every scan of ctx's last batch: h_poses [n_scans][6].  Asynchronous on `stream`. */
+/* adds the static points of every scan of ctx's last batch: h_poses [n_scans][6].  Asynchronous on `stream`; h_poses is turned
+ * into matrices and copied before the call returns (poses that differ from the previous call's wait for `stream` first: the
+ * map's one staging copy may still be in flight). */
 int scvod_batch_map_accumulate(scvod_ctx* ctx, scvod_map* map, const float* h_poses, int32_t flags, void* stream);
 /* the same for scans [first, first + count) of the batch only (a shard's own block, without its halo); h_poses still [n_scans][6] */
 int scvod_batch_map_accumulate_range(scvod_ctx* ctx, scvod_map* map, const float* h_poses, int32_t flags, int32_t first, int32_t count, void* stream);
