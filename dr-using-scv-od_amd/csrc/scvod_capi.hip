@@ -157,6 +157,17 @@ struct scvod_ctx {
     int64_t cal_fetch_cap = 0;
     CalJob cal{};
     bool cal_done = false;       // the stage ran on the current batch
+    // export of the result (scvod_batch_point_labels / scvod_batch_export_points, scvod_export.hip): scratch of its own, allocated by
+    // the first export and NOT counted by scvod_arena_bytes
+    uint8_t* exp_labels = nullptr;   // [cap_pts] the label bytes the compaction reads
+    int32_t* exp_scan_cnt = nullptr; // [cap_scans]
+    float* exp_pose = nullptr;       // [cap_scans][12]
+    long long* exp_stats = nullptr;  // [4]
+    int32_t* exp_tiles = nullptr;    // [exp_tiles_cap] tile counts / prefixes, grown when a batch needs more
+    size_t exp_tiles_cap = 0;
+    std::vector<float> exp_up_pose;  // what exp_pose holds
+    hipStream_t exp_stream = nullptr;  // stream of the last export (scvod_batch_export_stats waits for it)
+    bool exp_ran = false;
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1403,6 +1414,11 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->cal_buf) hipFree(c->cal_buf);
     if (c->cal_fetch) hipFree(c->cal_fetch);
     if (c->chain_ws) hipFree(c->chain_ws);
+    if (c->exp_labels) hipFree(c->exp_labels);
+    if (c->exp_scan_cnt) hipFree(c->exp_scan_cnt);
+    if (c->exp_pose) hipFree(c->exp_pose);
+    if (c->exp_stats) hipFree(c->exp_stats);
+    if (c->exp_tiles) hipFree(c->exp_tiles);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
         if (b) hipFree(b);
@@ -2382,6 +2398,109 @@ int scvod_batch_fetch_track(scvod_ctx* c, int32_t s, scvod_track_result* out) {
     out->pair_label = p_plab;
     out->pair_count = p_pcnt;
     out->pt_dyn = c->tk_stage_dyn.data();
+    return SCVOD_OK;
+}
+
+// ---- the result handed on: per-input-point labels and the kept points of the batch (scvod_export.hip) ----
+// what both calls need of the ctx: a Patchwork batch, its clustering and types, and -- unless the dynamic points are ignored -- a
+// tracking result that is current (the test scvod_batch_map_accumulate applies)
+static int export_check(scvod_ctx* c, int use_dyn, const char* who) {
+    if (!c->batch_valid || c->batch_mode != 1 || !c->A.pts) return fail(c, SCVOD_ERR_STATE, "%s needs a batch of scvod_batch_process", who);
+    if (!c->clusters_valid || !c->types_valid) return fail(c, SCVOD_ERR_STATE, "%s needs scvod_batch_cluster and scvod_batch_cluster_types of the batch", who);
+    if (use_dyn && !c->track_valid) return fail(c, SCVOD_ERR_INVALID, "%s: no current tracking result: run scvod_batch_track or pass SCVOD_MAP_IGNORE_DYNAMIC", who);
+    return merge_check(c);
+}
+
+int scvod_batch_point_labels(scvod_ctx* c, uint8_t* d_labels, int64_t cap, int32_t flags, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!d_labels || cap < 0) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (flags & ~SCVOD_MAP_IGNORE_DYNAMIC) return fail(c, SCVOD_ERR_INVALID, "scvod_batch_point_labels takes SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", flags);
+    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
+    if (int rc = export_check(c, use_dyn, "scvod_batch_point_labels")) return rc;
+    if (cap < c->A.total_pts) return fail(c, SCVOD_ERR_CAPACITY, "label buffer too small (%lld < %lld points)", (long long)cap, (long long)c->A.total_pts);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    if (c->A.total_pts > 0) {
+        HIPCHK(c, hipMemsetAsync(d_labels, SCVOD_PT_DROPPED, (size_t)c->A.total_pts, st));
+        launch_point_labels(c->A, d_labels, use_dyn, st);
+        HIPCHK(c, hipGetLastError());
+    }
+    return SCVOD_OK;
+}
+
+int scvod_batch_export_points(scvod_ctx* c, int32_t flags, const float* h_poses, const uint32_t* d_payload_in, void* d_xyzi_out,
+                              uint32_t* d_payload_out, int32_t* d_src_out, int64_t cap_points, int32_t* d_out_offsets, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (cap_points < 0 || !d_out_offsets) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (flags & ~(SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED | SCVOD_MAP_IGNORE_DYNAMIC))
+        return fail(c, SCVOD_ERR_INVALID, "scvod_batch_export_points takes SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED and SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", flags);
+    if (d_payload_out && !d_payload_in) return fail(c, SCVOD_ERR_INVALID, "a payload output needs a payload input");
+    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
+    if (int rc = export_check(c, use_dyn, "scvod_batch_export_points")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    const int B = c->A.n_scans;
+    if (!c->exp_labels) {  // first export of this ctx
+        HIPCHK(c, hipMalloc(&c->exp_labels, (size_t)(c->cap_pts > 0 ? c->cap_pts : 1)));
+        HIPCHK(c, hipMalloc(&c->exp_scan_cnt, sizeof(int32_t) * (size_t)c->cap_scans));
+        HIPCHK(c, hipMalloc(&c->exp_pose, sizeof(float) * 12 * (size_t)c->cap_scans));
+        HIPCHK(c, hipMalloc(&c->exp_stats, sizeof(long long) * 4));
+    }
+    const int tps = (c->A.max_scan_pts + kExpTile - 1) / kExpTile;
+    const size_t tiles = (size_t)B * (size_t)tps;
+    if (tiles > c->exp_tiles_cap) {  // (a batch with more tiles than any before: the old table may still be read by an export in flight)
+        if (c->exp_tiles) {
+            HIPCHK(c, hipStreamSynchronize(c->exp_stream));
+            hipFree(c->exp_tiles);
+            c->exp_tiles = nullptr;
+            c->exp_tiles_cap = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->exp_tiles, sizeof(int32_t) * (tiles + tiles / 2)));
+        c->exp_tiles_cap = tiles + tiles / 2;
+    }
+    if (h_poses) {  // pcl::getTransformation per scan, staged before the call returns: h_poses is the caller's again at once
+        std::vector<float> T((size_t)12 * B);
+        for (int s = 0; s < B; ++s) scvod_pose_matrix(h_poses + 6 * s, T.data() + 12 * s);
+        if (int rc = upload_if_changed(c, c->exp_up_pose, T.data(), T.size(), c->exp_pose, st)) return rc;
+    }
+    if (c->A.total_pts > 0) {
+        HIPCHK(c, hipMemsetAsync(c->exp_labels, SCVOD_PT_DROPPED, (size_t)c->A.total_pts, st));
+        launch_point_labels(c->A, c->exp_labels, use_dyn, st);
+    }
+    ExportJob J;
+    J.labels = c->exp_labels;
+    J.keep_mask = (1u << SCVOD_PT_UNCLUSTERED) | (1u << SCVOD_PT_STATIC_OTHER) | (1u << SCVOD_PT_STATIC_CAR);
+    if (!(flags & SCVOD_MAP_NO_GROUND)) J.keep_mask |= 1u << SCVOD_PT_GROUND;
+    if (!(flags & SCVOD_MAP_NO_REJECTED)) J.keep_mask |= 1u << SCVOD_PT_REJECTED;
+    if (!use_dyn) J.keep_mask |= 1u << SCVOD_PT_DYNAMIC;  // (no label says DYNAMIC then: the bit only states the rule)
+    J.pose = h_poses ? c->exp_pose : nullptr;
+    J.payload_in = d_payload_in;
+    J.out = (float4*)d_xyzi_out;
+    J.payload_out = d_payload_out;
+    J.src_out = d_src_out;
+    J.cap = (long long)cap_points;
+    J.out_off = d_out_offsets;
+    J.tile_cnt = c->exp_tiles;
+    J.scan_cnt = c->exp_scan_cnt;
+    J.stats = c->exp_stats;
+    J.tiles_per_scan = tps;
+    launch_export(c->A, J, st);
+    HIPCHK(c, hipGetLastError());
+    c->exp_stream = st;
+    c->exp_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_export_stats(scvod_ctx* c, int64_t* h_out4) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out4) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->exp_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_batch_export_points on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long h[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, c->exp_stats, sizeof(h), hipMemcpyDeviceToHost, c->exp_stream));
+    HIPCHK(c, hipStreamSynchronize(c->exp_stream));
+    for (int k = 0; k < 4; ++k) h_out4[k] = (int64_t)h[k];
+    if (h[2]) return fail(c, SCVOD_ERR_CAPACITY, "the last export kept %lld points, its buffers hold %lld", h[1], h[0]);
     return SCVOD_OK;
 }
 

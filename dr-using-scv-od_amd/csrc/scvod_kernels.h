@@ -282,6 +282,28 @@ struct CalJob {
     unsigned long long* cand;      // [1] candidates examined (with stats)
 };
 
+// export of a batch's result (scvod_batch_point_labels / scvod_batch_export_points; scvod_export.hip): one SCVOD_PT_* byte per INPUT
+// point, and the kept points compacted in input order.  A scan is cut into tiles of kExpTile points (256 threads x 8 rounds, round u
+// covers the points tile + u * 256 + thread); the tiles of scan s are tile_cnt[s * tiles_per_scan ..).  Scratch of its own (not the arena).
+constexpr int kExpTile = 2048;
+struct ExportJob {
+    const uint8_t* labels;         // [total points] the label bytes the export reads (its own buffer, never the map's marks)
+    uint32_t keep_mask;            // bit L set: points labelled L are kept
+    const float* pose;             // [B][12] row-major 3x4 per scan, or nullptr: sensor frame
+    const uint32_t* payload_in;    // [total points] or nullptr
+    float4* out;                   // caller's buffers: nullptr = count only
+    uint32_t* payload_out;         // or nullptr
+    int32_t* src_out;              // or nullptr
+    long long cap;                 // points the caller's buffers hold
+    int32_t* out_off;              // [B + 1] caller's
+    int32_t* tile_cnt;             // [B * tiles_per_scan] kept points per tile, then their exclusive prefix inside the scan
+    int32_t* scan_cnt;             // [B] kept points per scan
+    long long* stats;              // [4] points written, points kept, 1 = the output outgrew cap, 0
+    int32_t tiles_per_scan;
+};
+void launch_point_labels(const Arena& A, uint8_t* labels, int use_dyn, hipStream_t st);
+void launch_export(const Arena& A, const ExportJob& J, hipStream_t st);
+
 typedef void (*TimerHook)(void* user, const char* name, int begin);
 
 // Launches.  `th`/`tu` optional per-kernel timing hook (called before and after each launch).

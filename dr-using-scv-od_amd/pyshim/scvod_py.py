@@ -172,6 +172,9 @@ def load_lib():
         "scvod_map_export_parts": (C.c_int, [vp, i32, vp, i64, vp, vp]),
         "scvod_map_export_parts_padded": (C.c_int, [vp, i32, vp, i64, vp, vp]),
         "scvod_map_points": (C.c_int, [vp, vp, vp, i64, C.POINTER(i64), vp]),
+        "scvod_batch_point_labels": (C.c_int, [vp, vp, i64, i32, vp]),
+        "scvod_batch_export_points": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
+        "scvod_batch_export_stats": (C.c_int, [vp, vp]),
         "scvod_batch_timings": (C.c_int, [vp, vp, vp, i32]),
         "scvod_set_timing": (C.c_int, [vp, i32]),
         "scvod_nn_search": (C.c_int, [vp, vp, i32, vp, i32, f32, vp, vp, vp]),
@@ -196,6 +199,7 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_set_region_growing", "scvod_batch_fetch_cluster_classes", "scvod_batch_fetch_region_growing", "scvod_batch_region_growing_stats", "scvod_set_intensity_calibration", "scvod_batch_fetch_intensity_calibration", "scvod_batch_intensity_calibration_stats", "scvod_batch_intensity_calibration_candidates", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
                     "scvod_map_create", "scvod_map_destroy", "scvod_map_last_error", "scvod_map_capacity", "scvod_map_clear",
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
+                    "scvod_batch_point_labels", "scvod_batch_export_points", "scvod_batch_export_stats",
                     "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid"]
 
 
@@ -348,6 +352,7 @@ class Ctx:
     def batch_process(self, d_xyzi, scan_offsets, stream=None, sync=True):
         off, po = self._i32(scan_offsets)
         self._n_scans = off.shape[0] - 1
+        self._n_pts = int(off[-1])
         ptr = C.c_void_p(d_xyzi.data_ptr())
         self._chk(self.lib.scvod_batch_process(self.h, ptr, po, self._n_scans, C.c_void_p(stream or 0), int(sync)))
 
@@ -605,6 +610,47 @@ class Ctx:
         self._chk(self.lib.scvod_batch_export_table(self.h, int(s), C.c_void_p(d_out.data_ptr()), int(d_out.shape[0]),
                                                     C.c_void_p(stream or 0)))
 
+    # ---- the result handed on (include/scvod.h: scvod_batch_point_labels ...) ----
+    def batch_point_labels(self, d_labels=None, flags=0, stream=None):
+        """one PT_* byte per INPUT point of the last batch into d_labels (a torch uint8 device tensor of at least the batch's point
+        count; allocated when None).  Asynchronous on `stream`; flags 0 or MAP_IGNORE_DYNAMIC"""
+        if d_labels is None:
+            import torch
+            d_labels = torch.empty(max(self._n_pts, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        self._chk(self.lib.scvod_batch_point_labels(self.h, C.c_void_p(d_labels.data_ptr()), int(d_labels.numel()), int(flags),
+                                                    C.c_void_p(stream or 0)))
+        return d_labels
+
+    def batch_export_points(self, d_out_offsets, d_xyzi_out=None, flags=0, poses=None, d_payload_in=None, d_payload_out=None,
+                            d_src_out=None, stream=None):
+        """the kept points of the last batch, compacted in input order, into d_xyzi_out (torch float32 device tensor [cap, 4]; None:
+        count only); d_out_offsets: torch int32 device tensor [n_scans + 1]; d_src_out int32 [cap], d_payload_in uint32-sized words
+        per input point, d_payload_out the same per exported point (int32 tensors do).  poses None: sensor frame, else [n_scans, 6]
+        (copied before the call returns).  Asynchronous on `stream`: batch_export_stats() tells how many points there were"""
+        assert d_out_offsets.numel() >= self._n_scans + 1
+        cap = 0
+        if d_xyzi_out is not None:
+            assert d_xyzi_out.is_contiguous() and d_xyzi_out.numel() % 4 == 0
+            cap = d_xyzi_out.numel() // 4
+            for t in (d_src_out, d_payload_out):
+                assert t is None or t.numel() >= cap
+        pp = None
+        if poses is not None:
+            p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+            assert p.shape[0] == self._n_scans
+            pp = p.ctypes.data_as(C.c_void_p)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.scvod_batch_export_points(self.h, int(flags), pp, ptr(d_payload_in), ptr(d_xyzi_out), ptr(d_payload_out),
+                                                     ptr(d_src_out), int(cap), ptr(d_out_offsets), C.c_void_p(stream or 0)))
+
+    def batch_export_stats(self):
+        """{written, kept, overflow} of the last batch_export_points; synchronises its stream; raises when that export overflowed"""
+        out = np.zeros(4, np.int64)
+        self._chk(self.lib.scvod_batch_export_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(written=int(out[0]), kept=int(out[1]), overflow=bool(out[2]))
+
     def set_timing(self, on):
         self._chk(self.lib.scvod_set_timing(self.h, int(bool(on))))
 
@@ -684,6 +730,8 @@ class Ctx:
 
 
 MAP_NO_GROUND, MAP_NO_REJECTED, MAP_IGNORE_DYNAMIC = 1, 2, 4
+# scvod_batch_point_labels: one byte per input point (include/scvod.h, SCVOD_PT_*)
+PT_DROPPED, PT_GROUND, PT_REJECTED, PT_UNCLUSTERED, PT_STATIC_OTHER, PT_STATIC_CAR, PT_DYNAMIC = range(7)
 
 
 class StaticMap:

@@ -603,6 +603,56 @@ int scvod_map_merge(scvod_map* map, const void* d_records, int64_t n, void* stre
 /* the map as points: d_xyzi [cap][4] floats (cell origin + stored offset, intensity), optionally the records beside them */
 int scvod_map_points(scvod_map* map, void* d_xyzi, void* d_records, int64_t cap, int64_t* n_out, void* stream);
 
+/* ---- the result of a batch handed on: per-point labels and the cleaned scans, on the device -------------------------------
+ * Reference analogue: the `static_pt` / `dynamic_pt` lists of SSC::saveSegCloud mode 3 (src/ssc.cpp:477-554) and the clouds of the
+ * evaluation block (`cloud_eva_static`, `g_cloud_vec`, the _static / _dynamic / _original .pcd files, ssc.cpp:1454-1540).  The
+ * static map above keeps one point per cell; these two calls hand out the scans themselves.  Both are stream-ordered (stream NULL =
+ * the stream of the ctx's last batch call), launch and allocate nothing unless they are called, never synchronise with the host,
+ * change no other output of the batch, and read marks of their own: what the static map reads per input point stays as it was.
+ *
+ * One byte per INPUT point, index scan_offsets[s] + i: */
+#define SCVOD_PT_DROPPED 0       /* in neither Patchwork cloud: SCVOD_CLS_DROPPED (outside the range gate, below the z cut, a
+                                    patch of at most num_min_pts points)                                                     */
+#define SCVOD_PT_GROUND 1        /* member of cloud_out                                                                       */
+#define SCVOD_PT_REJECTED 2      /* non-ground, failed the range/FOV test (cloud_eva_static, rejected_src)                    */
+#define SCVOD_PT_UNCLUSTERED 3   /* apri point whose cluster refineClusterByBoundingBox erased (SCVOD_DYN_UNCLUSTERED)        */
+#define SCVOD_PT_STATIC_OTHER 4  /* apri point of a cluster that is neither dynamic nor `car`                                 */
+#define SCVOD_PT_STATIC_CAR 5    /* apri point of a `car` cluster that is not dynamic (state -1, a scan without a successor,
+                                    included)                                                                                 */
+#define SCVOD_PT_DYNAMIC 6       /* pt_dyn == SCVOD_DYN_DYNAMIC                                                               */
+/* Writes the labels of the last batch into d_labels (device memory of `cap` >= the batch's point count bytes; SCVOD_ERR_CAPACITY
+ * otherwise).  The type is the segmentation's, what scvod_batch_fetch_cluster_types reports (the fused partition's when the
+ * intensity merge is on), not the type the tracking chain re-assigns to a predecessor at ssc.cpp:1354; the region growing's
+ * building / tree split is not carried into the byte.  Needs scvod_batch_cluster and scvod_batch_cluster_types of the batch
+ * (SCVOD_ERR_STATE) and a CURRENT scvod_batch_track -- the validity test scvod_batch_map_accumulate applies; SCVOD_ERR_INVALID when
+ * the tracking result is missing or stale.  flags: 0 or SCVOD_MAP_IGNORE_DYNAMIC -- the clustering and the types suffice then,
+ * and no point is labelled SCVOD_PT_DYNAMIC. */
+int scvod_batch_point_labels(scvod_ctx* ctx, uint8_t* d_labels, int64_t cap, int32_t flags, void* stream);
+/* The kept points of every scan of the last batch, compacted: scans concatenated in batch order, inside a scan in INPUT order (a
+ * stable compaction: the output is bit-identical from run to run).  The keep rule is that of scvod_batch_map_accumulate and a
+ * function of the label byte alone: SCVOD_PT_DROPPED never; SCVOD_PT_DYNAMIC only with SCVOD_MAP_IGNORE_DYNAMIC; SCVOD_PT_GROUND
+ * unless SCVOD_MAP_NO_GROUND; SCVOD_PT_REJECTED unless SCVOD_MAP_NO_REJECTED; everything else always.  The part flags (and any
+ * other bit) are refused with SCVOD_ERR_INVALID; the state the call needs is that of scvod_batch_point_labels with the same flags.
+ *   d_xyzi_out     [cap_points] packed float4 records, or NULL: count only (the offsets and the sizes are still produced, nothing
+ *                  else is written)
+ *   d_out_offsets  [n_scans + 1] device array: scan s owns the records [d_out_offsets[s], d_out_offsets[s + 1]); always the TRUE sizes
+ *   d_src_out      [cap_points] or NULL: the input index inside its scan of every exported point
+ *   d_payload_in   [batch points] or NULL: one uint32 per input point (e.g. SemanticKITTI labels), carried along into
+ *   d_payload_out  [cap_points] or NULL
+ *   h_poses        NULL: sensor frame, the records are the input's bit for bit.  Otherwise [n_scans][6] poses, turned into matrices
+ *                  as scvod_batch_map_accumulate does (scvod_pose_matrix) and staged before the call returns -- the array is the
+ *                  caller's again at once; a point moves by T0*x + T1*y + T2*z + T3 per row, evaluated left to right in fp32 without
+ *                  contraction (the map kernel's expression); the intensity is untouched.
+ * When the kept points outgrow cap_points nothing is written at or behind the capacity, and the overflow is latched until the next
+ * export.  Scratch (one byte per point and 12 floats per scan of the ctx's capacity, one word per 2048 points of a scan) is
+ * allocated by the first export and is NOT part of scvod_arena_bytes. */
+int scvod_batch_export_points(scvod_ctx* ctx, int32_t flags, const float* h_poses, const uint32_t* d_payload_in, void* d_xyzi_out,
+                              uint32_t* d_payload_out, int32_t* d_src_out, int64_t cap_points, int32_t* d_out_offsets, void* stream);
+/* h_out4 = {points written, points kept (the capacity the export needs), 1 when the last export outgrew its buffers, 0} of the last
+ * scvod_batch_export_points (points written is 0 for a count-only call).  Synchronises that export's stream.  Returns
+ * SCVOD_ERR_CAPACITY when the last export overflowed, SCVOD_ERR_STATE before the first export. */
+int scvod_batch_export_stats(scvod_ctx* ctx, int64_t* h_out4);
+
 #ifdef __cplusplus
 }
 #endif
