@@ -168,6 +168,19 @@ struct scvod_ctx {
     std::vector<float> exp_up_pose;  // what exp_pose holds
     hipStream_t exp_stream = nullptr;  // stream of the last export (scvod_batch_export_stats waits for it)
     bool exp_ran = false;
+    // object table (scvod_batch_objects, scvod_objects.hip): scratch of its own, the small part allocated by the first call, the per-point
+    // part by the first call that asks for more than the counts; not part of the arena
+    int32_t* obj_scan_cnt = nullptr;  // [cap_scans][2]
+    long long* obj_stats = nullptr;   // [4]
+    int32_t* obj_tiles = nullptr;     // [obj_tiles_cap][2], grown when a batch needs more
+    size_t obj_tiles_cap = 0;
+    uint64_t* obj_keys = nullptr;     // [2 cap_pts] keys in, keys out
+    int32_t* obj_words = nullptr;     // [3 cap_pts + 1] root_obj, nvox, begin
+    void* obj_sort_tmp = nullptr;
+    size_t obj_sort_bytes = 0;
+    int64_t obj_bytes = 0;
+    hipStream_t obj_stream = nullptr;  // stream of the last call (scvod_batch_objects_stats waits for it)
+    bool obj_ran = false;
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1419,6 +1432,12 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->exp_pose) hipFree(c->exp_pose);
     if (c->exp_stats) hipFree(c->exp_stats);
     if (c->exp_tiles) hipFree(c->exp_tiles);
+    if (c->obj_scan_cnt) hipFree(c->obj_scan_cnt);
+    if (c->obj_stats) hipFree(c->obj_stats);
+    if (c->obj_tiles) hipFree(c->obj_tiles);
+    if (c->obj_keys) hipFree(c->obj_keys);
+    if (c->obj_words) hipFree(c->obj_words);
+    if (c->obj_sort_tmp) hipFree(c->obj_sort_tmp);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
         if (b) hipFree(b);
@@ -2503,6 +2522,97 @@ int scvod_batch_export_stats(scvod_ctx* c, int64_t* h_out4) {
     if (h[2]) return fail(c, SCVOD_ERR_CAPACITY, "the last export kept %lld points, its buffers hold %lld", h[1], h[0]);
     return SCVOD_OK;
 }
+
+// ---- the clusters of the batch as an object table (scvod_objects.hip) ----
+int scvod_batch_objects(scvod_ctx* c, int32_t flags, void* d_objects, int64_t cap_objects, int32_t* d_obj_offsets, int32_t* d_member_src,
+                        int64_t cap_members, int32_t* d_point_object, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (cap_objects < 0 || cap_members < 0 || !d_obj_offsets) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (flags & ~SCVOD_OBJ_NO_TRACK) return fail(c, SCVOD_ERR_INVALID, "scvod_batch_objects takes SCVOD_OBJ_NO_TRACK only (flags %d)", flags);
+    const int use_track = (flags & SCVOD_OBJ_NO_TRACK) ? 0 : 1;
+    if (int rc = export_check(c, use_track, "scvod_batch_objects")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    const int B = c->A.n_scans;
+    const size_t N = (size_t)(c->cap_pts > 0 ? c->cap_pts : 1);
+    if (!c->obj_stats) {  // first call of this ctx
+        HIPCHK(c, hipMalloc(&c->obj_scan_cnt, sizeof(int32_t) * 2 * (size_t)c->cap_scans));
+        HIPCHK(c, hipMalloc(&c->obj_stats, sizeof(long long) * 4));
+        c->obj_bytes += (int64_t)(sizeof(int32_t) * 2 * (size_t)c->cap_scans + sizeof(long long) * 4);
+    }
+    const int tps = (c->A.max_scan_pts + kExpTile - 1) / kExpTile;
+    const size_t tiles = (size_t)B * (size_t)tps;
+    if (tiles > c->obj_tiles_cap) {  // (the old table may still be read by a call in flight)
+        if (c->obj_tiles) {
+            HIPCHK(c, hipStreamSynchronize(c->obj_stream));
+            hipFree(c->obj_tiles);
+            c->obj_tiles = nullptr;
+            c->obj_bytes -= (int64_t)(sizeof(int32_t) * 2 * c->obj_tiles_cap);
+            c->obj_tiles_cap = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->obj_tiles, sizeof(int32_t) * 2 * (tiles + tiles / 2)));
+        c->obj_tiles_cap = tiles + tiles / 2;
+        c->obj_bytes += (int64_t)(sizeof(int32_t) * 2 * c->obj_tiles_cap);
+    }
+    const bool lists = d_objects || d_member_src || d_point_object;
+    if (lists && !c->obj_keys) {  // first call that asks for more than the counts
+        c->obj_sort_bytes = obj_sort_bytes((long long)N);
+        HIPCHK(c, hipMalloc(&c->obj_keys, sizeof(uint64_t) * 2 * N));
+        HIPCHK(c, hipMalloc(&c->obj_words, sizeof(int32_t) * (3 * N + 1)));
+        HIPCHK(c, hipMalloc(&c->obj_sort_tmp, c->obj_sort_bytes > 0 ? c->obj_sort_bytes : 16));
+        c->obj_bytes += (int64_t)(sizeof(uint64_t) * 2 * N + sizeof(int32_t) * (3 * N + 1) + c->obj_sort_bytes);
+    }
+    if (lists) {  // (the sort's workspace is asked for per size; one sized for the capacity normally holds every batch)
+        const size_t need = obj_sort_bytes((long long)c->A.total_pts);
+        if (need > c->obj_sort_bytes) {
+            HIPCHK(c, hipStreamSynchronize(c->obj_stream ? c->obj_stream : st));
+            hipFree(c->obj_sort_tmp);
+            c->obj_sort_tmp = nullptr;
+            HIPCHK(c, hipMalloc(&c->obj_sort_tmp, need));
+            c->obj_bytes += (int64_t)(need - c->obj_sort_bytes);
+            c->obj_sort_bytes = need;
+        }
+    }
+    ObjectJob J;
+    J.use_track = use_track;
+    J.cls = c->rg_done ? c->rg.cls : c->A.pt_type;  // (without the stage: pt_type, whose `other` is tree)
+    J.out = (scvod_object*)d_objects;
+    J.cap_obj = (long long)cap_objects;
+    J.obj_off = d_obj_offsets;
+    J.member_src = d_member_src;
+    J.cap_mem = (long long)cap_members;
+    J.point_object = d_point_object;
+    J.tile_cnt = c->obj_tiles;
+    J.scan_cnt = c->obj_scan_cnt;
+    J.stats = c->obj_stats;
+    J.key_in = lists ? c->obj_keys : nullptr;
+    J.key_out = lists ? c->obj_keys + N : nullptr;
+    J.root_obj = lists ? c->obj_words : nullptr;
+    J.nvox = lists ? c->obj_words + N : nullptr;
+    J.begin = lists ? c->obj_words + 2 * N : nullptr;
+    J.tiles_per_scan = tps;
+    if (d_point_object && c->A.total_pts > 0) HIPCHK(c, hipMemsetAsync(d_point_object, 0xff, sizeof(int32_t) * (size_t)c->A.total_pts, st));
+    HIPCHK(c, launch_objects(c->A, J, c->obj_sort_tmp, c->obj_sort_bytes, st));
+    HIPCHK(c, hipGetLastError());
+    c->obj_stream = st;
+    c->obj_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_objects_stats(scvod_ctx* c, int64_t* h_out4) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out4) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->obj_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_batch_objects on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long h[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, c->obj_stats, sizeof(h), hipMemcpyDeviceToHost, c->obj_stream));
+    HIPCHK(c, hipStreamSynchronize(c->obj_stream));
+    for (int k = 0; k < 4; ++k) h_out4[k] = (int64_t)h[k];
+    if (h[3]) return fail(c, SCVOD_ERR_CAPACITY, "the last object table holds %lld objects and %lld member points: a buffer was too small", h[1], h[2]);
+    return SCVOD_OK;
+}
+
+int64_t scvod_batch_objects_scratch_bytes(scvod_ctx* c) { return c ? c->obj_bytes : 0; }
 
 // Streaming ingest of a sequence that lives in HOST memory (the reference reads one .bin per scan from disk,
 // SSC::getCloud ssc.cpp:1040-1125): chunks of scans are copied host -> device on a copy stream into one of two buffers

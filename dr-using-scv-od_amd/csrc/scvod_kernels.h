@@ -304,6 +304,32 @@ struct ExportJob {
 void launch_point_labels(const Arena& A, uint8_t* labels, int use_dyn, hipStream_t st);
 void launch_export(const Arena& A, const ExportJob& J, hipStream_t st);
 
+// the clusters of a batch as an object table (scvod_batch_objects; scvod_objects.hip).  Tiles as in the export, over the APRI points of a
+// scan; per tile two words {objects, member points}, the first turned into its exclusive prefix inside the scan.  Scratch of its own (not
+// the arena): per point of the ctx's capacity unless stated.
+struct ObjectJob {
+    int32_t use_track;             // 0: SCVOD_OBJ_NO_TRACK (state -1, dynamic 0 everywhere)
+    const uint8_t* cls;            // [N] per apri point: 1 tree / other, 2 car, 3 building (the region growing's bytes when it ran, else pt_type)
+    scvod_object* out;             // caller's buffers: nullptr = no records
+    long long cap_obj;
+    int32_t* obj_off;              // [B + 1] caller's
+    int32_t* member_src;           // or nullptr
+    long long cap_mem;
+    int32_t* point_object;         // [total points] or nullptr; cleared to -1 by the caller of launch_objects
+    int32_t* tile_cnt;             // [2 B tiles_per_scan]
+    int32_t* scan_cnt;             // [2 B] objects, member points per scan
+    long long* stats;              // [4] objects written, objects found, member slots needed, 1 = a buffer was outgrown
+    uint64_t* key_in;              // [N] (object << 32 | apri position) per slot, upper word ~0 for a point of no object; nullptr: count only
+    uint64_t* key_out;             // [N] sorted on the object bits: [0, members) is the member list
+    int32_t* root_obj;             // [N] per object root (scan_off[s] + name): its index in the table
+    int32_t* begin;                // [N + 1] per object: first slot of its run in key_out; [objects] = members
+    int32_t* nvox;                 // [N] per object: occupy_voxels.size()
+    int32_t tiles_per_scan;
+};
+int obj_sort_bits(long long total_pts);
+size_t obj_sort_bytes(long long cap_pts);  // temporary storage of the radix sort of a batch's keys
+hipError_t launch_objects(const Arena& A, const ObjectJob& J, void* sort_tmp, size_t sort_bytes, hipStream_t st);  // (the sort's status)
+
 typedef void (*TimerHook)(void* user, const char* name, int begin);
 
 // Launches.  `th`/`tu` optional per-kernel timing hook (called before and after each launch).

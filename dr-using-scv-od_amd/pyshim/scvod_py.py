@@ -40,6 +40,19 @@ PLANE_DTYPE = np.dtype([("normal", "f4", 3), ("mean", "f4", 3), ("sv", "f4", 3),
 assert APRI_DTYPE.itemsize == 44 and PLANE_DTYPE.itemsize == 48
 
 
+# struct scvod_object (include/scvod.h): one cluster of the object table, 64 bytes
+OBJECT_DTYPE = np.dtype([("scan", "i4"), ("name", "i4"), ("n_points", "i4"), ("n_voxels", "i4"), ("box_min", "f4", 3),
+                         ("box_max", "f4", 3), ("center", "f4", 3), ("angle_diff", "f4"), ("cls", "i1"), ("state", "i1"),
+                         ("dynamic", "u1"), ("reserved", "u1"), ("point_begin", "i4")])
+OBJ_NO_TRACK = 1
+
+
+class Object(C.Structure):
+    _fields_ = [("scan", C.c_int32), ("name", C.c_int32), ("n_points", C.c_int32), ("n_voxels", C.c_int32),
+                ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("center", C.c_float * 3), ("angle_diff", C.c_float),
+                ("cls", C.c_int8), ("state", C.c_int8), ("dynamic", C.c_uint8), ("reserved", C.c_uint8), ("point_begin", C.c_int32)]
+
+
 class ScanResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_points", "n_ground", "n_nonground", "n_dropped", "n_apri", "n_rejected",
                                           "n_voxels", "n_patches")] + \
@@ -175,6 +188,9 @@ def load_lib():
         "scvod_batch_point_labels": (C.c_int, [vp, vp, i64, i32, vp]),
         "scvod_batch_export_points": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
         "scvod_batch_export_stats": (C.c_int, [vp, vp]),
+        "scvod_batch_objects": (C.c_int, [vp, i32, vp, i64, vp, vp, i64, vp, vp]),
+        "scvod_batch_objects_stats": (C.c_int, [vp, vp]),
+        "scvod_batch_objects_scratch_bytes": (i64, [vp]),
         "scvod_batch_timings": (C.c_int, [vp, vp, vp, i32]),
         "scvod_set_timing": (C.c_int, [vp, i32]),
         "scvod_nn_search": (C.c_int, [vp, vp, i32, vp, i32, f32, vp, vp, vp]),
@@ -200,6 +216,7 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_map_create", "scvod_map_destroy", "scvod_map_last_error", "scvod_map_capacity", "scvod_map_clear",
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
                     "scvod_batch_point_labels", "scvod_batch_export_points", "scvod_batch_export_stats",
+                    "scvod_batch_objects", "scvod_batch_objects_stats", "scvod_batch_objects_scratch_bytes",
                     "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid"]
 
 
@@ -650,6 +667,37 @@ class Ctx:
         out = np.zeros(4, np.int64)
         self._chk(self.lib.scvod_batch_export_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return dict(written=int(out[0]), kept=int(out[1]), overflow=bool(out[2]))
+
+    # ---- the clusters as an object table (include/scvod.h: scvod_batch_objects) ----
+    def batch_objects(self, d_obj_offsets, d_objects=None, flags=0, d_member_src=None, d_point_object=None, stream=None):
+        """the clusters of the last batch that survived the box refine as OBJECT_DTYPE records into d_objects (a contiguous torch
+        device tensor of 64-byte rows, e.g. uint8 [cap, 64]; None: no records); d_obj_offsets: torch int32 device tensor
+        [n_scans + 1]; d_member_src int32 [cap_members]: the input index of every member point, grouped by object; d_point_object
+        int32 [batch points]: the object of every input point, -1 for none.  flags 0 or OBJ_NO_TRACK.  Asynchronous on `stream`:
+        batch_objects_stats() tells how many objects and member points there were"""
+        assert d_obj_offsets.numel() >= self._n_scans + 1
+        cap = 0
+        if d_objects is not None:
+            nbytes = d_objects.numel() * d_objects.element_size()
+            assert d_objects.is_contiguous() and nbytes % OBJECT_DTYPE.itemsize == 0
+            cap = nbytes // OBJECT_DTYPE.itemsize
+        assert d_point_object is None or d_point_object.numel() >= self._n_pts
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.scvod_batch_objects(self.h, int(flags), ptr(d_objects), int(cap), ptr(d_obj_offsets), ptr(d_member_src),
+                                               int(d_member_src.numel()) if d_member_src is not None else 0, ptr(d_point_object),
+                                               C.c_void_p(stream or 0)))
+
+    def batch_objects_stats(self):
+        """{written, objects, members, overflow} of the last batch_objects; synchronises its stream; raises when that call overflowed"""
+        out = np.zeros(4, np.int64)
+        self._chk(self.lib.scvod_batch_objects_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(written=int(out[0]), objects=int(out[1]), members=int(out[2]), overflow=bool(out[3]))
+
+    def batch_objects_scratch_bytes(self):
+        """device scratch of the object table on this ctx (not part of arena_bytes)"""
+        return int(self.lib.scvod_batch_objects_scratch_bytes(self.h))
 
     def set_timing(self, on):
         self._chk(self.lib.scvod_set_timing(self.h, int(bool(on))))

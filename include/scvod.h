@@ -653,6 +653,61 @@ int scvod_batch_export_points(scvod_ctx* ctx, int32_t flags, const float* h_pose
  * SCVOD_ERR_CAPACITY when the last export overflowed, SCVOD_ERR_STATE before the first export. */
 int scvod_batch_export_stats(scvod_ctx* ctx, int64_t* h_out4);
 
+/* ---- the clusters of a batch as an object table, on the device ---------------------------------------------------------------
+ * Reference analogue: Frame::cluster_set as SSC::segDF leaves it per scan -- Cluster::name / type / state / bounding_box / occupy_pts /
+ * occupy_voxels (include/utility.h:142-162; src/ssc.cpp:377-385, 437-467, 844-872) and the box columns of the feature row that
+ * getDescriptorByEigenValue fills (ssc.cpp:723-751).  Listed are exactly the members of cluster_set after
+ * refineClusterByBoundingBox: the clusters whose type is not "erased".  Order: scans in batch order, inside a scan ascending canonical
+ * name; the table is bit-identical from run to run.  One record is 64 bytes: */
+typedef struct scvod_object {
+    int32_t scan;        /* index of the scan in the batch                                                                      */
+    int32_t name;        /* canonical cluster name: the smallest apri index of the cluster, scan-local (the fused cluster's name
+                            with the intensity merge on)                                                                        */
+    int32_t n_points;    /* occupy_pts.size()                                                                                   */
+    int32_t n_voxels;    /* occupy_voxels.size() after sampleVec: the distinct voxel_idx among the cluster's points
+                            (ssc.cpp:365, 383) -- also where a voxel's first point belongs to another cluster                   */
+    float box_min[3];    /* pcl::getMinMax3D over the cluster's points (ssc.cpp:421-425): plain float min / max, exact and       */
+    float box_max[3];    /*   order-independent (-0 orders below +0)                                                             */
+    float center[3];     /* getCenterOfCloud (ssc.cpp:427-435): three sequential fp32 sums over the cluster's points in ascending
+                            apri index, each divided by (float)n_points, no contraction                    */
+    float angle_diff;    /* f_11(0, 8) = fabs(getPolarAngle(point_max) - getPolarAngle(point_min)) (ssc.cpp:731-733), with
+                            PointAPRI::angle's float expression                                                                  */
+    int8_t cls;          /* 1 tree / other, 2 car, 3 building (only when the region growing ran on the last
+                            scvod_batch_cluster_types): what scvod_batch_fetch_cluster_classes reports                           */
+    int8_t state;        /* Cluster::state of a car cluster as scvod_batch_fetch_track's cluster_state reports it; -1 for every
+                            other cluster, and everywhere with SCVOD_OBJ_NO_TRACK                                                */
+    uint8_t dynamic;     /* 1 iff the cluster's points carry SCVOD_DYN_DYNAMIC                                                   */
+    uint8_t reserved;    /* 0                                                                                                    */
+    int32_t point_begin; /* first slot of the cluster's members in the member list, counted over the whole batch                */
+} scvod_object;
+/* The remaining columns of the reference's 11-value feature row follow from the record and are not stored: point_max.z = box_max[2];
+ * square = (double)(box_max[0] - box_min[0]) * (double)(box_max[1] - box_min[1]) (the library's cc_box_square); point_min.z =
+ * box_min[2]; the six constants 1.0; type = cls.
+ *
+ * scvod_batch_objects is stream-ordered (stream NULL = the stream of the ctx's last batch call), never synchronises with the host,
+ * launches and allocates nothing unless it is called, reads the arena and writes only the caller's buffers and scratch of its own
+ * (allocated on first use, NOT part of scvod_arena_bytes: scvod_batch_objects_scratch_bytes reports it; about 28 bytes per point of
+ * the ctx's capacity plus the sort's workspace once a call asks for more than the counts).  Needs scvod_batch_cluster and
+ * scvod_batch_cluster_types of the batch (SCVOD_ERR_STATE) and a CURRENT scvod_batch_track (SCVOD_ERR_INVALID when it is missing or
+ * stale), exactly as scvod_batch_point_labels; with SCVOD_OBJ_NO_TRACK the clustering and the types suffice.  Any other flag bit is
+ * SCVOD_ERR_INVALID.
+ *   d_objects        [cap_objects] scvod_object records, or NULL: no records
+ *   d_obj_offsets    [n_scans + 1] device array: scan s owns the records [d_obj_offsets[s], d_obj_offsets[s + 1]); always the TRUE sizes
+ *   d_member_src     [cap_members] or NULL: per object, in table order, the INPUT index inside its scan (apri_src) of every member
+ *                    point in ascending apri index -- occupy_pts in the form scvod_batch_export_points' d_src_out and a caller's own
+ *                    per-point payload can be joined with.  point_begin is filled whether or not the list is asked for
+ *   d_point_object   [batch points] or NULL: per INPUT point the index of its object in the table, -1 for the points of no object
+ * Nothing is written at or behind cap_objects / cap_members; the offsets and the stats still report the true sizes; the overflow is
+ * latched until the next call. */
+#define SCVOD_OBJ_NO_TRACK 1 /* clustering + types suffice; state -1, dynamic 0 everywhere */
+int scvod_batch_objects(scvod_ctx* ctx, int32_t flags, void* d_objects, int64_t cap_objects, int32_t* d_obj_offsets,
+                        int32_t* d_member_src, int64_t cap_members, int32_t* d_point_object, void* stream);
+/* h_out4 = {objects written, objects found, member slots needed, 1 when the last call outgrew a buffer} of the last
+ * scvod_batch_objects.  Synchronises that call's stream.  SCVOD_ERR_CAPACITY after an overflow, SCVOD_ERR_STATE before the first call. */
+int scvod_batch_objects_stats(scvod_ctx* ctx, int64_t* h_out4);
+/* bytes of device scratch the object table holds on this ctx (0 before the first call) */
+int64_t scvod_batch_objects_scratch_bytes(scvod_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
