@@ -560,7 +560,11 @@ int scvod_nn_search_device(scvod_ctx* ctx, const float* d_map_xyz, int32_t n_map
  * moved to the world by pcl::getTransformation(pose) (ssc.cpp:1455-1458).  Kept as a set of occupied cells of edge `leaf`
  * with ONE representative point per cell chosen by an order-independent rule (smallest packed in-cell offset), so that
  * shards can accumulate independently and merge their record lists (the payload of the RCCL all_gather) into
- * bit-identical maps. */
+ * bit-identical maps.
+ * A point whose cell index leaves [-2^20, 2^20) on any axis, or has a NaN coordinate, is left out and counted: the next
+ * scvod_map_export* call reports SCVOD_ERR_CAPACITY until scvod_map_clear.  The stored intensity is intensity * 256 clamped to
+ * [0, 65535] and truncated; a NaN intensity is not specified (the cell is still recorded, its intensity bits are arbitrary).
+ * scvod_map_points rounds in fp32: beyond about 2^17 cells from the origin the handed-out coordinate may sit on a face of its cell. */
 typedef struct scvod_map scvod_map;
 #define SCVOD_MAP_NO_GROUND 1       /* leave cloud_out (ground) out                                  */
 #define SCVOD_MAP_NO_REJECTED 2     /* leave cloud_eva_static (range/FOV rejects) out                 */
