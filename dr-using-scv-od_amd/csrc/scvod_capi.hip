@@ -181,6 +181,15 @@ struct scvod_ctx {
     int64_t obj_bytes = 0;
     hipStream_t obj_stream = nullptr;  // stream of the last call (scvod_batch_objects_stats waits for it)
     bool obj_ran = false;
+    // eigenvalue descriptor of the table's objects (scvod_batch_object_shapes): it reads the sorted member keys and the run starts the
+    // last table call with lists left in obj_keys / obj_words, so it has to know which clustering they belong to
+    uint64_t cluster_serial = 0;      // counts the clusterings this ctx published
+    uint64_t obj_lists_serial = 0;    // the clustering whose lists the scratch holds; 0: none
+    int obj_lists_track = 0;          // that call read a tracking result (the validity rules of the table apply to the shapes too)
+    FeatureParams feat = {0.333, 740.0, 959.0, 1248.0, 0.278636, 1248.0, 0.956129, 0.99702};
+    long long* shape_stats = nullptr; // [4]
+    hipStream_t shape_stream = nullptr;
+    bool shape_ran = false;
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1438,6 +1447,7 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->obj_keys) hipFree(c->obj_keys);
     if (c->obj_words) hipFree(c->obj_words);
     if (c->obj_sort_tmp) hipFree(c->obj_sort_tmp);
+    if (c->shape_stats) hipFree(c->shape_stats);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
         if (b) hipFree(b);
@@ -1669,6 +1679,7 @@ int scvod_batch_cluster(scvod_ctx* c, void* stream, int32_t sync) {
     if (c->merged) c->A.pt_cluster = c->im.pt_merged;
     HIPCHK(c, hipGetLastError());
     c->clusters_valid = true;
+    ++c->cluster_serial;
     c->types_valid = false;  // scvod_batch_cluster_types publishes them
     c->track_valid = false;
     c->tables_valid = false;
@@ -2596,6 +2607,10 @@ int scvod_batch_objects(scvod_ctx* c, int32_t flags, void* d_objects, int64_t ca
     HIPCHK(c, hipGetLastError());
     c->obj_stream = st;
     c->obj_ran = true;
+    if (lists) {  // (a count-only call leaves the lists of an earlier call as they are)
+        c->obj_lists_serial = c->cluster_serial;
+        c->obj_lists_track = use_track;
+    }
     return SCVOD_OK;
 }
 
@@ -2613,6 +2628,93 @@ int scvod_batch_objects_stats(scvod_ctx* c, int64_t* h_out4) {
 }
 
 int64_t scvod_batch_objects_scratch_bytes(scvod_ctx* c) { return c ? c->obj_bytes : 0; }
+
+// ---- the eigenvalue descriptor of the table's objects (k_obj_shape, scvod_objects.hip) ----
+void scvod_feature_params_default(scvod_feature_params* p) {
+    if (!p) return;
+    p->kOneThird = 0.333;  // feature/k*_ (utility.h:318-325)
+    p->kLinearityMax = 740.0;
+    p->kPlanarityMax = 959.0;
+    p->kScatteringMax = 1248.0;
+    p->kOmnivarianceMax = 0.278636;
+    p->kAnisotropyMax = 1248.0;
+    p->kEigenEntropyMax = 0.956129;
+    p->kChangeOfCurvatureMax = 0.99702;
+}
+
+int scvod_set_object_features(scvod_ctx* c, const scvod_feature_params* p) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!p) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    const double v[8] = {p->kOneThird, p->kLinearityMax, p->kPlanarityMax, p->kScatteringMax, p->kOmnivarianceMax, p->kAnisotropyMax,
+                         p->kEigenEntropyMax, p->kChangeOfCurvatureMax};
+    if (!finite_d(v[0])) return fail(c, SCVOD_ERR_INVALID, "object features: kOneThird is not finite");
+    for (int k = 1; k < 8; ++k)
+        if (!(v[k] > 0.0) || !finite_d(v[k])) return fail(c, SCVOD_ERR_INVALID, "object features: every k*Max must be a positive finite number");
+    c->feat = FeatureParams{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+    return SCVOD_OK;
+}
+
+int scvod_batch_object_shapes(scvod_ctx* c, void* d_shapes, int64_t cap_shapes, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!d_shapes || cap_shapes < 0) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->obj_lists_serial) return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_shapes needs a scvod_batch_objects that asked for records or members");
+    if (int rc = export_check(c, c->obj_lists_track, "scvod_batch_object_shapes")) return rc;
+    if (c->obj_lists_serial != c->cluster_serial)
+        return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_shapes: the last object table belongs to an earlier clustering: call scvod_batch_objects again");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    if (!c->shape_stats) {  // first call of this ctx
+        HIPCHK(c, hipMalloc(&c->shape_stats, sizeof(long long) * 4));
+        c->obj_bytes += (int64_t)(sizeof(long long) * 4);
+    }
+    const size_t N = (size_t)(c->cap_pts > 0 ? c->cap_pts : 1);
+    ShapeJob J;
+    J.tab_stats = c->obj_stats;  // what the table left in the scratch; none of its caller's buffers
+    J.key_out = c->obj_keys + N;
+    J.begin = c->obj_words + 2 * N;
+    J.out = (ObjShape*)d_shapes;
+    J.cap = (long long)cap_shapes;
+    J.stats = c->shape_stats;
+    J.K = c->feat;
+    launch_object_shapes(c->A, J, st);
+    HIPCHK(c, hipGetLastError());
+    c->shape_stream = st;
+    c->shape_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_object_shapes_stats(scvod_ctx* c, int64_t* h_out4) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out4) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->shape_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_batch_object_shapes on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long h[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, c->shape_stats, sizeof(h), hipMemcpyDeviceToHost, c->shape_stream));
+    HIPCHK(c, hipStreamSynchronize(c->shape_stream));
+    for (int k = 0; k < 4; ++k) h_out4[k] = (int64_t)h[k];
+    if (h[3]) return fail(c, SCVOD_ERR_CAPACITY, "the table holds %lld objects, the shape buffer %lld", h[1], h[0]);
+    return SCVOD_OK;
+}
+
+// the 11-value row of getDescriptorByEigenValue (ssc.cpp:686-751) from a record of the table and, optionally, its shape
+void scvod_feature_row(const scvod_object* o, const scvod_object_shape* shape, double* out11) {
+    if (!o || !out11) return;
+    for (int k = 0; k < 6; ++k) out11[k] = shape ? shape->feat[k] : 1.0;
+    out11[6] = (double)o->box_max[2];
+    out11[7] = (double)(o->box_max[0] - o->box_min[0]) * (double)(o->box_max[1] - o->box_min[1]);  // diff_x * diff_y: float differences, double product
+    out11[8] = (double)o->angle_diff;
+    out11[9] = (double)o->box_min[2];
+    out11[10] = (double)o->cls;
+}
+
+// SSC::compareFeature (ssc.cpp:897-911), literally: a float accumulator that takes ten double products
+float scvod_compare_feature(const double* a, const double* b) {
+    if (!a || !b) return u2f(0x7fc00000u);
+    const double w[10] = {0.5, 0.5, 0.2, 0.2, 0.2, 0.2, 0.2, 0.6, 0.2, 0.0};
+    float diff = 0.f;
+    for (int k = 0; k < 10; ++k) diff = (float)((double)diff + fabs_d(a[k] - b[k]) * w[k]);
+    return diff;
+}
 
 // Streaming ingest of a sequence that lives in HOST memory (the reference reads one .bin per scan from disk,
 // SSC::getCloud ssc.cpp:1040-1125): chunks of scans are copied host -> device on a copy stream into one of two buffers

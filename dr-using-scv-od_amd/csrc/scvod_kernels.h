@@ -329,6 +329,18 @@ struct ObjectJob {
 int obj_sort_bits(long long total_pts);
 size_t obj_sort_bytes(long long cap_pts);  // temporary storage of the radix sort of a batch's keys
 hipError_t launch_objects(const Arena& A, const ObjectJob& J, void* sort_tmp, size_t sort_bytes, hipStream_t st);  // (the sort's status)
+// eigenvalue descriptor of the table's objects (scvod_batch_object_shapes): reads key_out, begin and stats[1] of the ObjectJob that
+// built the table -- the ctx's scratch; none of the table call's caller buffers
+struct ShapeJob {
+    const uint64_t* key_out;     // the table's sorted member list
+    const int32_t* begin;        // the table's run starts
+    const long long* tab_stats;  // the table's stats ([1]: its objects)
+    ObjShape* out;     // [cap] caller's
+    long long cap;
+    long long* stats;  // [4] records written, objects of the table, written records with flags bit 0, 1 = the table outgrew cap
+    FeatureParams K;
+};
+void launch_object_shapes(const Arena& A, const ShapeJob& J, hipStream_t st);
 
 typedef void (*TimerHook)(void* user, const char* name, int begin);
 

@@ -986,5 +986,199 @@ SCVOD_HD float calibrated_intensity_f32(float intensity, float max_intensity, co
     return v;
 }
 
+// ---- double log / exp (the eigenvalue features call std::log and std::pow, ssc.cpp:703, 713).  The device's libm and glibc do not
+// agree bit for bit, so Sun fdlibm's e_log.c / e_exp.c are restated operation by operation: IEEE add / mul / div only, the same bits
+// on the host and on the device, each within 1 ulp of the exact value.  How far they are from glibc is measured, not assumed
+// (tests/test_capi_object_shapes.py). -----------------------------------------------------------------------------
+SCVOD_HD double log_f64(double x) {
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, two54 = 1.80143985094819840000e+16,
+                 Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+                 Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+                 Lg7 = 1.479819860511658591e-01;
+    const double zero = 0.0;
+    uint64_t bx = d2u(x);
+    int32_t hx = (int32_t)(bx >> 32);
+    uint32_t lx = (uint32_t)bx;
+    int32_t k = 0;
+    if (hx < 0x00100000) {                                                /* x < 2**-1022 */
+        if ((((uint32_t)hx & 0x7fffffffu) | lx) == 0) return -two54 / zero; /* log(+-0) = -inf */
+        if (hx < 0) return (x - x) / zero;                                /* log(-#) = NaN */
+        k -= 54;
+        x *= two54; /* subnormal number, scale up x */
+        bx = d2u(x);
+        hx = (int32_t)(bx >> 32);
+    }
+    if (hx >= 0x7ff00000) return x + x;
+    k += (hx >> 20) - 1023;
+    hx &= 0x000fffff;
+    int32_t i = (hx + 0x95f64) & 0x100000;
+    x = u2d(((uint64_t)(uint32_t)(hx | (i ^ 0x3ff00000)) << 32) | (uint32_t)bx); /* normalize x or x/2 */
+    k += (i >> 20);
+    const double f = x - 1.0;
+    if ((0x000fffff & (2 + hx)) < 3) { /* |f| < 2**-20 */
+        if (f == zero) {
+            if (k == 0) return zero;
+            const double dk = (double)k;
+            return dk * ln2_hi + dk * ln2_lo;
+        }
+        const double R = f * f * (0.5 - 0.33333333333333333 * f);
+        if (k == 0) return f - R;
+        const double dk = (double)k;
+        return dk * ln2_hi - ((R - dk * ln2_lo) - f);
+    }
+    const double s = f / (2.0 + f);
+    const double dk = (double)k;
+    const double z = s * s;
+    i = hx - 0x6147a;
+    const double w = z * z;
+    const int32_t j = 0x6b851 - hx;
+    const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
+    const double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+    i |= j;
+    const double R = t2 + t1;
+    if (i > 0) {
+        const double hfsq = 0.5 * f * f;
+        if (k == 0) return f - (hfsq - s * (hfsq + R));
+        return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
+    }
+    if (k == 0) return f - s * (f - R);
+    return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
+}
+
+SCVOD_HD double exp_f64(double x) {
+    const double one = 1.0, huge = 1.0e+300, twom1000 = 9.33263618503218878990e-302, o_threshold = 7.09782712893383973096e+02,
+                 u_threshold = -7.45133219101941108420e+02, ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10,
+                 invln2 = 1.44269504088896338700e+00, P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03,
+                 P3 = 6.61375632143793436117e-05, P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
+    const uint64_t bx = d2u(x);
+    uint32_t hx = (uint32_t)(bx >> 32);
+    const int xsb = (int)((hx >> 31) & 1u); /* sign bit of x */
+    hx &= 0x7fffffffu;                      /* high word of |x| */
+    if (hx >= 0x40862E42u) {                /* |x| >= 709.78... */
+        if (hx >= 0x7ff00000u) {
+            if (((hx & 0xfffffu) | (uint32_t)bx) != 0) return x + x; /* NaN */
+            return (xsb == 0) ? x : 0.0;                            /* exp(+-inf) = {inf, 0} */
+        }
+        if (x > o_threshold) return huge * huge;         /* overflow */
+        if (x < u_threshold) return twom1000 * twom1000; /* underflow */
+    }
+    double hi = 0.0, lo = 0.0;
+    int32_t k = 0;
+    if (hx > 0x3fd62e42u) {        /* |x| > 0.5 ln2 */
+        if (hx < 0x3FF0A2B2u) {    /* and |x| < 1.5 ln2 */
+            hi = xsb ? x + ln2HI : x - ln2HI;
+            lo = xsb ? -ln2LO : ln2LO;
+            k = 1 - xsb - xsb;
+        } else {
+            k = (int32_t)(invln2 * x + (xsb ? -0.5 : 0.5));
+            const double t = (double)k;
+            hi = x - t * ln2HI; /* t * ln2HI is exact here */
+            lo = t * ln2LO;
+        }
+        x = hi - lo;
+    } else if (hx < 0x3e300000u) { /* |x| < 2**-28 */
+        if (huge + x > one) return one + x;
+    }
+    const double t = x * x;
+    const double c = x - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+    if (k == 0) return one - ((x * c) / (c - 2.0) - x);
+    const double y = one - ((lo - (x * c) / (2.0 - c)) - hi);
+    if (k >= -1021) return u2d(d2u(y) + ((uint64_t)(int64_t)k << 52)); /* add k to y's exponent */
+    return u2d(d2u(y) + ((uint64_t)(int64_t)(k + 1000) << 52)) * twom1000;
+}
+
+// pow(x, k) of the features: exp_f64(k * log_f64(x)) for x > 0 (not the correctly rounded power: the product's rounding is magnified
+// by its size); the C library's special cases otherwise -- pow(x, 0) = 1 also for a NaN, NaN in NaN out,
+// pow(+-0, k) = 0 for k > 0 and inf for k < 0 (signed for an odd integer k), a negative finite x with a k that is not an integer
+// NaN.  An integer k with a negative x goes through |x| and takes the sign of an odd k.  pow_f64_with takes log_f64(|x|) from the
+// caller, who may have one inlined copy of log_f64 serve several arguments (k_obj_shape: scalar registers).
+SCVOD_HD bool finite_d(double x) { return (d2u(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
+SCVOD_HD double pow_f64_with(double x, double k, double log_abs_x) {
+    if (k == 0.0) return 1.0;
+    if (x != x || k != k) return x + k;
+    if (x == 0.0) {
+        const bool odd = fabs_d(k) < 9007199254740992.0 && (double)(int64_t)k == k && ((int64_t)k & 1) != 0;
+        const double r = k > 0.0 ? 0.0 : 1.0 / 0.0;
+        return (odd && (d2u(x) >> 63)) ? -r : r;  // (an odd integer k keeps the sign of a zero)
+    }
+    bool neg = false;
+    if (x < 0.0 && fabs_d(k) < 9007199254740992.0) {  // (every double of that size and beyond, +-inf included, is an even integer)
+        const double kt = (double)(int64_t)k;
+        if (kt != k) return finite_d(x) ? (x - x) / (x - x) : (k > 0.0 ? 1.0 / 0.0 : 0.0);  // NaN; pow(-inf, k) = +inf or +0
+        neg = ((int64_t)k & 1) != 0;
+    }
+    const double r = exp_f64(k * log_abs_x);
+    return neg ? -r : r;
+}
+SCVOD_HD double pow_f64(double x, double k) { return pow_f64_with(x, k, log_f64(fabs_d(x))); }
+
+// ---- the eigenvalue descriptor of one cluster, SSC::getDescriptorByEigenValue (ssc.cpp:659-721, switched off there) --------------
+struct FeatureParams {  // feature/k*_ (utility.h:246-253, 318-325); the layout of scvod_feature_params
+    double one_third, linearity_max, planarity_max, scattering_max, omnivariance_max, anisotropy_max, eigen_entropy_max,
+        change_of_curvature_max;
+};
+struct ObjShape {  // the layout of scvod_object_shape (96 bytes)
+    float cov[6];
+    float eig[3];
+    int32_t flags;
+    double feat[7];
+};
+// pcl::computeCovarianceMatrix(cloud, centroid, cov) of PCL 1.8 for one point: the six products of p = xyz - centroid that the six
+// chains add (xx, xy, xz through q = p * p.x; yy, yz, zz directly).  Order {xx, xy, xz, yy, yz, zz}.
+SCVOD_HD void shape_products(float x, float y, float z, float cx, float cy, float cz, float pr[6]) {
+    const float px = x - cx, py = y - cy, pz = z - cz;
+    pr[3] = py * py;
+    pr[4] = py * pz;
+    pr[5] = pz * pz;
+    pr[0] = px * px;
+    pr[1] = py * px;
+    pr[2] = pz * px;
+}
+
+// from the six sums to the record: singular values of the symmetric matrix by svd3_jacobi, ascending (swap_if_gt, ssc.cpp:4-10,
+// 676-678), then the features in double, literally as ssc.cpp:680-718 writes them (e1 is the SMALLEST eigenvalue's share; of the
+// entropy only the third term is divided).  Divisions by zero and 0 * -inf stay what IEEE makes of them: flags bit 0.
+SCVOD_HD void shape_finish(const float cov6[6], int n_points, const FeatureParams& K, ObjShape& r) {
+    for (int i = 0; i < 6; ++i) r.cov[i] = cov6[i];
+    const float m[9] = {cov6[0], cov6[1], cov6[2], cov6[1], cov6[3], cov6[4], cov6[2], cov6[4], cov6[5]};
+    Svd3 sv;
+    svd3_jacobi(m, sv);
+    float ev0 = sv.sv[0], ev1 = sv.sv[1], ev2 = sv.sv[2], t;
+    if (ev0 > ev1) { t = ev0; ev0 = ev1; ev1 = t; }
+    if (ev0 > ev2) { t = ev0; ev0 = ev2; ev2 = t; }
+    if (ev1 > ev2) { t = ev1; ev1 = ev2; ev2 = t; }
+    r.eig[0] = ev0;
+    r.eig[1] = ev1;
+    r.eig[2] = ev2;
+    const double sum_eigenvalues = (double)(ev0 + ev1 + ev2);  // (the additions are float's)
+    const double e1 = (double)ev0 / sum_eigenvalues;
+    const double e2 = (double)ev1 / sum_eigenvalues;
+    const double e3 = (double)ev2 / sum_eigenvalues;
+    const double sum_of_eigenvalues = e1 + e2 + e3;
+    const double e123 = e1 * e2 * e3;
+    double l1 = e1, l2 = e2, l3 = e3, l123 = fabs_d(e123);  // -> log_f64 of each, by ONE inlined copy of log_f64
+#if defined(__clang__)
+#pragma clang loop unroll(disable)
+#endif
+    for (int it = 0; it < 4; ++it) {
+        const double l = log_f64(l1);
+        l1 = l2;
+        l2 = l3;
+        l3 = l123;
+        l123 = l;
+    }
+    r.feat[0] = fabs_d((e1 - e2) / e1 / K.linearity_max);
+    r.feat[1] = fabs_d((e2 - e3) / e1 / K.planarity_max);
+    r.feat[2] = fabs_d(e3 / e1 / K.scattering_max);
+    r.feat[3] = fabs_d(pow_f64_with(e123, K.one_third, l123) / K.omnivariance_max);
+    r.feat[4] = fabs_d((e1 - e3) / e1 / K.anisotropy_max);
+    r.feat[5] = fabs_d((e1 * l1) + (e2 * l2) + (e3 * l3) / K.eigen_entropy_max);
+    r.feat[6] = fabs_d(e3 / sum_of_eigenvalues / K.change_of_curvature_max);
+    int fl = n_points < 3 ? 2 : 0;
+    for (int i = 0; i < 7; ++i)
+        if (!finite_d(r.feat[i])) fl |= 1;
+    r.flags = fl;
+}
+
 }  // namespace scvod
 #endif  // SCVOD_MATH_H_

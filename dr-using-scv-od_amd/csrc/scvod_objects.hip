@@ -225,10 +225,10 @@ __global__ __launch_bounds__(256) void k_obj_voxels(Arena A, ObjectJob J) {
 struct ObjPoint {
     float x, y, z;
 };
-__device__ __forceinline__ ObjPoint obj_load(const Arena& A, const ObjectJob& J, int p, int e, int scan_base, int scan_n) {
+__device__ __forceinline__ ObjPoint obj_load(const Arena& A, const uint64_t* key_out, int p, int e, int scan_base, int scan_n) {
     ObjPoint r = {0.f, 0.f, 0.f};
     if (p < e) {
-        const uint32_t g = (uint32_t)J.key_out[p];
+        const uint32_t g = (uint32_t)key_out[p];
         const int src = A.apri_src[g];
         if ((unsigned)src < (unsigned)scan_n) {
             const float4 q = A.pts[(size_t)scan_base + src];
@@ -259,9 +259,9 @@ __global__ __launch_bounds__(256) void k_obj_reduce(Arena A, ObjectJob J, int n_
         const uint32_t g0 = (uint32_t)J.key_out[b];  // the first member is the smallest apri index: the name
         uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
         float sx = 0.f, sy = 0.f, sz = 0.f;
-        ObjPoint cur = obj_load(A, J, b + lane, e, base, scan_n);
+        ObjPoint cur = obj_load(A, J.key_out, b + lane, e, base, scan_n);
         for (int j = b; j < e; j += 64) {
-            const ObjPoint nxt = obj_load(A, J, j + 64 + lane, e, base, scan_n);
+            const ObjPoint nxt = obj_load(A, J.key_out, j + 64 + lane, e, base, scan_n);
             if (j + lane < e) {
                 const uint32_t kx = float_sort_key(cur.x), ky = float_sort_key(cur.y), kz = float_sort_key(cur.z);
                 mn[0] = min(mn[0], kx), mn[1] = min(mn[1], ky), mn[2] = min(mn[2], kz);
@@ -320,7 +320,95 @@ __global__ __launch_bounds__(256) void k_obj_reduce(Arena A, ObjectJob J, int n_
     }
 }
 
+// the eigenvalue descriptor of every object of the table (scvod_batch_object_shapes): one wave per object over the run k_obj_reduce
+// read, gathered and handed round the same way.  Pass 1: the three centroid chains (pcl::compute3DCentroid; the rule of
+// scvod_object::center, recomputed: the caller's table is not read).  Pass 2: every lane forms the six products of ITS member with
+// the centroid, and the six covariance chains -- independent of each other, so they are issued interleaved -- add them in member
+// order.  The sums are the same on every lane; lane 0 runs the 3x3 Jacobi and the double-precision features and writes the record.
+// No LDS, nothing waits for another workgroup; records at or behind J.cap are not computed.
+__global__ __launch_bounds__(256) void k_obj_shape(Arena A, ShapeJob J, int n_scans) {
+    const int lane = threadIdx.x & 63;
+    const long long n_all = J.tab_stats[1];
+    const long long n_obj = n_all < J.cap ? n_all : J.cap;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        J.stats[0] = n_obj;
+        J.stats[1] = n_all;
+        J.stats[3] = n_all > J.cap ? 1 : 0;
+    }
+    // one object per wave and no loop over objects: inside one, the compiler keeps the double constants of log / exp and the Jacobi's
+    // masks live across the two passes and runs out of scalar registers (46 spilled); the grid covers min(cap, batch points) objects
+    const long long o = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (o < n_obj) {
+        const int b = J.begin[o], e = J.begin[o + 1];
+        const int g0 = (int)(uint32_t)J.key_out[b];  // the first member's slot in the batch
+        int lo = 0, hi = n_scans;  // the scan of object o: the last s with scan_off[s] <= g0 (the table's offsets are the caller's, not read)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (A.scan_off[mid] <= g0) lo = mid; else hi = mid;
+        }
+        const int base = A.scan_off[lo];
+        const int scan_n = A.scan_off[lo + 1] - base;
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+        ObjPoint cur = obj_load(A, J.key_out, b + lane, e, base, scan_n);
+        for (int j = b; j < e; j += 64) {
+            const ObjPoint nxt = obj_load(A, J.key_out, j + 64 + lane, e, base, scan_n);
+            if (e - j >= 64) {
+#pragma unroll
+                for (int k = 0; k < 64; ++k) {
+                    sx += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur.x), k));
+                    sy += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur.y), k));
+                    sz += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur.z), k));
+                }
+            } else {
+                for (int k = 0; k < e - j; ++k) {
+                    sx += __shfl(cur.x, k, 64);
+                    sy += __shfl(cur.y, k, 64);
+                    sz += __shfl(cur.z, k, 64);
+                }
+            }
+            cur = nxt;
+        }
+        const float cnt = (float)(e - b);
+        const float cx = sx / cnt, cy = sy / cnt, cz = sz / cnt;
+        float c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        cur = obj_load(A, J.key_out, b + lane, e, base, scan_n);
+        for (int j = b; j < e; j += 64) {
+            const ObjPoint nxt = obj_load(A, J.key_out, j + 64 + lane, e, base, scan_n);
+            float pr[6];
+            shape_products(cur.x, cur.y, cur.z, cx, cy, cz, pr);
+            if (e - j >= 64) {
+                for (int k0 = 0; k0 < 64; k0 += 8) {  // (eight members per trip: 48 values in scalar registers at a time, not 384)
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+#pragma unroll
+                        for (int a = 0; a < 6; ++a) c6[a] += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pr[a]), k0 + k));
+                    }
+                }
+            } else {
+                for (int k = 0; k < e - j; ++k) {
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) c6[a] += __shfl(pr[a], k, 64);
+                }
+            }
+            cur = nxt;
+        }
+        if (lane == 0) {
+            ObjShape r;
+            shape_finish(c6, e - b, J.K, r);
+            J.out[o] = r;
+            if (r.flags & 1) atomicAdd((unsigned long long*)&J.stats[2], 1ull);
+        }
+    }
+}
+
 }  // namespace
+
+void launch_object_shapes(const Arena& A, const ShapeJob& J, hipStream_t st) {
+    hipMemsetAsync(J.stats, 0, sizeof(long long) * 4, st);
+    long long waves = J.cap < A.total_pts ? J.cap : A.total_pts;  // (an object has at least one of the batch's points)
+    if (waves < 1) waves = 1;                                    // (block 0 writes the stats)
+    hipLaunchKernelGGL(k_obj_shape, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, A, J, A.n_scans);
+}
 
 int obj_sort_bits(long long total_pts) {  // bits that hold every object index of the batch AND the masked kObjNone above them
     int bits = 1;

@@ -53,6 +53,20 @@ class Object(C.Structure):
                 ("cls", C.c_int8), ("state", C.c_int8), ("dynamic", C.c_uint8), ("reserved", C.c_uint8), ("point_begin", C.c_int32)]
 
 
+# struct scvod_object_shape (include/scvod.h): the eigenvalue descriptor of one object, 96 bytes
+OBJECT_SHAPE_DTYPE = np.dtype([("cov", "f4", 6), ("eig", "f4", 3), ("flags", "i4"), ("feat", "f8", 7)])
+FEATURE_NAMES = ("linearity", "planarity", "scattering", "omnivariance", "anisotropy", "eigen_entropy", "change_of_curvature")
+
+
+class ObjectShape(C.Structure):
+    _fields_ = [("cov", C.c_float * 6), ("eig", C.c_float * 3), ("flags", C.c_int32), ("feat", C.c_double * 7)]
+
+
+class FeatureParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("kOneThird", "kLinearityMax", "kPlanarityMax", "kScatteringMax", "kOmnivarianceMax",
+                                          "kAnisotropyMax", "kEigenEntropyMax", "kChangeOfCurvatureMax")]
+
+
 class ScanResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_points", "n_ground", "n_nonground", "n_dropped", "n_apri", "n_rejected",
                                           "n_voxels", "n_patches")] + \
@@ -191,6 +205,12 @@ def load_lib():
         "scvod_batch_objects": (C.c_int, [vp, i32, vp, i64, vp, vp, i64, vp, vp]),
         "scvod_batch_objects_stats": (C.c_int, [vp, vp]),
         "scvod_batch_objects_scratch_bytes": (i64, [vp]),
+        "scvod_feature_params_default": (None, [C.POINTER(FeatureParams)]),
+        "scvod_set_object_features": (C.c_int, [vp, C.POINTER(FeatureParams)]),
+        "scvod_batch_object_shapes": (C.c_int, [vp, vp, i64, vp]),
+        "scvod_batch_object_shapes_stats": (C.c_int, [vp, vp]),
+        "scvod_feature_row": (None, [vp, vp, vp]),
+        "scvod_compare_feature": (f32, [vp, vp]),
         "scvod_batch_timings": (C.c_int, [vp, vp, vp, i32]),
         "scvod_set_timing": (C.c_int, [vp, i32]),
         "scvod_nn_search": (C.c_int, [vp, vp, i32, vp, i32, f32, vp, vp, vp]),
@@ -217,7 +237,36 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
                     "scvod_batch_point_labels", "scvod_batch_export_points", "scvod_batch_export_stats",
                     "scvod_batch_objects", "scvod_batch_objects_stats", "scvod_batch_objects_scratch_bytes",
+                    "scvod_feature_params_default", "scvod_set_object_features", "scvod_batch_object_shapes", "scvod_batch_object_shapes_stats",
+                    "scvod_feature_row", "scvod_compare_feature",
                     "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid"]
+
+
+def feature_params(**kw):
+    """scvod_feature_params with the reference's defaults (utility.h:318-325), fields overridden by keyword"""
+    p = FeatureParams()
+    load_lib().scvod_feature_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, float(v))
+    return p
+
+
+def feature_row(obj, shape=None):
+    """the 11-value row of getDescriptorByEigenValue from one OBJECT_DTYPE record and, optionally, its OBJECT_SHAPE_DTYPE record
+    (None: the six constants 1.0).  Host only"""
+    o = np.ascontiguousarray(obj, OBJECT_DTYPE).reshape(1)
+    sh = np.ascontiguousarray(shape, OBJECT_SHAPE_DTYPE).reshape(1) if shape is not None else None
+    out = np.zeros(11, np.float64)
+    load_lib().scvod_feature_row(o.ctypes.data_as(C.c_void_p), sh.ctypes.data_as(C.c_void_p) if sh is not None else None,
+                                 out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def compare_feature(a, b):
+    """SSC::compareFeature of two 11-value rows (a float).  Host only"""
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    assert a.size >= 10 and b.size >= 10
+    return float(load_lib().scvod_compare_feature(a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
 
 
 def make_params(preset=None, **kw):
@@ -698,6 +747,26 @@ class Ctx:
     def batch_objects_scratch_bytes(self):
         """device scratch of the object table on this ctx (not part of arena_bytes)"""
         return int(self.lib.scvod_batch_objects_scratch_bytes(self.h))
+
+    # ---- the eigenvalue descriptor of the table's objects (include/scvod.h: scvod_batch_object_shapes) ----
+    def set_object_features(self, params=None, **kw):
+        """the constants of the features: a FeatureParams, or the defaults with fields overridden by keyword"""
+        p = params if params is not None else feature_params(**kw)
+        self._chk(self.lib.scvod_set_object_features(self.h, C.byref(p)))
+
+    def batch_object_shapes(self, d_shapes, stream=None):
+        """one OBJECT_SHAPE_DTYPE record per object of the last batch_objects that asked for more than the counts, in table order,
+        into d_shapes (a contiguous torch device tensor of 96-byte rows, e.g. uint8 [cap, 96]).  Asynchronous on `stream`"""
+        nbytes = d_shapes.numel() * d_shapes.element_size()
+        assert d_shapes.is_contiguous() and nbytes % OBJECT_SHAPE_DTYPE.itemsize == 0
+        self._chk(self.lib.scvod_batch_object_shapes(self.h, C.c_void_p(d_shapes.data_ptr()), nbytes // OBJECT_SHAPE_DTYPE.itemsize,
+                                                     C.c_void_p(stream or 0)))
+
+    def batch_object_shapes_stats(self):
+        """{written, objects, not_finite, overflow} of the last batch_object_shapes; synchronises its stream; raises after an overflow"""
+        out = np.zeros(4, np.int64)
+        self._chk(self.lib.scvod_batch_object_shapes_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(written=int(out[0]), objects=int(out[1]), not_finite=int(out[2]), overflow=bool(out[3]))
 
     def set_timing(self, on):
         self._chk(self.lib.scvod_set_timing(self.h, int(bool(on))))

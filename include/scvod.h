@@ -686,7 +686,7 @@ typedef struct scvod_object {
 } scvod_object;
 /* The remaining columns of the reference's 11-value feature row follow from the record and are not stored: point_max.z = box_max[2];
  * square = (double)(box_max[0] - box_min[0]) * (double)(box_max[1] - box_min[1]) (the library's cc_box_square); point_min.z =
- * box_min[2]; the six constants 1.0; type = cls.
+ * box_min[2]; the six constants 1.0 (or the six values scvod_batch_object_shapes computes); type = cls: scvod_feature_row.
  *
  * scvod_batch_objects is stream-ordered (stream NULL = the stream of the ctx's last batch call), never synchronises with the host,
  * launches and allocates nothing unless it is called, reads the arena and writes only the caller's buffers and scratch of its own
@@ -711,6 +711,52 @@ int scvod_batch_objects(scvod_ctx* ctx, int32_t flags, void* d_objects, int64_t 
 int scvod_batch_objects_stats(scvod_ctx* ctx, int64_t* h_out4);
 /* bytes of device scratch the object table holds on this ctx (0 before the first call) */
 int64_t scvod_batch_objects_scratch_bytes(scvod_ctx* ctx);
+
+/* ---- the eigenvalue descriptor of the table's objects, on the device (opt-in: nothing runs unless it is called) -------------------
+ * Reference analogue: the part of SSC::getDescriptorByEigenValue that the reference holds as text and leaves switched off
+ * (src/ssc.cpp:659-721, constants include/utility.h:246-253, 318-325, YAML keys feature/k*_), and SSC::compareFeature
+ * (ssc.cpp:897-911).  Per object of the table, from its member points in ascending apri index:
+ *   centroid     pcl::compute3DCentroid: the rule of scvod_object::center, recomputed (the caller's table is not read)
+ *   cov          pcl::computeCovarianceMatrix(cloud, centroid, cov) of PCL 1.8, NOT normalised: six sequential fp32 chains
+ *   eig          the singular values of that symmetric matrix by Eigen's JacobiSVD (the Patchwork specification), ascending.  The
+ *                reference asks Eigen::EigenSolver; this convention is parity-unpinned
+ *   feat         in double, literally as written at ssc.cpp:680-718 with e_i = eig[i] / (double)(eig[0] + eig[1] + eig[2]); log and pow
+ *                are fdlibm's log / exp restated (scvod_math.h), the same bits on the host and on the device
+ * Divisions by zero and 0 * -inf stay what IEEE makes of them; such objects are flagged and counted, not repaired.  96 bytes: */
+typedef struct scvod_object_shape {
+    float cov[6];    /* xx, xy, xz, yy, yz, zz                                                                                   */
+    float eig[3];    /* ascending: eig[0] is the smallest                                                                        */
+    int32_t flags;   /* bit 0: some feature is not finite; bit 1: n_points < 3                                                   */
+    double feat[7];  /* linearity, planarity, scattering, omnivariance, anisotropy, eigen_entropy, change_of_curvature          */
+} scvod_object_shape;
+typedef struct scvod_feature_params {
+    double kOneThird, kLinearityMax, kPlanarityMax, kScatteringMax, kOmnivarianceMax, kAnisotropyMax, kEigenEntropyMax,
+        kChangeOfCurvatureMax;
+} scvod_feature_params;
+/* the nh.param<> defaults of utility.h:318-325: 0.333, 740, 959, 1248, 0.278636, 1248, 0.956129, 0.99702 */
+void scvod_feature_params_default(scvod_feature_params* p);
+/* the constants the next shape calls of this ctx use (a new ctx holds the defaults).  Checked before any device is looked for:
+ * SCVOD_ERR_INVALID for a NULL argument, a kOneThird that is not finite and a k*Max that is not a positive finite number. */
+int scvod_set_object_features(scvod_ctx* ctx, const scvod_feature_params* p);
+/* One scvod_object_shape per object of the LAST scvod_batch_objects call of this batch that asked for records, members or the
+ * per-point objects (it left the sorted member list in the table's scratch), in table order, into d_shapes [cap_shapes].
+ * Stream-ordered (stream NULL = the stream of the ctx's last batch call; the table call must be ordered before it), never
+ * synchronises, reads the arena and the table's scratch and writes d_shapes and four stats words of its own (allocated by the first
+ * call and counted by scvod_batch_objects_scratch_bytes: + 32 bytes; scvod_arena_bytes does not change).  SCVOD_ERR_STATE when no such
+ * table call was made (a count-only call is none) or when the clustering changed since; otherwise the state the table call needed is
+ * needed again, with its flags: SCVOD_ERR_STATE without clustering and types of the batch, SCVOD_ERR_INVALID when the table read a
+ * tracking result that is stale now.  Nothing is written at or behind cap_shapes; the overflow is latched until the next call. */
+int scvod_batch_object_shapes(scvod_ctx* ctx, void* d_shapes, int64_t cap_shapes, void* stream);
+/* h_out4 = {records written, objects of the table, written records with flags bit 0, 1 when the table outgrew cap_shapes} of the
+ * last scvod_batch_object_shapes.  Synchronises that call's stream.  SCVOD_ERR_CAPACITY after an overflow, SCVOD_ERR_STATE before
+ * the first call. */
+int scvod_batch_object_shapes_stats(scvod_ctx* ctx, int64_t* h_out4);
+/* Host only, no device.  The 11-value row of ssc.cpp:686-751: columns 0-5 = feat[0..5] (the six constants 1.0 when shape is NULL:
+ * the row the reference builds today), 6 = box_max[2], 7 = cc_box_square, 8 = angle_diff, 9 = box_min[2], 10 = cls. */
+void scvod_feature_row(const scvod_object* object, const scvod_object_shape* shape, double* out11);
+/* Host only.  SSC::compareFeature literally: float diff = 0; diff += |a[i] - b[i]| * w[i] with the double weights 0.5, 0.5, 0.2,
+ * 0.2, 0.2, 0.2, 0.2, 0.6, 0.2, 0.0 of ssc.cpp:900-909 (column 10 is not read). */
+float scvod_compare_feature(const double* a, const double* b);
 
 #ifdef __cplusplus
 }
