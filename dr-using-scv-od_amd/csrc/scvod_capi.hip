@@ -190,6 +190,14 @@ struct scvod_ctx {
     long long* shape_stats = nullptr; // [4]
     hipStream_t shape_stream = nullptr;
     bool shape_ran = false;
+    // evaluation against labelled truth (scvod_evaluate_device / scvod_batch_evaluate / scvod_classify_map_device, scvod_eval.hip): one
+    // grow-only scratch block and 16 counter words of their own (a grown block must not take an unread result with it); not part of the arena
+    void* ev_buf = nullptr;
+    size_t ev_cap = 0;
+    unsigned long long* ev_counters = nullptr;  // [8] evaluation, [8] map classes
+    hipStream_t ev_stream = nullptr;   // stream of the last evaluation (scvod_evaluate_stats waits for it; a growing block too)
+    hipStream_t ev_cls_stream = nullptr;
+    bool ev_ran = false, ev_cls_ran = false;
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1448,6 +1456,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->obj_words) hipFree(c->obj_words);
     if (c->obj_sort_tmp) hipFree(c->obj_sort_tmp);
     if (c->shape_stats) hipFree(c->shape_stats);
+    if (c->ev_buf) hipFree(c->ev_buf);
+    if (c->ev_counters) hipFree(c->ev_counters);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
         if (b) hipFree(b);
@@ -2923,6 +2933,197 @@ int scvod_nn_search_device(scvod_ctx* c, const float* d_map_xyz, int32_t n_map, 
     const float origin[3] = {0.f, 0.f, 0.f};
     return nn_run(c, d_map_xyz, n_map, d_query_xyz, n_query, radius, d_nn_idx, d_nn_sqdist, d_within, origin, 0,
                   stream ? (hipStream_t)stream : c->stream);
+}
+
+// ---- evaluation against labelled truth, on the device (scvod_eval.hip) ----
+void scvod_eval_params_default(scvod_eval_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->voxelsize = 0.2;
+    p->n_dynamic_classes = 8;
+    for (int k = 0; k < 8; ++k) p->dynamic_classes[k] = (uint16_t)(252 + k);  // analysis.py:6
+}
+
+void scvod_eval_finish(const int64_t counts[7], scvod_eval_result* out) {
+    if (!counts || !out) return;
+    out->num_gt_static = counts[0];
+    out->num_gt_dynamic = counts[1];
+    out->num_est_static = counts[2];
+    out->num_est_dynamic = counts[3];
+    out->num_preserved = counts[4];
+    out->num_static_preserved = counts[5];
+    out->num_dynamic_preserved = counts[6];
+    const double nan = std::nan("");
+    // analysis.py:186-190 / metric.py:28-30, operation by operation (the library is built without contraction)
+    const double pr = counts[0] ? 100.0 * (double)counts[5] / (double)counts[0] : nan;
+    const double rr = counts[1] ? 100.0 * (double)(counts[1] - counts[6]) / (double)counts[1] : nan;
+    double f1 = nan;  // (a rate without a denominator: analysis.py would raise)
+    if (counts[0] && counts[1]) f1 = pr + rr > 0 ? 2.0 * (pr / 100.0) * (rr / 100.0) / ((pr / 100.0) + (rr / 100.0)) : 0.0;
+    out->PR = pr;
+    out->RR = rr;
+    out->F1 = f1;
+}
+
+// the parameters of a call (NULL: the defaults) as the kernels take them; argument errors only
+static int ev_params(scvod_ctx* c, const scvod_eval_params* params, EvClasses* K, double* voxelsize) {
+    scvod_eval_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_eval_params_default(&p);
+    if (p.n_dynamic_classes < 0 || p.n_dynamic_classes > 16) return fail(c, SCVOD_ERR_INVALID, "%d dynamic classes (0..16)", p.n_dynamic_classes);
+    if (!(p.voxelsize > 0.0) || !std::isfinite(p.voxelsize)) return fail(c, SCVOD_ERR_INVALID, "voxelsize must be positive and finite");
+    memset(K, 0, sizeof(*K));
+    K->n = p.n_dynamic_classes;
+    for (int k = 0; k < K->n; ++k) K->c[k] = p.dynamic_classes[k];
+    *voxelsize = p.voxelsize;
+    return SCVOD_OK;
+}
+
+// the evaluation's scratch block of at least `bytes` (grow-only; growing waits for the evaluations in flight, which read the old one)
+static int ev_reserve(scvod_ctx* c, size_t bytes) {
+    if (!c->ev_counters) {
+        HIPCHK(c, hipMalloc(&c->ev_counters, sizeof(unsigned long long) * 16));
+        HIPCHK(c, hipMemset(c->ev_counters, 0, sizeof(unsigned long long) * 16));
+    }
+    if (bytes > c->ev_cap) {
+        if (c->ev_buf) {
+            if (c->ev_ran) HIPCHK(c, hipStreamSynchronize(c->ev_stream));
+            if (c->ev_cls_ran) HIPCHK(c, hipStreamSynchronize(c->ev_cls_stream));
+            hipFree(c->ev_buf);
+            c->ev_buf = nullptr;
+            c->ev_cap = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->ev_buf, bytes + bytes / 4));
+        c->ev_cap = bytes + bytes / 4;
+    }
+    return SCVOD_OK;
+}
+
+static float ev_cell(double radius) {  // nn_run's rule
+    const float r = (float)radius;
+    return r > 0.2f ? r : 0.2f;
+}
+
+int scvod_evaluate_device(scvod_ctx* c, const float* d_gt_xyz, const uint32_t* d_gt_label, int32_t n_gt, const float* d_est_xyz,
+                          const uint32_t* d_est_label, int32_t n_est, const scvod_eval_params* params, uint8_t* d_point_result, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_gt < 0 || n_est < 0 || (n_gt > 0 && (!d_gt_xyz || !d_gt_label)) || (n_est > 0 && (!d_est_xyz || !d_est_label)))
+        return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    EvClasses K;
+    double vs;
+    if (int rc = ev_params(c, params, &K, &vs)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const int32_t buckets = ev_buckets(n_est);
+    if (int rc = ev_reserve(c, sizeof(int) * ev_grid_ints(buckets, n_est))) return rc;
+    launch_eval(d_gt_xyz, d_gt_label, n_gt, d_est_xyz, d_est_label, nullptr, n_est, vs * std::sqrt(3.0) / 2, K, ev_cell(vs), buckets,
+                (int*)c->ev_buf, c->ev_counters, d_point_result, st);
+    HIPCHK(c, hipGetLastError());
+    c->ev_stream = st;
+    c->ev_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_evaluate(scvod_ctx* c, const uint32_t* d_gt_label, const float* h_poses, int32_t flags, const scvod_eval_params* params,
+                         uint8_t* d_point_result, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!d_gt_label || !h_poses) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (flags & ~(SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED | SCVOD_MAP_IGNORE_DYNAMIC))
+        return fail(c, SCVOD_ERR_INVALID, "scvod_batch_evaluate takes SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED and SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", flags);
+    EvClasses K;
+    double vs;
+    if (int rc = ev_params(c, params, &K, &vs)) return rc;
+    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
+    if (int rc = export_check(c, use_dyn, "scvod_batch_evaluate")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    const int B = c->A.n_scans;
+    const int32_t N = (int32_t)c->A.total_pts;
+    const int32_t buckets = ev_buckets(N);
+    // world xyz | keep byte | label byte | pose matrices | grid
+    const size_t n1 = (size_t)(N > 0 ? N : 1);
+    const size_t off_keep = align_up(12 * n1, 256), off_lab = off_keep + align_up(n1, 256), off_pose = off_lab + align_up(n1, 256),
+                 off_grid = off_pose + align_up(sizeof(float) * 12 * (size_t)(B > 0 ? B : 1), 256);
+    if (int rc = ev_reserve(c, off_grid + sizeof(int) * ev_grid_ints(buckets, N))) return rc;
+    unsigned char* base = (unsigned char*)c->ev_buf;
+    float* world = (float*)base;
+    uint8_t* keep = base + off_keep;
+    uint8_t* lab = base + off_lab;
+    float* pose = (float*)(base + off_pose);
+    if (B > 0) {  // pcl::getTransformation per scan, staged before the call returns: h_poses is the caller's again at once
+        std::vector<float> T((size_t)12 * B);
+        for (int s = 0; s < B; ++s) scvod_pose_matrix(h_poses + 6 * s, T.data() + 12 * s);
+        if (int rc = staged_upload(c, T.data(), sizeof(float) * T.size(), pose, st)) return rc;
+    }
+    uint32_t keep_mask = (1u << SCVOD_PT_UNCLUSTERED) | (1u << SCVOD_PT_STATIC_OTHER) | (1u << SCVOD_PT_STATIC_CAR);  // scvod_batch_export_points' rule
+    if (!(flags & SCVOD_MAP_NO_GROUND)) keep_mask |= 1u << SCVOD_PT_GROUND;
+    if (!(flags & SCVOD_MAP_NO_REJECTED)) keep_mask |= 1u << SCVOD_PT_REJECTED;
+    if (!use_dyn) keep_mask |= 1u << SCVOD_PT_DYNAMIC;
+    if (N > 0) {
+        HIPCHK(c, hipMemsetAsync(lab, SCVOD_PT_DROPPED, (size_t)N, st));
+        launch_point_labels(c->A, lab, use_dyn, st);
+        launch_eval_world(c->A, lab, keep_mask, pose, world, keep, st);
+    }
+    launch_eval(world, d_gt_label, N, world, d_gt_label, keep, N, vs * std::sqrt(3.0) / 2, K, ev_cell(vs), buckets, (int*)(base + off_grid),
+                c->ev_counters, d_point_result, st);
+    HIPCHK(c, hipGetLastError());
+    c->ev_stream = st;
+    c->ev_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_evaluate_stats(scvod_ctx* c, scvod_eval_result* out) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!out) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->ev_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_evaluate_device or scvod_batch_evaluate on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, c->ev_counters, sizeof(h), hipMemcpyDeviceToHost, c->ev_stream));
+    HIPCHK(c, hipStreamSynchronize(c->ev_stream));
+    int64_t counts[7];
+    for (int k = 0; k < 7; ++k) counts[k] = (int64_t)h[k];
+    scvod_eval_finish(counts, out);
+    return SCVOD_OK;
+}
+
+int64_t scvod_evaluate_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->ev_cap + (c->ev_counters ? (int64_t)sizeof(unsigned long long) * 16 : 0) : 0;
+}
+
+int scvod_classify_map_device(scvod_ctx* c, const float* d_orig_xyz, const uint8_t* d_pred_static, int32_t n, const float* d_static_xyz,
+                              int32_t n_static, const float* d_dynamic_xyz, int32_t n_dynamic, float r15, float r10, uint8_t* d_class, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n < 0 || n_static < 0 || n_dynamic < 0 || (n > 0 && (!d_orig_xyz || !d_pred_static)) || (n_static > 0 && !d_static_xyz) ||
+        (n_dynamic > 0 && !d_dynamic_xyz))
+        return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    const float cell = 0.2f;
+    if (!(r15 > 0.f) || !(r10 > 0.f) || r15 > 0.99f * cell || r10 > 0.99f * cell)
+        return fail(c, SCVOD_ERR_INVALID, "radii %g / %g: positive and at most 0.99 cell edges of 0.2", (double)r15, (double)r10);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const int32_t bs = ev_buckets(n_static), bd = ev_buckets(n_dynamic);
+    const size_t off_d = align_up(sizeof(int) * ev_grid_ints(bs, n_static), 256);
+    if (int rc = ev_reserve(c, off_d + sizeof(int) * ev_grid_ints(bd, n_dynamic))) return rc;
+    unsigned char* base = (unsigned char*)c->ev_buf;
+    launch_classify(d_orig_xyz, d_pred_static, n, d_static_xyz, n_static, d_dynamic_xyz, n_dynamic, r15, r10, cell, bs, (int*)base, bd,
+                    (int*)(base + off_d), c->ev_counters + 8, d_class, st);
+    HIPCHK(c, hipGetLastError());
+    c->ev_cls_stream = st;
+    c->ev_cls_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_classify_map_stats(scvod_ctx* c, int64_t* h_out5) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out5) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->ev_cls_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_classify_map_device on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, c->ev_counters + 8, sizeof(h), hipMemcpyDeviceToHost, c->ev_cls_stream));
+    HIPCHK(c, hipStreamSynchronize(c->ev_cls_stream));
+    for (int k = 0; k < 5; ++k) h_out5[k] = (int64_t)h[k];
+    return SCVOD_OK;
 }
 
 }  // extern "C"

@@ -382,6 +382,30 @@ void launch_export_table(const Arena& A, int s, int4* out, long long cap_records
 void launch_nn(const float* map_xyz, int32_t n_map, const float* q_xyz, int32_t n_q, float radius, int32_t* nn_idx,
                float* nn_sq, uint8_t* within, const float origin[3], float cell, int32_t buckets, int* work, int bounded,
                hipStream_t st);
+// exclusive scan of `n` ints on `st` (the three k_scan_* launches of the grid search): out[i] = in[0] + .. + in[i - 1], *grand_total = the sum;
+// block_tot: (n + 1023) / 1024 ints of scratch.  For the units that build a CSR grid of their own (scvod_eval.hip)
+void launch_scan_ints(const int* in, int* out, int* block_tot, int* grand_total, int n, hipStream_t st);
+
+// evaluation against labelled truth (scvod_evaluate_device / scvod_batch_evaluate / scvod_classify_map_device; scvod_eval.hip).  A grid is
+// the CSR hash grid of launch_nn over the estimate cloud, in `work` (ev_grid_ints ints); counters: 8 words, cleared by every launch
+struct EvClasses {  // the semantic classes (label & 0xFFFF) that count as dynamic
+    int32_t n;
+    uint16_t c[16];
+};
+int32_t ev_buckets(int32_t n_map);
+size_t ev_grid_ints(int32_t buckets, int32_t n_map);
+// counters: gt static, gt dynamic, est static, est dynamic, preserved, static preserved, dynamic preserved, 0.  est_keep: nullptr or one
+// byte per estimate point (0: not part of the estimate).  point_result: nullptr or one byte per gt point
+void launch_eval(const float* gt_xyz, const uint32_t* gt_label, int32_t n_gt, const float* est_xyz, const uint32_t* est_label,
+                 const uint8_t* est_keep, int32_t n_est, double limit, const EvClasses& K, float cell, int32_t buckets, int* work,
+                 unsigned long long* counters, uint8_t* point_result, hipStream_t st);
+// per input point of the arena's batch: packed world xyz (pose: [B][12] device) and keep = bit labels[p] of keep_mask
+void launch_eval_world(const Arena& A, const uint8_t* labels, uint32_t keep_mask, const float* pose, float* world_xyz, uint8_t* keep,
+                       hipStream_t st);
+// counters: points of class 0 (unmatched), 1 .. 4 (metric.py's TP_STATIC .. FN_DYNAMIC), 0, 0, 0.  cls: nullptr or one byte per point
+void launch_classify(const float* orig_xyz, const uint8_t* pred_static, int32_t n, const float* static_xyz, int32_t n_static,
+                     const float* dynamic_xyz, int32_t n_dynamic, float r15, float r10, float cell, int32_t buckets_s, int* work_s,
+                     int32_t buckets_d, int* work_d, unsigned long long* counters, uint8_t* cls, hipStream_t st);
 
 }  // namespace scvod
 #endif

@@ -764,6 +764,13 @@ void launch_nn(const float* map_xyz, int32_t n_map, const float* q_xyz, int32_t 
                        radius * radius, nn_idx, nn_sq, within);
 }
 
+void launch_scan_ints(const int* in, int* out, int* block_tot, int* grand_total, int n, hipStream_t st) {
+    const int nb = (n + 1023) / 1024;
+    hipLaunchKernelGGL(k_scan_blocks, dim3(nb), dim3(1024), 0, st, in, out, block_tot, n);
+    hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, st, block_tot, nb, grand_total);
+    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, st, out, block_tot, n);
+}
+
 }  // namespace scvod
 
 #ifdef SCVOD_PROFILE

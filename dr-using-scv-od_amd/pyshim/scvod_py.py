@@ -67,6 +67,25 @@ class FeatureParams(C.Structure):
                                           "kAnisotropyMax", "kEigenEntropyMax", "kChangeOfCurvatureMax")]
 
 
+class EvalParams(C.Structure):
+    """struct scvod_eval_params (include/scvod.h)"""
+    _fields_ = [("voxelsize", C.c_double), ("n_dynamic_classes", C.c_int32), ("dynamic_classes", C.c_uint16 * 16)]
+
+
+EVAL_COUNTS = ("num_gt_static", "num_gt_dynamic", "num_est_static", "num_est_dynamic", "num_preserved", "num_static_preserved",
+               "num_dynamic_preserved")
+
+
+class EvalResult(C.Structure):
+    """struct scvod_eval_result (include/scvod.h): the seven counts of metric.preservation_rejection, then PR, RR, F1"""
+    _fields_ = [(n, C.c_int64) for n in EVAL_COUNTS] + [(n, C.c_double) for n in ("PR", "RR", "F1")]
+
+
+EVAL_RESULT = EvalResult
+# scvod_evaluate_device's per-point byte; scvod_classify_map_device's classes are metric.py's TP_STATIC .. UNMATCHED
+EVAL_INLIER, EVAL_GT_DYNAMIC, EVAL_EST_DYNAMIC = 1, 2, 4
+
+
 class ScanResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_points", "n_ground", "n_nonground", "n_dropped", "n_apri", "n_rejected",
                                           "n_voxels", "n_patches")] + \
@@ -216,6 +235,14 @@ def load_lib():
         "scvod_nn_search": (C.c_int, [vp, vp, i32, vp, i32, f32, vp, vp, vp]),
         "scvod_nn_radius_search": (C.c_int, [vp, vp, i32, vp, i32, f32, vp, vp]),
         "scvod_nn_search_device": (C.c_int, [vp, vp, i32, vp, i32, f32, vp, vp, vp, vp]),
+        "scvod_eval_params_default": (None, [C.POINTER(EvalParams)]),
+        "scvod_eval_finish": (None, [vp, C.POINTER(EvalResult)]),
+        "scvod_evaluate_device": (C.c_int, [vp, vp, vp, i32, vp, vp, i32, C.POINTER(EvalParams), vp, vp]),
+        "scvod_batch_evaluate": (C.c_int, [vp, vp, vp, i32, C.POINTER(EvalParams), vp, vp]),
+        "scvod_evaluate_stats": (C.c_int, [vp, C.POINTER(EvalResult)]),
+        "scvod_evaluate_scratch_bytes": (i64, [vp]),
+        "scvod_classify_map_device": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, i32, f32, f32, vp, vp]),
+        "scvod_classify_map_stats": (C.c_int, [vp, vp]),
         "scvod_batch_voxelgrid": (C.c_int, [vp, vp, vp, vp, i32, vp, f32, vp, i64, vp, vp]),
         "scvod_voxelgrid": (C.c_int, [vp, vp, vp, i32, vp, f32, vp, i32, vp]),
     }
@@ -239,7 +266,36 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_batch_objects", "scvod_batch_objects_stats", "scvod_batch_objects_scratch_bytes",
                     "scvod_feature_params_default", "scvod_set_object_features", "scvod_batch_object_shapes", "scvod_batch_object_shapes_stats",
                     "scvod_feature_row", "scvod_compare_feature",
-                    "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid"]
+                    "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid",
+                    "scvod_eval_params_default", "scvod_eval_finish", "scvod_evaluate_device", "scvod_batch_evaluate", "scvod_evaluate_stats",
+                    "scvod_evaluate_scratch_bytes", "scvod_classify_map_device", "scvod_classify_map_stats"]
+
+
+def eval_params_default(voxelsize=None, dynamic_classes=None):
+    """scvod_eval_params with the reference's defaults (voxelsize 0.2, the classes 252..259), overridden by keyword"""
+    p = EvalParams()
+    load_lib().scvod_eval_params_default(C.byref(p))
+    if voxelsize is not None:
+        p.voxelsize = float(voxelsize)
+    if dynamic_classes is not None:
+        cl = [int(v) for v in dynamic_classes]
+        p.n_dynamic_classes = len(cl)  # (more than 16: the library refuses the call)
+        for k, v in enumerate(cl[:16]):
+            p.dynamic_classes[k] = v
+    return p
+
+
+def _eval_dict(r):
+    return {k: getattr(r, k) for k, _ in EvalResult._fields_}
+
+
+def eval_finish(counts):
+    """the seven counts of metric.preservation_rejection (in EVAL_RESULT's order) -> the dict with PR / RR / F1.  Host only"""
+    cnt = np.ascontiguousarray(counts, np.int64)
+    assert cnt.size == 7
+    r = EvalResult()
+    load_lib().scvod_eval_finish(cnt.ctypes.data_as(C.c_void_p), C.byref(r))
+    return _eval_dict(r)
 
 
 def feature_params(**kw):
@@ -796,6 +852,64 @@ class Ctx:
                                                   C.c_void_p(sq.data_ptr()), C.c_void_p(w.data_ptr()),
                                                   C.c_void_p(stream) if stream else None))
         return idx[:nq], sq[:nq], w[:nq]
+
+    # ---- evaluation against labelled truth on the device (include/scvod.h: scvod_evaluate_device ...) ----
+    @staticmethod
+    def _xyz(t):
+        assert t.is_contiguous() and t.numel() % 3 == 0 and t.element_size() == 4
+        return (C.c_void_p(t.data_ptr()) if t.numel() else None), t.numel() // 3
+
+    def evaluate_device(self, d_gt_xyz, d_gt_label, d_est_xyz, d_est_label, params=None, d_point_result=None, stream=None):
+        """ground truth against an estimate, both on the device: contiguous torch float32 [n, 3] clouds, labels as 4-byte words (int32
+        tensors holding the uint32 bits do).  d_point_result: torch uint8 [n_gt] or None.  Asynchronous on `stream`: evaluate_stats()"""
+        pg, n_gt = self._xyz(d_gt_xyz)
+        pe, n_est = self._xyz(d_est_xyz)
+        assert d_gt_label.numel() >= n_gt and d_est_label.numel() >= n_est and d_gt_label.element_size() == 4 == d_est_label.element_size()
+        assert d_point_result is None or d_point_result.numel() >= n_gt
+        self._chk(self.lib.scvod_evaluate_device(self.h, pg, C.c_void_p(d_gt_label.data_ptr()) if n_gt else None, n_gt, pe,
+                                                 C.c_void_p(d_est_label.data_ptr()) if n_est else None, n_est,
+                                                 C.byref(params) if params is not None else None,
+                                                 C.c_void_p(d_point_result.data_ptr()) if d_point_result is not None else None,
+                                                 C.c_void_p(stream or 0)))
+
+    def batch_evaluate(self, d_gt_label, poses, flags=0, params=None, d_point_result=None, stream=None):
+        """the ERASOR protocol of quality.compare for the last batch: every input point in the world frame (poses [n_scans, 6], copied
+        before the call returns) with its label (4-byte words per input point) against the points batch_export_points would keep with
+        the same flags.  Asynchronous on `stream`: evaluate_stats()"""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p.shape[0] == self._n_scans and d_gt_label.numel() >= self._n_pts and d_gt_label.element_size() == 4
+        assert d_point_result is None or d_point_result.numel() >= self._n_pts
+        self._chk(self.lib.scvod_batch_evaluate(self.h, C.c_void_p(d_gt_label.data_ptr()), p.ctypes.data_as(C.c_void_p), int(flags),
+                                                C.byref(params) if params is not None else None,
+                                                C.c_void_p(d_point_result.data_ptr()) if d_point_result is not None else None,
+                                                C.c_void_p(stream or 0)))
+
+    def evaluate_stats(self):
+        """the dict of metric.preservation_rejection for the last evaluate_device / batch_evaluate; synchronises its stream"""
+        r = EvalResult()
+        self._chk(self.lib.scvod_evaluate_stats(self.h, C.byref(r)))
+        return _eval_dict(r)
+
+    def evaluate_scratch_bytes(self):
+        """device scratch of the evaluation on this ctx (not part of arena_bytes)"""
+        return int(self.lib.scvod_evaluate_scratch_bytes(self.h))
+
+    def classify_map_device(self, d_orig_xyz, d_pred_static, d_static_xyz, d_dynamic_xyz, r15=0.15, r10=0.1, d_class=None, stream=None):
+        """metric.classify_map_points on the device: contiguous torch float32 [n, 3] clouds, d_pred_static one byte per point of the
+        original map (uint8 or bool), d_class torch uint8 [n] or None (counts only).  Asynchronous on `stream`: classify_map_stats()"""
+        po, n = self._xyz(d_orig_xyz)
+        ps, n_s = self._xyz(d_static_xyz)
+        pd, n_d = self._xyz(d_dynamic_xyz)
+        assert d_pred_static.numel() >= n and d_pred_static.element_size() == 1 and (d_class is None or d_class.numel() >= n)
+        self._chk(self.lib.scvod_classify_map_device(self.h, po, C.c_void_p(d_pred_static.data_ptr()) if n else None, n, ps, n_s, pd, n_d,
+                                                     float(r15), float(r10), C.c_void_p(d_class.data_ptr()) if d_class is not None else None,
+                                                     C.c_void_p(stream or 0)))
+
+    def classify_map_stats(self):
+        """points per class {unmatched, tp_static, fn_static, tn_dynamic, fn_dynamic} of the last classify_map_device; synchronises"""
+        out = np.zeros(5, np.int64)
+        self._chk(self.lib.scvod_classify_map_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(zip(("unmatched", "tp_static", "fn_static", "tn_dynamic", "fn_dynamic"), (int(v) for v in out)))
 
     def voxelgrid(self, xyzi, leaf=(0.08, 0.08, 0.08), labels=None, max_intensity=1.0):
         """SSC::getCloud label filter + pcl::VoxelGrid of one host scan (ssc.cpp:1063-1076, 1103-1106)."""

@@ -758,6 +758,69 @@ void scvod_feature_row(const scvod_object* object, const scvod_object_shape* sha
  * 0.2, 0.2, 0.2, 0.2, 0.6, 0.2, 0.0 of ssc.cpp:900-909 (column 10 is not read). */
 float scvod_compare_feature(const double* a, const double* b);
 
+/* ---- evaluation against labelled truth, on the device (opt-in: nothing runs or is allocated unless it is called) ------------------
+ * Reference analogue: tool/analysis.py:124-194 -- the counters behind the published PR / RR / F1 table -- and the colour classes of the
+ * map viewer (src/evaluate.cpp:79-145).  A ground-truth point is an INLIER when its nearest estimate point (squared distance
+ * d = (dx*dx + dy*dy) + dz*dz in fp32, ties to the lowest estimate index) satisfies sqrt((double)d) < voxelsize * sqrt(3.0) / 2, evaluated
+ * in double exactly as written.  A label is DYNAMIC when (label & 0xFFFF) is in the class list.  The look-up is one 27-cell probe of a hash
+ * grid with cell edge max(voxelsize, 0.2): the inlier radius is 0.87 cell edges, so the nearest candidate inside it is the true nearest
+ * neighbour and a point without one has no inlier -- there is no second pass.  All counts are integer sums: the same on every run. */
+typedef struct scvod_eval_params {
+    double voxelsize;            /* analysis.py's voxelsize: positive and finite                                         */
+    int32_t n_dynamic_classes;   /* 0..16                                                                                */
+    uint16_t dynamic_classes[16];
+} scvod_eval_params;
+/* voxelsize 0.2, the classes 252..259 (analysis.py:6, config ssc/dynamic_label_) */
+void scvod_eval_params_default(scvod_eval_params* p);
+typedef struct scvod_eval_result {
+    int64_t num_gt_static, num_gt_dynamic, num_est_static, num_est_dynamic, num_preserved, num_static_preserved, num_dynamic_preserved;
+    double PR, RR, F1;
+} scvod_eval_result;
+/* Host only, no device.  counts: the seven counts in the order of the struct.  PR = 100.0 * num_static_preserved / num_gt_static,
+ * RR = 100.0 * (num_gt_dynamic - num_dynamic_preserved) / num_gt_dynamic, F1 = 2 * (PR / 100) * (RR / 100) / ((PR / 100) + (RR / 100))
+ * when PR + RR > 0, else 0.0: the double operations of analysis.py:186-190 in their order.  A rate whose denominator is 0 is NaN, and
+ * F1 is then NaN: analysis.py would raise there; reporting NaN is this library's choice. */
+void scvod_eval_finish(const int64_t counts[7], scvod_eval_result* out);
+/* Ground truth (d_gt_xyz packed at 12 B per point as in scvod_nn_search_device, d_gt_label uint32) against an estimate cloud of the same
+ * form.  d_point_result: NULL, or one byte per gt point: bit 0 inlier, bit 1 gt dynamic, bit 2 estimate dynamic at the neighbour (set only
+ * together with bit 0: a point without an inlier has no neighbour); nothing per point is written without it.  Stream-ordered (stream
+ * NULL = the ctx's stream), never synchronises with the host; each call overwrites the counters of the one before, and the evaluation
+ * calls of one ctx must be ordered among themselves (they share the scratch).  Argument errors (NULL ctx, negative sizes, a NULL array of
+ * a non-empty cloud, more than 16 classes, a voxelsize that is not positive and finite) are SCVOD_ERR_INVALID before any device is
+ * looked for.  Scratch (the grid and the counter words; for the batch form also world xyz, a keep byte and a label byte per point and
+ * 12 floats per scan) is an allocation of its own, grow-only, freed by scvod_destroy and NOT part of scvod_arena_bytes; a call that
+ * needs more than any before waits for the evaluation in flight before it grows. */
+int scvod_evaluate_device(scvod_ctx* ctx, const float* d_gt_xyz, const uint32_t* d_gt_label, int32_t n_gt, const float* d_est_xyz,
+                          const uint32_t* d_est_label, int32_t n_est, const scvod_eval_params* params, uint8_t* d_point_result,
+                          void* stream);
+/* The ERASOR protocol for the ctx's last batch: ground truth is EVERY input point of the batch in the world frame (h_poses [n_scans][6],
+ * the expression of scvod_batch_export_points, staged before the call returns) with its label d_gt_label [batch points]; the estimate is
+ * the points scvod_batch_export_points would keep with the same `flags`, carrying the same labels -- as a keep mask over the same world
+ * array: the export is stable, so the tie rule sees the export's order.  State rules and errors are those of scvod_batch_point_labels
+ * with the same flags (SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED, SCVOD_MAP_IGNORE_DYNAMIC; the part flags are refused).  No output
+ * of the batch changes.  The whole batch is evaluated: a shard that wants to leave its halo out exports its own scans and calls
+ * scvod_evaluate_device itself.  Stream NULL = the stream of the ctx's last batch call. */
+int scvod_batch_evaluate(scvod_ctx* ctx, const uint32_t* d_gt_label, const float* h_poses, int32_t flags, const scvod_eval_params* params,
+                         uint8_t* d_point_result, void* stream);
+/* counts and rates (scvod_eval_finish) of the last scvod_evaluate_device / scvod_batch_evaluate.  Synchronises that call's stream.
+ * SCVOD_ERR_STATE before the first evaluation. */
+int scvod_evaluate_stats(scvod_ctx* ctx, scvod_eval_result* out);
+/* bytes of device scratch the evaluation holds on this ctx (0 before the first call) */
+int64_t scvod_evaluate_scratch_bytes(scvod_ctx* ctx);
+/* evaluate() of src/evaluate.cpp:79-145 per point of the original map (d_orig_xyz packed xyz, d_pred_static one byte per point, != 0:
+ * predicted static): s15 / s10 = a point of the static cloud lies at squared distance < r15*r15 / r10*r10 (products in fp32), d15 / d10
+ * the same for the dynamic cloud; then, in this order, predicted static and s15 -> 1 (TP_STATIC), predicted static, not s15, d10 -> 2
+ * (FN_STATIC), predicted dynamic and d15 -> 3 (TN_DYNAMIC), predicted dynamic, not d15, s10 -> 4 (FN_DYNAMIC), otherwise 0 (UNMATCHED).
+ * An empty cloud matches nothing.  d_class: one byte per point, or NULL (counts only).  The grids' cell edge is 0.2, so r15 and r10
+ * must be positive and at most 0.198 (evaluate.cpp's are 0.15 and 0.10); SCVOD_ERR_INVALID otherwise.  Stream rules, scratch and argument
+ * errors as scvod_evaluate_device; the class counters are words of their own (an evaluation in between leaves them alone). */
+int scvod_classify_map_device(scvod_ctx* ctx, const float* d_orig_xyz, const uint8_t* d_pred_static, int32_t n, const float* d_static_xyz,
+                              int32_t n_static, const float* d_dynamic_xyz, int32_t n_dynamic, float r15, float r10, uint8_t* d_class,
+                              void* stream);
+/* h_out5 = points of class 0 .. 4 of the last scvod_classify_map_device.  Synchronises that call's stream.  SCVOD_ERR_STATE before the
+ * first call. */
+int scvod_classify_map_stats(scvod_ctx* ctx, int64_t* h_out5);
+
 #ifdef __cplusplus
 }
 #endif
