@@ -198,6 +198,13 @@ struct scvod_ctx {
     hipStream_t ev_stream = nullptr;   // stream of the last evaluation (scvod_evaluate_stats waits for it; a growing block too)
     hipStream_t ev_cls_stream = nullptr;
     bool ev_ran = false, ev_cls_ran = false;
+    // class scores against labelled truth (scvod_score_classes_device / scvod_batch_score_classes, scvod_classes.hip): a grow-only block
+    // and 24 counter words of their own, allocated by the first call
+    void* cs_buf = nullptr;
+    size_t cs_cap = 0;
+    unsigned long long* cs_counters = nullptr;
+    hipStream_t cs_stream = nullptr;   // stream of the last scoring call (scvod_score_classes_stats waits for it; a growing block too)
+    bool cs_ran = false;
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1458,6 +1465,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->shape_stats) hipFree(c->shape_stats);
     if (c->ev_buf) hipFree(c->ev_buf);
     if (c->ev_counters) hipFree(c->ev_counters);
+    if (c->cs_buf) hipFree(c->cs_buf);
+    if (c->cs_counters) hipFree(c->cs_counters);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
         if (b) hipFree(b);
@@ -2468,6 +2477,26 @@ int scvod_batch_point_labels(scvod_ctx* c, uint8_t* d_labels, int64_t cap, int32
     return SCVOD_OK;
 }
 
+int scvod_batch_point_classes(scvod_ctx* c, uint8_t* d_classes, int64_t cap, int32_t flags, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!d_classes || cap < 0) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (flags & ~SCVOD_MAP_IGNORE_DYNAMIC) return fail(c, SCVOD_ERR_INVALID, "scvod_batch_point_classes takes SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", flags);
+    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
+    if (int rc = export_check(c, use_dyn, "scvod_batch_point_classes")) return rc;
+    if (cap < c->A.total_pts) return fail(c, SCVOD_ERR_CAPACITY, "class buffer too small (%lld < %lld points)", (long long)cap, (long long)c->A.total_pts);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    if (c->A.total_pts > 0) {
+        HIPCHK(c, hipMemsetAsync(d_classes, SCVOD_PT_DROPPED, (size_t)c->A.total_pts, st));
+        if (c->rg_done)
+            launch_point_classes(c->A, c->rg.cls, d_classes, use_dyn, st);
+        else
+            launch_point_labels(c->A, d_classes, use_dyn, st);  // (without the stage every non-car cluster is tree: no point gets 7)
+        HIPCHK(c, hipGetLastError());
+    }
+    return SCVOD_OK;
+}
+
 int scvod_batch_export_points(scvod_ctx* c, int32_t flags, const float* h_poses, const uint32_t* d_payload_in, void* d_xyzi_out,
                               uint32_t* d_payload_out, int32_t* d_src_out, int64_t cap_points, int32_t* d_out_offsets, void* stream) {
     if (!c) return SCVOD_ERR_INVALID;
@@ -3124,6 +3153,191 @@ int scvod_classify_map_stats(scvod_ctx* c, int64_t* h_out5) {
     HIPCHK(c, hipStreamSynchronize(c->ev_cls_stream));
     for (int k = 0; k < 5; ++k) h_out5[k] = (int64_t)h[k];
     return SCVOD_OK;
+}
+
+// ---- class scores against labelled truth (scvod_classes.hip) ----
+void scvod_class_params_default(scvod_class_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->max_dist = 0.75f;
+    p->cell = 0.25f;
+    const uint16_t g[6] = {40, 44, 48, 49, 71, 72}, b[4] = {50, 51, 52, 60}, t[3] = {70, 80, 81};  // plotObject.cpp:3-5
+    p->n_ground = 6;
+    p->n_building = 4;
+    p->n_tree = 3;
+    for (int k = 0; k < 6; ++k) p->ground[k] = g[k];
+    for (int k = 0; k < 4; ++k) p->building[k] = b[k];
+    for (int k = 0; k < 3; ++k) p->tree[k] = t[k];
+}
+
+void scvod_class_finish(const int64_t conf_and_far[21], scvod_class_result* out) {
+    if (!conf_and_far || !out) return;
+    for (int t = 0; t < 4; ++t) {
+        int64_t num = 0;
+        for (int e = 0; e < 5; ++e) num += (out->conf[t][e] = conf_and_far[t * 5 + e]);
+        out->num[t] = num;
+    }
+    out->pd_far = conf_and_far[20];
+    out->P[0] = out->conf[0][1];
+    out->P[1] = out->conf[1][2] + out->conf[1][3];
+    out->P[2] = out->conf[2][2] + out->conf[2][3];
+    out->P[3] = out->conf[3][0] + out->conf[3][4] + out->pd_far;
+    for (int t = 0; t < 4; ++t) {  // plotObject.cpp:143-146: (float)P / num, 0 / 0 prints nan
+        out->rate_P[t] = (float)out->P[t] / (float)out->num[t];
+        out->rate_N[t] = (float)(out->num[t] - out->P[t]) / (float)out->num[t];
+    }
+}
+
+// the parameters of a call (NULL: the defaults) as the kernels take them; argument errors only
+static int cs_params(scvod_ctx* c, const scvod_class_params* params, CsLists* L, float* cell, float* max_dist, int32_t* rings) {
+    scvod_class_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_class_params_default(&p);
+    if (p.n_ground < 0 || p.n_ground > 8 || p.n_building < 0 || p.n_building > 8 || p.n_tree < 0 || p.n_tree > 8)
+        return fail(c, SCVOD_ERR_INVALID, "class lists of %d / %d / %d labels (0..8 each)", p.n_ground, p.n_building, p.n_tree);
+    if (!(p.cell > 0.f) || !std::isfinite(p.cell) || !(p.max_dist > 0.f) || !std::isfinite(p.max_dist))
+        return fail(c, SCVOD_ERR_INVALID, "cell and max_dist must be positive and finite");
+    if (!(p.max_dist * p.max_dist > 0.5f) || !std::isfinite(p.max_dist * p.max_dist))
+        return fail(c, SCVOD_ERR_INVALID, "max_dist %g: max_dist * max_dist must exceed 0.5 (the pd rule's distance)", (double)p.max_dist);
+    const double r = std::ceil((double)p.max_dist / (0.99 * (double)p.cell));
+    if (!(r <= 32.0)) return fail(c, SCVOD_ERR_INVALID, "max_dist %g spans more than 32 rings of cells of %g", (double)p.max_dist, (double)p.cell);
+    memset(L, 0, sizeof(*L));
+    L->n_ground = p.n_ground;
+    L->n_building = p.n_building;
+    L->n_tree = p.n_tree;
+    for (int k = 0; k < 8; ++k) {
+        L->ground[k] = p.ground[k];
+        L->building[k] = p.building[k];
+        L->tree[k] = p.tree[k];
+    }
+    *cell = p.cell;
+    *max_dist = p.max_dist;
+    *rings = r < 1.0 ? 1 : (int32_t)r;
+    return SCVOD_OK;
+}
+
+// the scoring's scratch block of at least `bytes` (grow-only; growing waits for the scoring in flight, which reads the old one)
+static int cs_reserve(scvod_ctx* c, size_t bytes) {
+    if (!c->cs_counters) {
+        HIPCHK(c, hipMalloc(&c->cs_counters, sizeof(unsigned long long) * 24));
+        HIPCHK(c, hipMemset(c->cs_counters, 0, sizeof(unsigned long long) * 24));
+    }
+    if (bytes > c->cs_cap) {
+        if (c->cs_buf) {
+            if (c->cs_ran) HIPCHK(c, hipStreamSynchronize(c->cs_stream));
+            hipFree(c->cs_buf);
+            c->cs_buf = nullptr;
+            c->cs_cap = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->cs_buf, bytes + bytes / 4));
+        c->cs_cap = bytes + bytes / 4;
+    }
+    return SCVOD_OK;
+}
+
+int scvod_score_classes_device(scvod_ctx* c, const float* d_gt_xyz, const uint32_t* d_gt_label, int32_t n_gt, const float* d_est_xyz,
+                               const uint8_t* d_est_class, int32_t n_est, const scvod_class_params* params, uint8_t* d_point_result,
+                               void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_gt < 0 || n_est < 0 || (n_gt > 0 && (!d_gt_xyz || !d_gt_label)) || (n_est > 0 && (!d_est_xyz || !d_est_class)))
+        return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    CsLists L;
+    float cell, max_dist;
+    int32_t rings;
+    if (int rc = cs_params(c, params, &L, &cell, &max_dist, &rings)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const int32_t buckets = ev_buckets(n_est);
+    if (int rc = cs_reserve(c, cs_work_bytes(buckets, n_est, n_gt))) return rc;
+    launch_class_score(d_gt_xyz, d_gt_label, n_gt, d_est_xyz, d_est_class, nullptr, n_est, L, cell, max_dist, rings, buckets, (int*)c->cs_buf,
+                       c->cs_counters, d_point_result, st);
+    HIPCHK(c, hipGetLastError());
+    c->cs_stream = st;
+    c->cs_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_score_classes(scvod_ctx* c, const uint32_t* d_gt_label, const float* h_poses, int32_t flags, const scvod_class_params* params,
+                              uint8_t* d_point_result, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!d_gt_label || !h_poses) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (flags & ~(SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED | SCVOD_MAP_IGNORE_DYNAMIC))
+        return fail(c, SCVOD_ERR_INVALID, "scvod_batch_score_classes takes SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED and SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", flags);
+    CsLists L;
+    float cell, max_dist;
+    int32_t rings;
+    if (int rc = cs_params(c, params, &L, &cell, &max_dist, &rings)) return rc;
+    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
+    if (int rc = export_check(c, use_dyn, "scvod_batch_score_classes")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    const int B = c->A.n_scans;
+    const int32_t N = (int32_t)c->A.total_pts;
+    const int32_t buckets = ev_buckets(N);
+    // world xyz | keep byte | class byte | pose matrices | grid and list
+    const size_t n1 = (size_t)(N > 0 ? N : 1);
+    const size_t off_keep = align_up(12 * n1, 256), off_cls = off_keep + align_up(n1, 256), off_pose = off_cls + align_up(n1, 256),
+                 off_grid = off_pose + align_up(sizeof(float) * 12 * (size_t)(B > 0 ? B : 1), 256);
+    if (int rc = cs_reserve(c, off_grid + cs_work_bytes(buckets, N, N))) return rc;
+    unsigned char* base = (unsigned char*)c->cs_buf;
+    float* world = (float*)base;
+    uint8_t* keep = base + off_keep;
+    uint8_t* cls = base + off_cls;
+    float* pose = (float*)(base + off_pose);
+    if (B > 0) {  // pcl::getTransformation per scan, staged before the call returns: h_poses is the caller's again at once
+        std::vector<float> T((size_t)12 * B);
+        for (int s = 0; s < B; ++s) scvod_pose_matrix(h_poses + 6 * s, T.data() + 12 * s);
+        if (int rc = staged_upload(c, T.data(), sizeof(float) * T.size(), pose, st)) return rc;
+    }
+    // scvod_batch_export_points' rule; a building point is kept as the STATIC_OTHER point it is for the export
+    uint32_t keep_mask = (1u << SCVOD_PT_UNCLUSTERED) | (1u << SCVOD_PT_STATIC_OTHER) | (1u << SCVOD_PT_STATIC_CAR) | (1u << SCVOD_PT_STATIC_BUILDING);
+    if (!(flags & SCVOD_MAP_NO_GROUND)) keep_mask |= 1u << SCVOD_PT_GROUND;
+    if (!(flags & SCVOD_MAP_NO_REJECTED)) keep_mask |= 1u << SCVOD_PT_REJECTED;
+    if (!use_dyn) keep_mask |= 1u << SCVOD_PT_DYNAMIC;
+    if (N > 0) {
+        HIPCHK(c, hipMemsetAsync(cls, SCVOD_PT_DROPPED, (size_t)N, st));
+        if (c->rg_done)
+            launch_point_classes(c->A, c->rg.cls, cls, use_dyn, st);
+        else
+            launch_point_labels(c->A, cls, use_dyn, st);
+        launch_eval_world(c->A, cls, keep_mask, pose, world, keep, st);  // (k_ev_world: the export's expression and keep rule)
+    }
+    launch_class_score(world, d_gt_label, N, world, cls, keep, N, L, cell, max_dist, rings, buckets, (int*)(base + off_grid), c->cs_counters,
+                       d_point_result, st);
+    HIPCHK(c, hipGetLastError());
+    c->cs_stream = st;
+    c->cs_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_score_classes_stats(scvod_ctx* c, scvod_class_result* out) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!out) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->cs_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_score_classes_device or scvod_batch_score_classes on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h[24] = {0};
+    HIPCHK(c, hipMemcpyAsync(h, c->cs_counters, sizeof(h), hipMemcpyDeviceToHost, c->cs_stream));
+    HIPCHK(c, hipStreamSynchronize(c->cs_stream));
+    int64_t counts[21];
+    for (int k = 0; k < 21; ++k) counts[k] = (int64_t)h[k];
+    scvod_class_finish(counts, out);
+    return SCVOD_OK;
+}
+
+int64_t scvod_score_classes_pass2_queries(scvod_ctx* c) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!c->cs_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_score_classes_device or scvod_batch_score_classes on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h = 0;
+    HIPCHK(c, hipMemcpyAsync(&h, c->cs_counters + 21, sizeof(h), hipMemcpyDeviceToHost, c->cs_stream));
+    HIPCHK(c, hipStreamSynchronize(c->cs_stream));
+    return (int64_t)h;
+}
+
+int64_t scvod_score_classes_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->cs_cap + (c->cs_counters ? (int64_t)sizeof(unsigned long long) * 24 : 0) : 0;
 }
 
 }  // extern "C"

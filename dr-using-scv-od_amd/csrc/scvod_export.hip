@@ -1,5 +1,6 @@
 // scvod_export.hip -- the result of a batch handed to the next consumer on the device (gfx950): one label byte per INPUT point
-// (scvod_batch_point_labels) and the kept points of every scan, compacted in input order (scvod_batch_export_points).
+// (scvod_batch_point_labels; scvod_batch_point_classes with the building / tree split) and the kept points of every scan, compacted in
+// input order (scvod_batch_export_points).
 //
 // Reference analogue: the `static_pt` / `dynamic_pt` lists of SSC::saveSegCloud mode 3 (ssc.cpp:477-554) and the clouds of the
 // evaluation block (`cloud_eva_static`, `g_cloud_vec`, the _static / _dynamic / _original .pcd files, ssc.cpp:1454-1540).  The
@@ -45,6 +46,41 @@ __global__ __launch_bounds__(256) void k_exp_labels(Arena A, uint8_t* __restrict
             if (t < n_a) {
                 idx[u] = A.apri_src[(size_t)base + t];
                 lab[u] = exp_label_of(A.pt_type[(size_t)base + t], use_dyn ? A.pt_dyn[(size_t)base + t] : (uint8_t)0, use_dyn);
+            } else if (t < n_a + n_g) {
+                idx[u] = A.ground_idx[(size_t)base + (t - n_a)];
+                lab[u] = SCVOD_PT_GROUND;
+            } else if (t < total) {
+                idx[u] = A.rejected_src[(size_t)base + (t - n_a - n_g)];
+                lab[u] = SCVOD_PT_REJECTED;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if ((unsigned)idx[u] < (unsigned)n) labels[(size_t)base + idx[u]] = lab[u];
+    }
+}
+
+// k_exp_labels with the region growing's split carried into the byte (scvod_batch_point_classes): the same three lists, and per apri
+// point one more byte -- cls, the class of its cluster (3: building).  A point that would be STATIC_OTHER becomes STATIC_BUILDING there.
+__global__ __launch_bounds__(256) void k_exp_classes(Arena A, const uint8_t* __restrict__ cls, uint8_t* __restrict__ labels, int use_dyn) {
+    const int s = blockIdx.y;
+    const int base = A.scan_off[s];
+    const int n = A.scan_off[s + 1] - base;
+    const int n_g = A.counts[s * 8 + 1], n_a = A.counts[s * 8 + 4], n_r = A.counts[s * 8 + 5];
+    const int total = n_a + n_g + n_r;
+    constexpr int U = 4;
+    for (int t0 = blockIdx.x * (256 * U) + threadIdx.x; t0 < total; t0 += gridDim.x * (256 * U)) {
+        int idx[U];
+        uint8_t lab[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = t0 + u * 256;
+            idx[u] = -1;
+            lab[u] = SCVOD_PT_DROPPED;
+            if (t < n_a) {
+                idx[u] = A.apri_src[(size_t)base + t];
+                lab[u] = exp_label_of(A.pt_type[(size_t)base + t], use_dyn ? A.pt_dyn[(size_t)base + t] : (uint8_t)0, use_dyn);
+                if (lab[u] == SCVOD_PT_STATIC_OTHER && cls[(size_t)base + t] == 3) lab[u] = SCVOD_PT_STATIC_BUILDING;
             } else if (t < n_a + n_g) {
                 idx[u] = A.ground_idx[(size_t)base + (t - n_a)];
                 lab[u] = SCVOD_PT_GROUND;
@@ -186,6 +222,11 @@ __global__ __launch_bounds__(256) void k_exp_write(Arena A, ExportJob J) {
 void launch_point_labels(const Arena& A, uint8_t* labels, int use_dyn, hipStream_t st) {
     if (A.max_scan_pts <= 0) return;
     hipLaunchKernelGGL(k_exp_labels, dim3((A.max_scan_pts + 2047) / 2048, A.n_scans), dim3(256), 0, st, A, labels, use_dyn);
+}
+
+void launch_point_classes(const Arena& A, const uint8_t* cls, uint8_t* labels, int use_dyn, hipStream_t st) {
+    if (A.max_scan_pts <= 0) return;
+    hipLaunchKernelGGL(k_exp_classes, dim3((A.max_scan_pts + 2047) / 2048, A.n_scans), dim3(256), 0, st, A, cls, labels, use_dyn);
 }
 
 void launch_export(const Arena& A, const ExportJob& J, hipStream_t st) {

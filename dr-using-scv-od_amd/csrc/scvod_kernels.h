@@ -302,6 +302,8 @@ struct ExportJob {
     int32_t tiles_per_scan;
 };
 void launch_point_labels(const Arena& A, uint8_t* labels, int use_dyn, hipStream_t st);
+// the labels with the class of an apri point's cluster carried along (scvod_batch_point_classes): cls [N] per apri point, 3 = building
+void launch_point_classes(const Arena& A, const uint8_t* cls, uint8_t* labels, int use_dyn, hipStream_t st);
 void launch_export(const Arena& A, const ExportJob& J, hipStream_t st);
 
 // the clusters of a batch as an object table (scvod_batch_objects; scvod_objects.hip).  Tiles as in the export, over the APRI points of a
@@ -406,6 +408,18 @@ void launch_eval_world(const Arena& A, const uint8_t* labels, uint32_t keep_mask
 void launch_classify(const float* orig_xyz, const uint8_t* pred_static, int32_t n, const float* static_xyz, int32_t n_static,
                      const float* dynamic_xyz, int32_t n_dynamic, float r15, float r10, float cell, int32_t buckets_s, int* work_s,
                      int32_t buckets_d, int* work_d, unsigned long long* counters, uint8_t* cls, hipStream_t st);
+
+// class scores against labelled truth (scvod_score_classes_device / scvod_batch_score_classes; scvod_classes.hip).  The grid is the
+// evaluation's (ev_buckets, ev_grid_ints) with the caller's cell edge; work: cs_work_bytes bytes; counters: 24 words, cleared by every
+// launch: conf[4][5] row-major, pd_far, the pass-2 list's length, 0, 0.  est_class: one SCVOD_PT_* byte per estimate point
+struct CsLists {  // the semantic classes (label & 0xFFFF) of ground / building / tree truth points
+    int32_t n_ground, n_building, n_tree;
+    uint16_t ground[8], building[8], tree[8];
+};
+size_t cs_work_bytes(int32_t buckets, int32_t n_est, int32_t n_gt);
+void launch_class_score(const float* gt_xyz, const uint32_t* gt_label, int32_t n_gt, const float* est_xyz, const uint8_t* est_class,
+                        const uint8_t* est_keep, int32_t n_est, const CsLists& L, float cell, float max_dist, int32_t rings, int32_t buckets,
+                        int* work, unsigned long long* counters, uint8_t* point_result, hipStream_t st);
 
 }  // namespace scvod
 #endif

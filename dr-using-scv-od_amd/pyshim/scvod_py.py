@@ -86,6 +86,25 @@ EVAL_RESULT = EvalResult
 EVAL_INLIER, EVAL_GT_DYNAMIC, EVAL_EST_DYNAMIC = 1, 2, 4
 
 
+class ClassParams(C.Structure):
+    """struct scvod_class_params (include/scvod.h)"""
+    _fields_ = [("max_dist", C.c_float), ("cell", C.c_float), ("n_ground", C.c_int32), ("n_building", C.c_int32), ("n_tree", C.c_int32),
+                ("ground", C.c_uint16 * 8), ("building", C.c_uint16 * 8), ("tree", C.c_uint16 * 8)]
+
+
+class ClassResult(C.Structure):
+    """struct scvod_class_result (include/scvod.h): conf[truth class][estimate class], pd_far, then what scvod_class_finish fills"""
+    _fields_ = [("conf", (C.c_int64 * 5) * 4), ("pd_far", C.c_int64), ("num", C.c_int64 * 4), ("P", C.c_int64 * 4),
+                ("rate_P", C.c_float * 4), ("rate_N", C.c_float * 4)]
+
+
+CLASS_RESULT = ClassResult
+# truth classes (rows of conf) and estimate classes (its columns); scvod_score_classes_device's per-point byte
+CLASS_TRUTH = ("ground", "building", "tree", "pd")
+CLASS_ESTIMATE = ("other", "ground", "building", "tree", "none")
+CLASS_P = 32
+
+
 class ScanResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_points", "n_ground", "n_nonground", "n_dropped", "n_apri", "n_rejected",
                                           "n_voxels", "n_patches")] + \
@@ -243,6 +262,14 @@ def load_lib():
         "scvod_evaluate_scratch_bytes": (i64, [vp]),
         "scvod_classify_map_device": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, i32, f32, f32, vp, vp]),
         "scvod_classify_map_stats": (C.c_int, [vp, vp]),
+        "scvod_batch_point_classes": (C.c_int, [vp, vp, i64, i32, vp]),
+        "scvod_class_params_default": (None, [C.POINTER(ClassParams)]),
+        "scvod_class_finish": (None, [vp, C.POINTER(ClassResult)]),
+        "scvod_score_classes_device": (C.c_int, [vp, vp, vp, i32, vp, vp, i32, C.POINTER(ClassParams), vp, vp]),
+        "scvod_batch_score_classes": (C.c_int, [vp, vp, vp, i32, C.POINTER(ClassParams), vp, vp]),
+        "scvod_score_classes_stats": (C.c_int, [vp, C.POINTER(ClassResult)]),
+        "scvod_score_classes_pass2_queries": (i64, [vp]),
+        "scvod_score_classes_scratch_bytes": (i64, [vp]),
         "scvod_batch_voxelgrid": (C.c_int, [vp, vp, vp, vp, i32, vp, f32, vp, i64, vp, vp]),
         "scvod_voxelgrid": (C.c_int, [vp, vp, vp, i32, vp, f32, vp, i32, vp]),
     }
@@ -268,7 +295,10 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_feature_row", "scvod_compare_feature",
                     "scvod_batch_timings", "scvod_set_timing", "scvod_nn_search", "scvod_nn_radius_search", "scvod_nn_search_device", "scvod_batch_voxelgrid", "scvod_voxelgrid",
                     "scvod_eval_params_default", "scvod_eval_finish", "scvod_evaluate_device", "scvod_batch_evaluate", "scvod_evaluate_stats",
-                    "scvod_evaluate_scratch_bytes", "scvod_classify_map_device", "scvod_classify_map_stats"]
+                    "scvod_evaluate_scratch_bytes", "scvod_classify_map_device", "scvod_classify_map_stats",
+                    "scvod_batch_point_classes", "scvod_class_params_default", "scvod_class_finish", "scvod_score_classes_device",
+                    "scvod_batch_score_classes", "scvod_score_classes_stats", "scvod_score_classes_pass2_queries",
+                    "scvod_score_classes_scratch_bytes"]
 
 
 def eval_params_default(voxelsize=None, dynamic_classes=None):
@@ -296,6 +326,38 @@ def eval_finish(counts):
     r = EvalResult()
     load_lib().scvod_eval_finish(cnt.ctypes.data_as(C.c_void_p), C.byref(r))
     return _eval_dict(r)
+
+
+def class_params_default(max_dist=None, cell=None, ground=None, building=None, tree=None):
+    """scvod_class_params with the reference's lists (plotObject.cpp:3-5), max_dist 0.75 and cell 0.25, overridden by keyword"""
+    p = ClassParams()
+    load_lib().scvod_class_params_default(C.byref(p))
+    if max_dist is not None:
+        p.max_dist = float(max_dist)
+    if cell is not None:
+        p.cell = float(cell)
+    for name, lst in (("ground", ground), ("building", building), ("tree", tree)):
+        if lst is not None:
+            cl = [int(v) for v in lst]
+            setattr(p, "n_" + name, len(cl))  # (more than 8: the library refuses the call)
+            arr = getattr(p, name)
+            for k in range(8):
+                arr[k] = cl[k] if k < len(cl) else 0
+    return p
+
+
+def _class_dict(r):
+    return dict(conf=[[int(v) for v in row] for row in r.conf], pd_far=int(r.pd_far), num=[int(v) for v in r.num], P=[int(v) for v in r.P],
+                rate_P=np.asarray(list(r.rate_P), np.float32), rate_N=np.asarray(list(r.rate_N), np.float32))
+
+
+def class_finish(conf_and_far):
+    """conf (4 x 5, row-major) and pd_far, 21 counts -> the dict with num, P, rate_P, rate_N (fp32).  Host only"""
+    cnt = np.ascontiguousarray(conf_and_far, np.int64).reshape(-1)
+    assert cnt.size == 21
+    r = ClassResult()
+    load_lib().scvod_class_finish(cnt.ctypes.data_as(C.c_void_p), C.byref(r))
+    return _class_dict(r)
 
 
 def feature_params(**kw):
@@ -743,6 +805,16 @@ class Ctx:
                                                     C.c_void_p(stream or 0)))
         return d_labels
 
+    def batch_point_classes(self, d_classes=None, flags=0, stream=None):
+        """batch_point_labels with the region growing's split in the byte: PT_STATIC_BUILDING where a PT_STATIC_OTHER point's cluster
+        is a building.  Same arguments, same state rules"""
+        if d_classes is None:
+            import torch
+            d_classes = torch.empty(max(self._n_pts, 1), dtype=torch.uint8, device=f"cuda:{self.device}")
+        self._chk(self.lib.scvod_batch_point_classes(self.h, C.c_void_p(d_classes.data_ptr()), int(d_classes.numel()), int(flags),
+                                                     C.c_void_p(stream or 0)))
+        return d_classes
+
     def batch_export_points(self, d_out_offsets, d_xyzi_out=None, flags=0, poses=None, d_payload_in=None, d_payload_out=None,
                             d_src_out=None, stream=None):
         """the kept points of the last batch, compacted in input order, into d_xyzi_out (torch float32 device tensor [cap, 4]; None:
@@ -894,6 +966,51 @@ class Ctx:
         """device scratch of the evaluation on this ctx (not part of arena_bytes)"""
         return int(self.lib.scvod_evaluate_scratch_bytes(self.h))
 
+    # ---- class scores against labelled truth on the device (include/scvod.h: scvod_score_classes_device ...) ----
+    def score_classes_device(self, d_gt_xyz, d_gt_label, d_est_xyz, d_est_class, params=None, d_point_result=None, stream=None):
+        """labelled truth against an estimate with one PT_* byte per point (batch_point_classes' bytes), both on the device: contiguous
+        torch float32 [n, 3] clouds, labels as 4-byte words, classes as uint8.  d_point_result: torch uint8 [n_gt] or None.
+        Asynchronous on `stream`: score_classes_stats()"""
+        pg, n_gt = self._xyz(d_gt_xyz)
+        pe, n_est = self._xyz(d_est_xyz)
+        assert d_gt_label.numel() >= n_gt and d_gt_label.element_size() == 4
+        assert d_est_class.numel() >= n_est and d_est_class.element_size() == 1
+        assert d_point_result is None or d_point_result.numel() >= n_gt
+        self._chk(self.lib.scvod_score_classes_device(self.h, pg, C.c_void_p(d_gt_label.data_ptr()) if n_gt else None, n_gt, pe,
+                                                      C.c_void_p(d_est_class.data_ptr()) if n_est else None, n_est,
+                                                      C.byref(params) if params is not None else None,
+                                                      C.c_void_p(d_point_result.data_ptr()) if d_point_result is not None else None,
+                                                      C.c_void_p(stream or 0)))
+
+    def batch_score_classes(self, d_gt_label, poses, flags=0, params=None, d_point_result=None, stream=None):
+        """batch_evaluate's protocol for the class scores: every input point of the last batch in the world frame with its label against
+        the points batch_export_points would keep with the same flags, each carrying its byte of batch_point_classes.  Asynchronous on
+        `stream`: score_classes_stats()"""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p.shape[0] == self._n_scans and d_gt_label.numel() >= self._n_pts and d_gt_label.element_size() == 4
+        assert d_point_result is None or d_point_result.numel() >= self._n_pts
+        self._chk(self.lib.scvod_batch_score_classes(self.h, C.c_void_p(d_gt_label.data_ptr()), p.ctypes.data_as(C.c_void_p), int(flags),
+                                                     C.byref(params) if params is not None else None,
+                                                     C.c_void_p(d_point_result.data_ptr()) if d_point_result is not None else None,
+                                                     C.c_void_p(stream or 0)))
+
+    def score_classes_stats(self):
+        """conf, pd_far, num, P, rate_P, rate_N of the last score_classes_device / batch_score_classes; synchronises its stream"""
+        r = ClassResult()
+        self._chk(self.lib.scvod_score_classes_stats(self.h, C.byref(r)))
+        return _class_dict(r)
+
+    def score_classes_pass2_queries(self):
+        """truth points of the last scoring call that needed the ring search (a cost measure); synchronises its stream"""
+        n = int(self.lib.scvod_score_classes_pass2_queries(self.h))
+        if n < 0:
+            self._chk(n)
+        return n
+
+    def score_classes_scratch_bytes(self):
+        """device scratch of the class scores on this ctx (not part of arena_bytes or evaluate_scratch_bytes)"""
+        return int(self.lib.scvod_score_classes_scratch_bytes(self.h))
+
     def classify_map_device(self, d_orig_xyz, d_pred_static, d_static_xyz, d_dynamic_xyz, r15=0.15, r10=0.1, d_class=None, stream=None):
         """metric.classify_map_points on the device: contiguous torch float32 [n, 3] clouds, d_pred_static one byte per point of the
         original map (uint8 or bool), d_class torch uint8 [n] or None (counts only).  Asynchronous on `stream`: classify_map_stats()"""
@@ -963,6 +1080,7 @@ class Ctx:
 MAP_NO_GROUND, MAP_NO_REJECTED, MAP_IGNORE_DYNAMIC = 1, 2, 4
 # scvod_batch_point_labels: one byte per input point (include/scvod.h, SCVOD_PT_*)
 PT_DROPPED, PT_GROUND, PT_REJECTED, PT_UNCLUSTERED, PT_STATIC_OTHER, PT_STATIC_CAR, PT_DYNAMIC = range(7)
+PT_STATIC_BUILDING = 7  # scvod_batch_point_classes only
 
 
 class StaticMap:

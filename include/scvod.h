@@ -624,14 +624,23 @@ int scvod_map_points(scvod_map* map, void* d_xyzi, void* d_records, int64_t cap,
 #define SCVOD_PT_STATIC_CAR 5    /* apri point of a `car` cluster that is not dynamic (state -1, a scan without a successor,
                                     included)                                                                                 */
 #define SCVOD_PT_DYNAMIC 6       /* pt_dyn == SCVOD_DYN_DYNAMIC                                                               */
+#define SCVOD_PT_STATIC_BUILDING 7 /* scvod_batch_point_classes only: a SCVOD_PT_STATIC_OTHER point whose cluster the region growing
+                                      classed as building                                                                     */
 /* Writes the labels of the last batch into d_labels (device memory of `cap` >= the batch's point count bytes; SCVOD_ERR_CAPACITY
  * otherwise).  The type is the segmentation's, what scvod_batch_fetch_cluster_types reports (the fused partition's when the
  * intensity merge is on), not the type the tracking chain re-assigns to a predecessor at ssc.cpp:1354; the region growing's
- * building / tree split is not carried into the byte.  Needs scvod_batch_cluster and scvod_batch_cluster_types of the batch
+ * building / tree split is not carried into the byte (scvod_batch_point_classes carries it).  Needs scvod_batch_cluster and scvod_batch_cluster_types of the batch
  * (SCVOD_ERR_STATE) and a CURRENT scvod_batch_track -- the validity test scvod_batch_map_accumulate applies; SCVOD_ERR_INVALID when
  * the tracking result is missing or stale.  flags: 0 or SCVOD_MAP_IGNORE_DYNAMIC -- the clustering and the types suffice then,
  * and no point is labelled SCVOD_PT_DYNAMIC. */
 int scvod_batch_point_labels(scvod_ctx* ctx, uint8_t* d_labels, int64_t cap, int32_t flags, void* stream);
+/* scvod_batch_point_labels with the region growing's building / tree split carried into the byte: the same contract (state rules,
+ * errors, flags, stream order, no host synchronisation), the same bytes, except that an apri point which would be SCVOD_PT_STATIC_OTHER
+ * gets SCVOD_PT_STATIC_BUILDING when the class of its cluster is building -- what scvod_batch_fetch_cluster_classes reports for it once
+ * the region growing ran on the last scvod_batch_cluster_types.  Without the region growing every non-car cluster is tree and no point
+ * gets 7: the output is scvod_batch_point_labels' byte for byte.  scvod_batch_point_labels itself, the export and the static map never
+ * see the value 7. */
+int scvod_batch_point_classes(scvod_ctx* ctx, uint8_t* d_classes, int64_t cap, int32_t flags, void* stream);
 /* The kept points of every scan of the last batch, compacted: scans concatenated in batch order, inside a scan in INPUT order (a
  * stable compaction: the output is bit-identical from run to run).  The keep rule is that of scvod_batch_map_accumulate and a
  * function of the label byte alone: SCVOD_PT_DROPPED never; SCVOD_PT_DYNAMIC only with SCVOD_MAP_IGNORE_DYNAMIC; SCVOD_PT_GROUND
@@ -820,6 +829,73 @@ int scvod_classify_map_device(scvod_ctx* ctx, const float* d_orig_xyz, const uin
 /* h_out5 = points of class 0 .. 4 of the last scvod_classify_map_device.  Synchronises that call's stream.  SCVOD_ERR_STATE before the
  * first call. */
 int scvod_classify_map_stats(scvod_ctx* ctx, int64_t* h_out5);
+
+/* ---- the recognised ground / building / tree classes against labelled truth, on the device (opt-in: nothing runs or is allocated
+ * unless it is called) ----------------------------------------------------------------------------------------------------------------
+ * Reference analogue: src/plotObject.cpp:87-146, the tool behind the per-class table of doc/note.txt:57-78.  Every ground-truth point
+ * looks up its nearest estimate point (squared distance d = (dx*dx + dy*dy) + dz*dz in fp32, ties to the lowest estimate index).
+ *   truth class     of (label & 0xFFFF): 0 ground, 1 building, 2 tree -- the three lists, tested in this order (check(),
+ *                   plotObject.cpp:16-29) -- and 3 pd for a label in no list
+ *   estimate class  at the neighbour, from its SCVOD_PT_* byte as scvod_batch_point_classes writes it: 1 ground (SCVOD_PT_GROUND),
+ *                   2 building (SCVOD_PT_STATIC_BUILDING), 3 tree (SCVOD_PT_STATIC_OTHER), 0 other (every other byte: car, rejected,
+ *                   unclustered, dynamic), 4 none (no neighbour) -- the colour test of plotObject.cpp:51-85 on SSC::saveSegCloud's colours
+ *   rules           ground: P iff the neighbour is ground.  building: P iff building or tree.  tree: P iff tree or building.  pd: P iff
+ *                   the neighbour is `other` or d > 0.5f (PCL hands out squared distances: 0.5 m^2, as the reference wrote it).  No
+ *                   neighbour: N for the first three classes, P for pd
+ * Two departures from the reference: the estimate's y is y (plotObject.cpp copies z into it), and a neighbour
+ * counts only when d < max_dist * max_dist (product in fp32); a truth point without one has the estimate class `none`, which is a
+ * column of its own in conf.  max_dist * max_dist > 0.5f is required, so the pd rule is exactly the reference's unbounded one.
+ * The look-up is a hash grid of cell edge `cell` searched ring by ring with early exit, R = ceil(max_dist / (0.99 * cell)) rings at the
+ * most (R <= 32 is required); its result is that of an exhaustive search inside max_dist.  All counts are integer sums: the same on
+ * every run. */
+typedef struct scvod_class_params {
+    float max_dist;            /* neighbours are looked for inside this distance; default 0.75 */
+    float cell;                /* grid cell edge; default 0.25 */
+    int32_t n_ground, n_building, n_tree; /* 0..8 each */
+    uint16_t ground[8], building[8], tree[8];
+} scvod_class_params;
+/* max_dist 0.75, cell 0.25, the lists of plotObject.cpp:3-5: 40,44,48,49,71,72 / 50,51,52,60 / 70,80,81 */
+void scvod_class_params_default(scvod_class_params* p);
+typedef struct scvod_class_result {
+    int64_t conf[4][5];   /* truth class x estimate class at the neighbour */
+    int64_t pd_far;       /* pd points whose neighbour is not `other` but lies at d > 0.5 (they have a neighbour: `none` is not counted) */
+    int64_t num[4], P[4]; /* filled by scvod_class_finish: points and P points per truth class */
+    float rate_P[4], rate_N[4];
+} scvod_class_result;
+/* Host only, no device.  conf_and_far: conf row-major, then pd_far.  num = the row sums; P = conf[0][1], conf[1][2] + conf[1][3],
+ * conf[2][2] + conf[2][3], conf[3][0] + conf[3][4] + pd_far; rate_P = (float)P / (float)num and rate_N = (float)(num - P) / (float)num in
+ * fp32 (plotObject.cpp:143-146).  num == 0 gives NaN: the reference prints `nan` there. */
+void scvod_class_finish(const int64_t conf_and_far[21], scvod_class_result* out);
+/* Ground truth (d_gt_xyz packed at 12 B per point as in scvod_evaluate_device, d_gt_label uint32) against an estimate cloud of the same
+ * form with one SCVOD_PT_* byte per point -- the map-level form: export with scvod_batch_export_points plus d_src_out and gather the
+ * bytes of scvod_batch_point_classes.  d_point_result: NULL, or one byte per gt point: bits 0-1 the truth class, bits 2-4 the estimate
+ * class, bit 5 P.  Stream-ordered (stream NULL = the ctx's stream), never synchronises with the host; each call overwrites the counters
+ * of the one before, and the scoring calls of one ctx must be ordered among themselves (they share their scratch; the evaluation's
+ * scratch is another one, so the two families need no order between them).  Argument errors (NULL ctx, negative sizes, a NULL array
+ * of a non-empty cloud, a list longer than 8, a cell or max_dist that is not positive and finite, max_dist * max_dist <= 0.5, more than
+ * 32 rings) are SCVOD_ERR_INVALID before any device is looked for.  Scratch (the grid, 12 bytes per gt point for the list of the second
+ * pass, 24 counter words; for the batch form also world xyz, a keep byte and a class byte per point and 12 floats per scan) is an
+ * allocation of its own, grow-only, freed by scvod_destroy and NOT part of scvod_arena_bytes or scvod_evaluate_scratch_bytes; a call
+ * that needs more than any before waits for the scoring in flight before it grows. */
+int scvod_score_classes_device(scvod_ctx* ctx, const float* d_gt_xyz, const uint32_t* d_gt_label, int32_t n_gt, const float* d_est_xyz,
+                               const uint8_t* d_est_class, int32_t n_est, const scvod_class_params* params, uint8_t* d_point_result,
+                               void* stream);
+/* The protocol of scvod_batch_evaluate for the ctx's last batch: truth is EVERY input point of the batch in the world frame (h_poses
+ * [n_scans][6], the expression of scvod_batch_export_points, staged before the call returns) with its label d_gt_label [batch points];
+ * the estimate is the points scvod_batch_export_points would keep with the same `flags` -- as a keep mask over the same world array --
+ * each carrying its byte of scvod_batch_point_classes.  State rules and errors are those of scvod_batch_point_labels with the same
+ * flags (SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED, SCVOD_MAP_IGNORE_DYNAMIC; the part flags are refused).  No output of the batch
+ * changes.  Stream NULL = the stream of the ctx's last batch call. */
+int scvod_batch_score_classes(scvod_ctx* ctx, const uint32_t* d_gt_label, const float* h_poses, int32_t flags, const scvod_class_params* params,
+                              uint8_t* d_point_result, void* stream);
+/* counts and rates (scvod_class_finish) of the last scvod_score_classes_device / scvod_batch_score_classes.  Synchronises that call's
+ * stream.  SCVOD_ERR_STATE before the first scoring call. */
+int scvod_score_classes_stats(scvod_ctx* ctx, scvod_class_result* out);
+/* how many truth points of that call went on to the second pass (no candidate within 0.99 cell edges in the 27 cells around them): a
+ * measure of cost, not a result.  Synchronises that call's stream.  Returns the count or a negative status. */
+int64_t scvod_score_classes_pass2_queries(scvod_ctx* ctx);
+/* bytes of device scratch the class scores hold on this ctx (0 before the first call) */
+int64_t scvod_score_classes_scratch_bytes(scvod_ctx* ctx);
 
 #ifdef __cplusplus
 }
