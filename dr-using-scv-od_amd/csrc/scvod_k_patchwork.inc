@@ -113,12 +113,22 @@ __device__ __forceinline__ void order_range(const int32_t* off, int c_lo, int c_
     hi = (c_lo == 0) ? off[64] : off[c_lo - 1];
 }
 
+// which tiers run the pad-free network (scvod_sortnet.h): those measured faster with it (profiles/padfree_sort_cost.md);
+// the 256 tier is slower and the 1024 tier within noise, they keep the padded network.  SCVOD_SORT_PADFREE=0: none, 2: all
+constexpr bool pw_sort_padfree(int cap) { return SCVOD_SORT_PADFREE == 2 || (SCVOD_SORT_PADFREE == 1 && cap >= 2048); }
+
+// (the pad-free network carries a predicated and an unpredicated form of every pass: the register budget is held to the
+//  four waves per SIMD that the launches below put on a CU -- what the padded network reached on its own; the few values
+//  the two large tiers spill are per-item ones, none is touched between the barriers of the network)
 template <int CAP, int THREADS, int C_LO, int C_HI, int LGE>
-__global__ __launch_bounds__(THREADS) void k_pw_sort(DevParams P, Arena A) {
+__global__ __launch_bounds__(THREADS)
+__attribute__((amdgpu_waves_per_eu(pw_sort_padfree(CAP) ? (CAP >= 1024 ? 4 : 6) : 1, 8)))
+void k_pw_sort(DevParams P, Arena A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int lo, hi;
     order_range(A.order_off, C_LO, C_HI, lo, hi);
     constexpr int PK = (CAP == 4096) ? 1 : 2;  // (profiling build: the two large tiers are clocked)
+    constexpr bool PADFREE = pw_sort_padfree(CAP);
     PROF_BEGIN();
     for (int w = lo + blockIdx.x; w < hi; w += gridDim.x) {
         const int4 item = A.order[w];
@@ -130,6 +140,7 @@ __global__ __launch_bounds__(THREADS) void k_pw_sort(DevParams P, Arena A) {
             keys = (unsigned long long*)smem;
             int np2 = 1 << LGE;
             while (np2 < n) np2 <<= 1;
+            const int nlive = sortnet::live_end(n, LGE);
             // a full tier: all of a thread's key loads in flight together (coalesced), sorted straight from the registers
             constexpr int IT = CAP / THREADS;
             const unsigned long long* gk = (const unsigned long long*)A.keys + (size_t)base + off;
@@ -138,20 +149,36 @@ __global__ __launch_bounds__(THREADS) void k_pw_sort(DevParams P, Arena A) {
                 if (np2 == CAP) {
                     from_regs = true;
                     unsigned long long tmp[IT];
+                    if constexpr (PADFREE) {  // the first nlive / IT threads hold the keys, coalesced among themselves
+                        if ((int)threadIdx.x < (nlive >> LGE)) {
 #pragma unroll
-                    for (int it = 0; it < IT; ++it) {
-                        const int j = it * THREADS + (int)threadIdx.x;
-                        tmp[it] = (j < n) ? gk[j] : kKeyPad;
+                            for (int it = 0; it < IT; ++it) {
+                                const int j = sortnet::start_key(it, (int)threadIdx.x, nlive, LGE);
+                                tmp[it] = (j < n) ? gk[j] : kKeyPad;
+                            }
+                        }
+                        if (CAP >= 4096) PROF_MARK(PK, 0);
+                        padfree_sort_regs<THREADS, true, LGE>(tmp, keys, np2, nlive, (unsigned long long)kKeyPad);
+                    } else {
+#pragma unroll
+                        for (int it = 0; it < IT; ++it) {
+                            const int j = it * THREADS + (int)threadIdx.x;
+                            tmp[it] = (j < n) ? gk[j] : kKeyPad;
+                        }
+                        if (CAP >= 4096) PROF_MARK(PK, 0);
+                        block_bitonic_sort_pow2_regs<THREADS, true, LGE>(tmp, keys);
                     }
-                    if (CAP >= 4096) PROF_MARK(PK, 0);
-                    block_bitonic_sort_pow2_regs<THREADS, true, LGE>(tmp, keys);
                 }
             }
             if (!from_regs) {
-                for (int j = threadIdx.x; j < np2; j += THREADS) keys[sort_slot<true>(j)] = (j < n) ? gk[j] : kKeyPad;
+                const int nfill = PADFREE ? nlive : np2;  // (pad-free: slots >= nlive are never touched)
+                for (int j = threadIdx.x; j < nfill; j += THREADS) keys[sort_slot<true>(j)] = (j < n) ? gk[j] : kKeyPad;
                 __syncthreads();
                 if (CAP >= 4096) PROF_MARK(PK, 0);
-                block_bitonic_sort_pow2<THREADS, true, LGE>(keys, np2);
+                if constexpr (PADFREE)
+                    padfree_sort<THREADS, true, LGE>(keys, np2, nlive, (unsigned long long)kKeyPad);
+                else
+                    block_bitonic_sort_pow2<THREADS, true, LGE>(keys, np2);
             }
             if (CAP >= 4096) PROF_MARK(PK, 1);
         } else {

@@ -192,6 +192,9 @@ __global__ __launch_bounds__(1024) void k_vx_partition(DevParams P, Arena A) {
 #endif
 constexpr size_t vox_key_bytes(int cap, size_t ksize) { return (((size_t)(cap + cap / 8) * (SCVOD_VOX_K32_LDS ? ksize : 8)) + 15) & ~(size_t)15; }
 constexpr size_t vox_lds_bytes(int cap, size_t ksize = 8) { return vox_key_bytes(cap, ksize) + (size_t)cap * 8 + 128; }
+// which tiers run the pad-free network (scvod_sortnet.h): those measured faster with it (profiles/padfree_sort_cost.md);
+// the 256 and 1024 tiers are slower, they keep the padded network.  SCVOD_VOX_PADFREE=0: none, 2: all
+constexpr bool vx_bucket_padfree(int cap) { return SCVOD_VOX_PADFREE == 2 || (SCVOD_VOX_PADFREE == 1 && cap >= 2048); }
 template <int CAP, int THREADS, int C_LO, int C_HI, int LGE, int MODE = 0, typename KT = unsigned long long>
 __global__ __launch_bounds__(THREADS)
 #if SCVOD_VOX_K32_LDS
@@ -200,6 +203,7 @@ __attribute__((amdgpu_waves_per_eu((sizeof(KT) == 4 && CAP <= 4096 && CAP >= 204
 void k_vx_bucket(DevParams P, Arena A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool K32 = sizeof(KT) == 4;
+    constexpr bool PADFREE = vx_bucket_padfree(CAP);
     constexpr bool PADK = true;  // both key types: unpadded 4-byte keys let the compiler fuse neighbouring LDS accesses into
                                  // wide ones that fault on the network's unaligned groups (seen on the 8192-key tier)
     constexpr int SLOTS = CAP + CAP / 8;
@@ -236,6 +240,7 @@ void k_vx_bucket(DevParams P, Arena A) {
     if (in_lds) {
         int np2 = 1 << LGE;
         while (np2 < m) np2 <<= 1;
+        const int nlive = sortnet::live_end(m, LGE);  // the later phases read keys [0, m) only
         // a full tier: all of a thread's key loads in flight together (coalesced), sorted straight from the registers
         constexpr int IT = CAP / THREADS;
         keys = l_keys;
@@ -246,20 +251,36 @@ void k_vx_bucket(DevParams P, Arena A) {
             if (np2 == CAP) {
                 from_regs = true;
                 KT tmp[IT];
+                if constexpr (PADFREE) {  // the first nlive / IT threads hold the keys, coalesced among themselves
+                    if ((int)threadIdx.x < (nlive >> LGE)) {
 #pragma unroll
-                for (int it = 0; it < IT; ++it) {
-                    const int j = it * THREADS + (int)threadIdx.x;
-                    tmp[it] = (j < m) ? gkeys[j] : kpad;
+                        for (int it = 0; it < IT; ++it) {
+                            const int j = sortnet::start_key(it, (int)threadIdx.x, nlive, LGE);
+                            tmp[it] = (j < m) ? gkeys[j] : kpad;
+                        }
+                    }
+                    if (PV) PROF_MARK(3, 0);
+                    padfree_sort_regs<THREADS, PADK, LGE>(tmp, keys, np2, nlive, kpad);
+                } else {
+#pragma unroll
+                    for (int it = 0; it < IT; ++it) {
+                        const int j = it * THREADS + (int)threadIdx.x;
+                        tmp[it] = (j < m) ? gkeys[j] : kpad;
+                    }
+                    if (PV) PROF_MARK(3, 0);
+                    block_bitonic_sort_pow2_regs<THREADS, PADK, LGE>(tmp, keys);
                 }
-                if (PV) PROF_MARK(3, 0);
-                block_bitonic_sort_pow2_regs<THREADS, PADK, LGE>(tmp, keys);
             }
         }
         if (!from_regs) {
-            for (int j = threadIdx.x; j < np2; j += THREADS) l_keys[sort_slot<PADK>(j)] = (j < m) ? gkeys[j] : kpad;
+            const int nfill = PADFREE ? nlive : np2;  // (pad-free: slots >= nlive are never touched)
+            for (int j = threadIdx.x; j < nfill; j += THREADS) l_keys[sort_slot<PADK>(j)] = (j < m) ? gkeys[j] : kpad;
             __syncthreads();
             if (PV) PROF_MARK(3, 0);
-            block_bitonic_sort_pow2<THREADS, PADK, LGE>(keys, np2);
+            if constexpr (PADFREE)
+                padfree_sort<THREADS, PADK, LGE>(keys, np2, nlive, kpad);
+            else
+                block_bitonic_sort_pow2<THREADS, PADK, LGE>(keys, np2);
         }
         if (PV) PROF_MARK(3, 1);
     } else {

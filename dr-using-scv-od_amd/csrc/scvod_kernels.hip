@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "scvod_dev.h"
+#include "scvod_sortnet.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace scvod {
@@ -354,6 +355,67 @@ __device__ __forceinline__ void block_bitonic_merge_stages(T* a, int np2) {
             r -= LGE;
         }
     }
+}
+
+// ---- pad-free form of the same sorts (scvod_sortnet.h) --------------------------------------------
+// All-ascending network whose work follows the keys: with nlive = n rounded up to whole runs, logical
+// slots >= nlive are never loaded, stored or compared, and work items with nothing below nlive go
+// straight to the barrier.  Same runs, same passes and barriers per sort as the padded network above;
+// the index arithmetic and the register networks live in scvod_sortnet.h, where the CPU replays them.
+#ifndef SCVOD_SORT_PADFREE
+#define SCVOD_SORT_PADFREE 1  // Patchwork sort tiers: 1 = pad-free network where it measured faster (pw_sort_padfree), 0 = padded network, 2 = pad-free in every tier
+#endif
+#ifndef SCVOD_VOX_PADFREE
+#define SCVOD_VOX_PADFREE 1  // voxel-bucket tiers, likewise (vx_bucket_padfree)
+#endif
+struct CxAsc {
+    template <typename T>
+    __device__ __forceinline__ void operator()(T& lo, T& hi) const { cswap_asc(lo, hi); }
+};
+
+template <int THREADS, bool PAD, int LT, bool MIRROR, typename T>
+__device__ __forceinline__ void padfree_pass(T* a, int np2, int nlive, int r, T padv) {
+    const int items = sortnet::pass_items(np2, nlive, r, LT);
+    for (int t = threadIdx.x; t < items; t += THREADS) sortnet::pass_item<LT, MIRROR, PAD, T>(a, t, r, nlive, padv, CxAsc{});
+    __syncthreads();
+}
+
+template <int THREADS, bool PAD, int LGE, typename T>
+__device__ __forceinline__ void padfree_merge_stages(T* a, int np2, int nlive, T padv) {
+    sortnet::for_each_pass<LGE>(np2, [&](int r, int lt, bool mirror) {
+        if (!mirror)
+            padfree_pass<THREADS, PAD, LGE, false>(a, np2, nlive, r, padv);
+        else if (lt == 1)
+            padfree_pass<THREADS, PAD, 1, true>(a, np2, nlive, r, padv);
+        else if (lt == 2)
+            padfree_pass<THREADS, PAD, 2, true>(a, np2, nlive, r, padv);
+        else if (lt == 3 || LGE == 3)
+            padfree_pass<THREADS, PAD, 3, true>(a, np2, nlive, r, padv);
+        else if constexpr (LGE >= 4)
+            padfree_pass<THREADS, PAD, 4, true>(a, np2, nlive, r, padv);
+    });
+}
+
+// staged start: a[slot(j)] holds the keys for j < n and padv for n <= j < nlive
+template <int THREADS, bool PAD, int LGE, typename T>
+__device__ __forceinline__ void padfree_sort(T* a, int np2, int nlive, T padv) {
+    constexpr int E = 1 << LGE;
+    for (int g = threadIdx.x; g < (nlive >> LGE); g += THREADS) {
+        T e[E];
+#pragma unroll
+        for (int m = 0; m < E; ++m) e[m] = a[sort_slot<PAD>((g << LGE) + m)];
+        sortnet::run_store<LGE, PAD>(e, a, g, CxAsc{});
+    }
+    __syncthreads();
+    padfree_merge_stages<THREADS, PAD, LGE>(a, np2, nlive, padv);
+}
+
+// register start: the first nlive >> LGE threads hold one unsorted run each (sortnet::start_key), the others nothing
+template <int THREADS, bool PAD, int LGE, typename T>
+__device__ __forceinline__ void padfree_sort_regs(T (&e)[1 << LGE], T* a, int np2, int nlive, T padv) {
+    if ((int)threadIdx.x < (nlive >> LGE)) sortnet::run_store<LGE, PAD>(e, a, (int)threadIdx.x, CxAsc{});
+    __syncthreads();
+    padfree_merge_stages<THREADS, PAD, LGE>(a, np2, nlive, padv);
 }
 
 #include "scvod_k_patchwork.inc"  // Patchwork: classify / scatter / sort tiers / plane fit / arrange / ordered emission with the fused curved-voxel binning (A1-A4)
