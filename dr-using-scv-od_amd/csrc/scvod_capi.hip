@@ -205,6 +205,13 @@ struct scvod_ctx {
     unsigned long long* cs_counters = nullptr;
     hipStream_t cs_stream = nullptr;   // stream of the last scoring call (scvod_score_classes_stats waits for it; a growing block too)
     bool cs_ran = false;
+    // scan stacking (scvod_batch_stack_scans, scvod_stack.hip): the segment and tile tables, one grow-only block of their own allocated
+    // by the first call; not part of the arena
+    void* stk_buf = nullptr;
+    size_t stk_cap = 0;
+    hipStream_t stk_stream = nullptr;  // stream of the last stacking call (a growing block waits for it)
+    bool stk_ran = false;
+    std::vector<unsigned char> stk_host;  // the tables as built on the host (scratch of the call; the upload is staged from a copy)
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1467,6 +1474,7 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->ev_counters) hipFree(c->ev_counters);
     if (c->cs_buf) hipFree(c->cs_buf);
     if (c->cs_counters) hipFree(c->cs_counters);
+    if (c->stk_buf) hipFree(c->stk_buf);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
         if (b) hipFree(b);
@@ -3339,5 +3347,129 @@ int64_t scvod_score_classes_pass2_queries(scvod_ctx* c) {
 int64_t scvod_score_classes_scratch_bytes(scvod_ctx* c) {
     return c ? (int64_t)c->cs_cap + (c->cs_counters ? (int64_t)sizeof(unsigned long long) * 24 : 0) : 0;
 }
+
+// ---- scan stacking (scvod_stack.hip) ----
+int scvod_batch_stack_scans(scvod_ctx* c, const void* d_xyzi_in, const int32_t* h_in_offsets, int32_t n_in, const float* h_poses, int32_t window,
+                            int32_t interval, int32_t flags, const uint32_t* d_payload_in, void* d_xyzi_out, uint32_t* d_payload_out,
+                            int32_t* d_src_out, int64_t cap_points, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_in < 0 || cap_points < 0 || !h_in_offsets) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (h_in_offsets[0] < 0) return fail(c, SCVOD_ERR_INVALID, "scan offsets must not start below 0");
+    const int n_out = scvod_stack_offsets(h_in_offsets, n_in, window, interval, flags, nullptr, nullptr, 0, nullptr);
+    if (n_out == SCVOD_ERR_INVALID)
+        return fail(c, SCVOD_ERR_INVALID, "scvod_batch_stack_scans: window %d must be odd and 1..%d, interval %d >= 1, flags %d 0 or SCVOD_STACK_REFERENCE_BOUND, offsets ascending",
+                    window, SCVOD_STACK_MAX_WINDOW, interval, flags);
+    if (d_payload_out && !d_payload_in) return fail(c, SCVOD_ERR_INVALID, "a payload output needs a payload input");
+    if (((uintptr_t)d_xyzi_in & 15) || ((uintptr_t)d_xyzi_out & 15)) return fail(c, SCVOD_ERR_INVALID, "the xyzi arrays must be 16-byte aligned");
+    if (((uintptr_t)d_payload_in & 3) || ((uintptr_t)d_payload_out & 3) || ((uintptr_t)d_src_out & 3))
+        return fail(c, SCVOD_ERR_INVALID, "the payload and source index arrays must be 4-byte aligned");
+    if (n_out == 0) return SCVOD_OK;
+    if (!h_poses) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    // segments in output order: per group the middle scan, then the others ascending; tiles of the non-empty ones
+    const size_t n_seg = (size_t)n_out * (size_t)window;
+    long long need = 0;
+    size_t n_tiles = 0;
+    for (int g = 0; g < n_out; ++g) {
+        const long long pts = (long long)h_in_offsets[(size_t)g * interval + window] - (long long)h_in_offsets[(size_t)g * interval];
+        need += pts;
+        for (int k = 0; k < window; ++k) {
+            const size_t s = (size_t)g * interval + k;
+            n_tiles += (size_t)(((long long)h_in_offsets[s + 1] - h_in_offsets[s] + kStackTile - 1) / kStackTile);
+        }
+    }
+    if (need > 2147483647ll) return fail(c, SCVOD_ERR_CAPACITY, "%lld stacked points outgrow int32 offsets", need);
+    if (need > cap_points) return fail(c, SCVOD_ERR_CAPACITY, "%lld stacked points, the output holds %lld", need, (long long)cap_points);
+    if (need == 0) return SCVOD_OK;
+    if (n_tiles > 2147483647ull) return fail(c, SCVOD_ERR_CAPACITY, "too many tiles");
+    if (!d_xyzi_in || !d_xyzi_out) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    {  // an output range must not meet the range it is made from (the overlapping windows of interval < window read a scan repeatedly)
+        const long long lo = h_in_offsets[0], hi = h_in_offsets[n_in];
+        auto meets = [](const void* a, long long a_bytes, const void* b, long long b_bytes) {
+            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+            return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+        };
+        if (meets(d_xyzi_out, 16 * need, (const char*)d_xyzi_in + 16 * lo, 16 * (hi - lo)))
+            return fail(c, SCVOD_ERR_INVALID, "the xyzi output overlaps the xyzi input");
+        if (d_payload_out && meets(d_payload_out, 4 * need, (const char*)d_payload_in + 4 * lo, 4 * (hi - lo)))
+            return fail(c, SCVOD_ERR_INVALID, "the payload output overlaps the payload input");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t off_tiles = sizeof(StackSeg) * n_seg, bytes = off_tiles + sizeof(StackTile) * n_tiles;
+    c->stk_host.resize(bytes);
+    StackSeg* segs = (StackSeg*)c->stk_host.data();
+    StackTile* tiles = (StackTile*)(c->stk_host.data() + off_tiles);
+    size_t seg = 0, tile = 0;
+    long long out = 0;
+    for (int g = 0; g < n_out; ++g) {
+        const int first = g * interval, mid = first + window / 2;
+        for (int j = 0; j < window; ++j) {
+            // j = 0: the middle scan; then the scans of the window in ascending index, the middle one left out
+            const int k = j == 0 ? mid : (first + j - 1 < mid ? first + j - 1 : first + j);
+            StackSeg& S = segs[seg];
+            memset(&S, 0, sizeof(S));
+            S.in_base = h_in_offsets[k];
+            S.out_base = (int32_t)out;
+            S.n = h_in_offsets[k + 1] - h_in_offsets[k];
+            S.copy = k == mid ? 1 : 0;
+            if (!S.copy) scvod_pose_delta(h_poses + 6 * (size_t)k, h_poses + 6 * (size_t)mid, S.T);  // trans_mid^-1 * trans_k
+            for (int i = 0; i < S.n; i += kStackTile) tiles[tile++] = StackTile{(int32_t)seg, i};
+            out += S.n;
+            ++seg;
+        }
+    }
+    if (bytes > c->stk_cap) {  // (the old tables may still be read by a stacking call in flight)
+        if (c->stk_buf) {
+            if (c->stk_ran) HIPCHK(c, hipStreamSynchronize(c->stk_stream));
+            hipFree(c->stk_buf);
+            c->stk_buf = nullptr;
+            c->stk_cap = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->stk_buf, bytes + bytes / 4));
+        c->stk_cap = bytes + bytes / 4;
+    }
+    if (int rc = staged_upload(c, c->stk_host.data(), bytes, c->stk_buf, st)) return rc;
+    launch_stack((const StackSeg*)c->stk_buf, (const StackTile*)((const unsigned char*)c->stk_buf + off_tiles), (int)n_tiles,
+                 (const float4*)d_xyzi_in, (float4*)d_xyzi_out, d_payload_in, d_payload_out, d_src_out, st);
+    HIPCHK(c, hipGetLastError());
+    c->stk_stream = st;
+    c->stk_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_stack_scans(scvod_ctx* c, const float* h_xyzi_in, const int32_t* h_in_offsets, int32_t n_in, const float* h_poses, int32_t window,
+                      int32_t interval, int32_t flags, float* h_xyzi_out, int64_t cap_points) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_in < 0 || cap_points < 0 || !h_in_offsets) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (h_in_offsets[0] < 0) return fail(c, SCVOD_ERR_INVALID, "scan offsets must not start below 0");
+    int32_t largest = 0;
+    const int n_out = scvod_stack_offsets(h_in_offsets, n_in, window, interval, flags, nullptr, nullptr, 0, &largest);
+    if (n_out < 0) return fail(c, n_out, "scvod_stack_scans: bad window %d / interval %d / flags %d / offsets", window, interval, flags);
+    long long need = 0;
+    for (int g = 0; g < n_out; ++g) need += (long long)h_in_offsets[(size_t)g * interval + window] - (long long)h_in_offsets[(size_t)g * interval];
+    if (need > cap_points) return fail(c, SCVOD_ERR_CAPACITY, "%lld stacked points, the output holds %lld", need, (long long)cap_points);
+    if (need == 0) return SCVOD_OK;
+    if (!h_xyzi_in || !h_xyzi_out || !h_poses) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    const long long lo = h_in_offsets[0], n_pts = (long long)h_in_offsets[n_in] - lo;
+    std::vector<int32_t> off((size_t)n_in + 1);
+    for (int k = 0; k <= n_in; ++k) off[k] = h_in_offsets[k] - (int32_t)lo;
+    void *d_in = nullptr, *d_out = nullptr;
+    int rc = SCVOD_OK;
+    if (hipMalloc(&d_in, 16 * (size_t)n_pts) != hipSuccess || hipMalloc(&d_out, 16 * (size_t)need) != hipSuccess)
+        rc = fail(c, SCVOD_ERR_HIP, "scvod_stack_scans: no device memory for %lld + %lld points", n_pts, need);
+    if (rc == SCVOD_OK && hipMemcpyAsync(d_in, h_xyzi_in + 4 * lo, 16 * (size_t)n_pts, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        rc = fail(c, SCVOD_ERR_HIP, "scvod_stack_scans: upload failed");
+    if (rc == SCVOD_OK)
+        rc = scvod_batch_stack_scans(c, d_in, off.data(), n_in, h_poses, window, interval, flags, nullptr, d_out, nullptr, nullptr, need, c->stream);
+    if (rc == SCVOD_OK && hipMemcpyAsync(h_xyzi_out, d_out, 16 * (size_t)need, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = fail(c, SCVOD_ERR_HIP, "scvod_stack_scans: download failed");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == SCVOD_OK) rc = fail(c, SCVOD_ERR_HIP, "scvod_stack_scans: the stream failed");
+    if (d_in) hipFree(d_in);
+    if (d_out) hipFree(d_out);
+    return rc;
+}
+
+int64_t scvod_stack_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)c->stk_cap : 0; }
 
 }  // extern "C"

@@ -306,6 +306,25 @@ void launch_point_labels(const Arena& A, uint8_t* labels, int use_dyn, hipStream
 void launch_point_classes(const Arena& A, const uint8_t* cls, uint8_t* labels, int use_dyn, hipStream_t st);
 void launch_export(const Arena& A, const ExportJob& J, hipStream_t st);
 
+// scan stacking (scvod_batch_stack_scans; scvod_stack.hip): every (group, scan of its window) pair is a SEGMENT -- a contiguous run of
+// input records that goes to a contiguous run of output records with one 3x4 matrix, or with none for the middle scan.  The host cuts
+// the non-empty segments into tiles of kStackTile points (256 threads x 8 rounds, as the export's) and lists them: a workgroup owns one
+// tile, so everything but the point itself is uniform over the workgroup.  Both tables live in scratch of their own (not the arena).
+constexpr int kStackTile = 2048;
+struct StackSeg {       // 64 bytes
+    float T[12];        // row-major 3x4 (unused when copy != 0)
+    int32_t in_base;    // first input record
+    int32_t out_base;   // first output record
+    int32_t n;          // records
+    int32_t copy;       // 1: the middle scan, records handed on bit for bit
+};
+struct StackTile {
+    int32_t seg;        // index into the segment table
+    int32_t first;      // first record of the tile inside its segment (a multiple of kStackTile)
+};
+void launch_stack(const StackSeg* segs, const StackTile* tiles, int n_tiles, const float4* in, float4* out, const uint32_t* payload_in,
+                  uint32_t* payload_out, int32_t* src_out, hipStream_t st);
+
 // the clusters of a batch as an object table (scvod_batch_objects; scvod_objects.hip).  Tiles as in the export, over the APRI points of a
 // scan; per tile two words {objects, member points}, the first turned into its exclusive prefix inside the scan.  Scratch of its own (not
 // the arena): per point of the ctx's capacity unless stated.

@@ -2,6 +2,7 @@
 // KITTI-layout sequence named by the YAML file's session/ keys (data_path_, label_path_, pose_path_, start_, end_) and
 // common/skip_.  Writes, per loaded frame, the points of the clusters that ended up dynamic (state == 1).
 //   usage: scvod_sequence <config.yaml> <out_dir> [--data DIR] [--labels DIR] [--poses FILE] [--start S] [--end E] [--skip K]
+//                         [--stack-window W --stack-interval I]   (the reference's scan stacker in front of the path: makeScan.cpp is 3 / 3)
 //          scvod_sequence --poses-only <config.yaml> [--poses FILE] [--start S] [--end E] [--skip K]   (no GPU needed)
 #include <cstdio>
 #include <cstring>
@@ -47,6 +48,8 @@ static void overrides(Utility& u, int argc, char** argv, int from) {
         else if (k == "--start") u.start = std::atoi(v.c_str());
         else if (k == "--end") u.end = std::atoi(v.c_str());
         else if (k == "--skip") u.skip = std::atoi(v.c_str());
+        else if (k == "--stack-window") u.stack_window = std::atoi(v.c_str());
+        else if (k == "--stack-interval") u.stack_interval = std::atoi(v.c_str());
         else throw std::invalid_argument("unknown option " + k);
     }
 }
@@ -71,7 +74,8 @@ int main(int argc, char** argv) {
             return 0;
         }
         if (argc < 3) {
-            std::cerr << "usage: scvod_sequence <config.yaml> <out_dir> [--data DIR] [--labels DIR] [--poses FILE] [--start S] [--end E] [--skip K]\n";
+            std::cerr << "usage: scvod_sequence <config.yaml> <out_dir> [--data DIR] [--labels DIR] [--poses FILE] [--start S] [--end E] [--skip K]"
+                         " [--stack-window W --stack-interval I]\n";
             return 2;
         }
         const std::string out = argv[2];

@@ -401,6 +401,46 @@ void SSC::getCloud() {
     }
 }
 
+// src/makeScan.cpp:153-244 on what the loaders left: cloud_vec -> one host array, scvod_stack_scans (upload, the device stage, download),
+// the stacked clouds back into cloud_vec; pose_vec / trans_vec keep the middle scans' entries (makeScan.cpp:177-184 hands on rpy2 / trans2)
+void SSC::stackScans() {
+    if (pose_vec.size() < cloud_vec.size())
+        throw std::runtime_error("SSC::stackScans: " + std::to_string(pose_vec.size()) + " poses for " + std::to_string(cloud_vec.size()) + " scans");
+    const int n_in = (int)cloud_vec.size();
+    std::vector<int32_t> off(n_in + 1, 0);
+    for (int k = 0; k < n_in; ++k) off[k + 1] = off[k] + (int32_t)cloud_vec[k]->points.size();
+    std::vector<float> in(4 * (size_t)off[n_in]), poses(6 * (size_t)n_in);
+    for (int k = 0; k < n_in; ++k) {
+        if (!cloud_vec[k]->points.empty()) std::memcpy(in.data() + 4 * (size_t)off[k], cloud_vec[k]->points.data(), 16 * cloud_vec[k]->points.size());
+        const Pose& p = pose_vec[k];
+        const float v[6] = {p.x, p.y, p.z, p.roll, p.pitch, p.yaw};
+        std::memcpy(poses.data() + 6 * (size_t)k, v, sizeof(v));
+    }
+    const int n_out = scvod_stack_offsets(off.data(), n_in, stack_window, stack_interval, 0, nullptr, nullptr, 0, nullptr);
+    if (n_out < 0) throw std::invalid_argument("session/stack_window_ must be odd and 1..9, session/stack_interval_ at least 1");
+    std::vector<int32_t> out_off(n_out + 1, 0), mid(n_out > 0 ? n_out : 1, 0);
+    if (scvod_stack_offsets(off.data(), n_in, stack_window, stack_interval, 0, out_off.data(), mid.data(), n_out, nullptr) != n_out)
+        throw std::runtime_error("scvod_stack_offsets failed");
+    std::vector<float> out(4 * (size_t)out_off[n_out]);
+    chk(ctx_, scvod_stack_scans(ctx_, in.data(), off.data(), n_in, poses.data(), stack_window, stack_interval, 0, out.data(), out_off[n_out]),
+        "scvod_stack_scans");
+    std::vector<pcl::PointCloud<pcl::PointXYZI>::Ptr> clouds;
+    std::vector<Pose> mid_pose;
+    std::vector<std::vector<float>> mid_trans;
+    for (int g = 0; g < n_out; ++g) {
+        pcl::PointCloud<pcl::PointXYZI>::Ptr c(new pcl::PointCloud<pcl::PointXYZI>());
+        c->points.resize((size_t)(out_off[g + 1] - out_off[g]));
+        if (!c->points.empty()) std::memcpy((void*)c->points.data(), out.data() + 4 * (size_t)out_off[g], 16 * c->points.size());
+        c->width = (unsigned)c->points.size();
+        clouds.emplace_back(c);
+        mid_pose.emplace_back(pose_vec[mid[g]]);
+        if ((size_t)mid[g] < trans_vec.size()) mid_trans.emplace_back(trans_vec[mid[g]]);
+    }
+    cloud_vec.swap(clouds);
+    pose_vec.swap(mid_pose);
+    trans_vec.swap(mid_trans);
+}
+
 // SSC::segDF (ssc.cpp:1428-1452): load, per scan process -> segment -> recognize -> keep the frame, then the tracking
 // chain.  segment() / recognize() are the GPU stand-in segmentGpu() here (curved-voxel clustering + box rules); a build
 // that links the reference's PCL host code calls its own segment() / recognize() instead.
@@ -408,6 +448,7 @@ void SSC::segDF() {
     id = start;
     getPose();
     getCloud();
+    if (stack_window != 1 || stack_interval != 1) stackScans();  // (only with the keys: session/stack_window_ / session/stack_interval_)
     for (auto& cloud : cloud_vec) {
         process(cloud);
         segmentGpu();

@@ -50,6 +50,10 @@ class SSC : public Utility {
     void getPose();
     void getCloud();
     void segDF();
+    // The reference's scan stacker (src/makeScan.cpp:153-244) between the loaders and the per-scan loop, on the device: with the
+    // facade-only keys session/stack_window_ / session/stack_interval_ other than 1 / 1, segDF replaces cloud_vec by the stacked clouds
+    // (every window's scans in the frame of its middle scan) and pose_vec / trans_vec by the middle scans' entries.
+    void stackScans();
     // GPU stand-in for segment() + recognize() when the reference's PCL host code is not linked: curved-voxel
     // clustering (ssc.cpp:299-393) + bounding-box refine / recognise rules (ssc.cpp:437-467, 849-872);
     // the intensity merge and the region growing of recognize (building / tree) run on the device when the facade-only keys

@@ -68,6 +68,9 @@ class Utility {
     int skip = 2;
     std::string data_path, label_path, pose_path;
     int init = 5, start = 5, end = 50;
+    // facade-only keys session/stack_window_ / session/stack_interval_: the reference's scan stacker (src/makeScan.cpp: window 3, interval 3)
+    // run on the device between the loaders and the per-scan loop of segDF; 1 / 1 is off and nothing is called
+    int stack_window = 1, stack_interval = 1;
     float sensor_height = 2.0f, min_dis = 0.0f, max_dis = 50.0f, min_angle = 0.0f, max_angle = 360.0f,
           min_azimuth = -30.0f, max_azimuth = 60.0f, range_res = 0.2f, sector_res = 1.2f, azimuth_res = 2.0f,
           refine_height = -1.0f, max_z = 1.0f, min_z = -1.0f, car_angle = 120.0f, car_height = 2.0f, car_square = 2.0f;
@@ -293,6 +296,8 @@ class Utility {
         y.param<int>("session/init_", init, 5);
         y.param<int>("session/start_", start, 5);
         y.param<int>("session/end_", end, 50);
+        y.param<int>("session/stack_window_", stack_window, 1);
+        y.param<int>("session/stack_interval_", stack_interval, 1);
         y.param<float>("ssc/sensor_height_", sensor_height, 2.0f);
         y.param<float>("ssc/min_dis_", min_dis, 0.0f);
         y.param<float>("ssc/max_dis_", max_dis, 50.0f);

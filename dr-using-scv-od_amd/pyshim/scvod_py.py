@@ -272,6 +272,11 @@ def load_lib():
         "scvod_score_classes_scratch_bytes": (i64, [vp]),
         "scvod_batch_voxelgrid": (C.c_int, [vp, vp, vp, vp, i32, vp, f32, vp, i64, vp, vp]),
         "scvod_voxelgrid": (C.c_int, [vp, vp, vp, i32, vp, f32, vp, i32, vp]),
+        "scvod_stack_offsets": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp]),
+        "scvod_pose_from_matrix": (None, [vp, vp]),
+        "scvod_batch_stack_scans": (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+        "scvod_stack_scans": (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, vp, i64]),
+        "scvod_stack_scratch_bytes": (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # raises AttributeError if a declared symbol is not exported
@@ -298,7 +303,9 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_evaluate_scratch_bytes", "scvod_classify_map_device", "scvod_classify_map_stats",
                     "scvod_batch_point_classes", "scvod_class_params_default", "scvod_class_finish", "scvod_score_classes_device",
                     "scvod_batch_score_classes", "scvod_score_classes_stats", "scvod_score_classes_pass2_queries",
-                    "scvod_score_classes_scratch_bytes"]
+                    "scvod_score_classes_scratch_bytes",
+                    "scvod_stack_offsets", "scvod_pose_from_matrix", "scvod_batch_stack_scans", "scvod_stack_scans",
+                    "scvod_stack_scratch_bytes"]
 
 
 def eval_params_default(voxelsize=None, dynamic_classes=None):
@@ -1028,6 +1035,48 @@ class Ctx:
         self._chk(self.lib.scvod_classify_map_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return dict(zip(("unmatched", "tp_static", "fn_static", "tn_dynamic", "fn_dynamic"), (int(v) for v in out)))
 
+    # ---- scan stacking (include/scvod.h: scvod_batch_stack_scans) ----
+    def batch_stack_scans(self, d_xyzi_in, offsets, poses, d_xyzi_out, window=3, interval=3, reference_bound=False, d_payload_in=None,
+                          d_payload_out=None, d_src_out=None, stream=None):
+        """every `window` consecutive scans (a group every `interval` scans) stacked into the frame of the group's middle scan: the
+        middle scan first, bit for bit, then the others in ascending scan index, moved by pose_delta(pose_k, pose_mid).  d_xyzi_in /
+        d_xyzi_out: torch float32 device tensors [*, 4]; offsets [n_in + 1] and poses [n_in, 6] host arrays (copied before the call
+        returns); d_payload_* uint32-sized words per point (int32 tensors do), d_src_out int32 per output point.  Asynchronous on
+        `stream`, no host synchronisation, the last batch stays valid.  Returns (out_offsets, mid) as stack_offsets does"""
+        off = np.ascontiguousarray(offsets, np.int32)
+        n_in = off.shape[0] - 1
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p.shape[0] == n_in
+        out_offsets, mid = stack_offsets(off, window, interval, reference_bound)
+        assert d_xyzi_out.numel() % 4 == 0
+        cap = d_xyzi_out.numel() // 4
+        for t in (d_src_out, d_payload_out):
+            assert t is None or t.numel() >= min(cap, int(out_offsets[-1]))
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.scvod_batch_stack_scans(self.h, ptr(d_xyzi_in), off.ctypes.data_as(C.c_void_p), n_in,
+                                                   p.ctypes.data_as(C.c_void_p), int(window), int(interval),
+                                                   STACK_REFERENCE_BOUND if reference_bound else 0, ptr(d_payload_in), ptr(d_xyzi_out),
+                                                   ptr(d_payload_out), ptr(d_src_out), int(cap), C.c_void_p(stream or 0)))
+        return out_offsets, mid
+
+    def stack_scans(self, xyzi, offsets, poses, window=3, interval=3, reference_bound=False):
+        """the same for scans in host memory (upload, stack, download; synchronous).  Returns (stacked xyzi, out_offsets, mid)"""
+        x, px = self._f32(xyzi)
+        off = np.ascontiguousarray(offsets, np.int32)
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        out_offsets, mid = stack_offsets(off, window, interval, reference_bound)
+        out = np.zeros((max(int(out_offsets[-1]), 1), 4), np.float32)
+        self._chk(self.lib.scvod_stack_scans(self.h, px, off.ctypes.data_as(C.c_void_p), off.shape[0] - 1, p.ctypes.data_as(C.c_void_p),
+                                             int(window), int(interval), STACK_REFERENCE_BOUND if reference_bound else 0,
+                                             out.ctypes.data_as(C.c_void_p), int(out_offsets[-1])))
+        return out[:int(out_offsets[-1])], out_offsets, mid
+
+    def stack_scratch_bytes(self):
+        """device scratch the stacking holds on this ctx (0 before the first batch_stack_scans)"""
+        return int(self.lib.scvod_stack_scratch_bytes(self.h))
+
     def voxelgrid(self, xyzi, leaf=(0.08, 0.08, 0.08), labels=None, max_intensity=1.0):
         """SSC::getCloud label filter + pcl::VoxelGrid of one host scan (ssc.cpp:1063-1076, 1103-1106)."""
         x, px = self._f32(xyzi)
@@ -1169,3 +1218,34 @@ def pose_matrix(pose):
     t = np.zeros(12, np.float32)
     load_lib().scvod_pose_matrix(p.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p))
     return t
+
+
+STACK_REFERENCE_BOUND = 1  # SCVOD_STACK_REFERENCE_BOUND
+
+
+def stack_offsets(offsets, window=3, interval=3, reference_bound=False):
+    """(out_offsets [n_out + 1], mid [n_out]) of the scan stacking (scvod_stack_offsets; host only): group g holds the scans
+    g * interval .. g * interval + window - 1 and hands on the pose of scan mid[g].  reference_bound: the loop bound of the
+    reference's stacker, which drops the last complete group when the scan count is a multiple of interval"""
+    lib = load_lib()
+    off = np.ascontiguousarray(offsets, np.int32)
+    n_in = off.shape[0] - 1
+    flags = STACK_REFERENCE_BOUND if reference_bound else 0
+    n_out = lib.scvod_stack_offsets(off.ctypes.data_as(C.c_void_p), n_in, int(window), int(interval), flags, None, None, 0, None)
+    if n_out < 0:
+        raise ScvodError(f"scvod_stack_offsets: status {n_out} (window {window}, interval {interval})")
+    out = np.zeros(n_out + 1, np.int32)
+    mid = np.zeros(n_out, np.int32)
+    rc = lib.scvod_stack_offsets(off.ctypes.data_as(C.c_void_p), n_in, int(window), int(interval), flags, out.ctypes.data_as(C.c_void_p),
+                                 mid.ctypes.data_as(C.c_void_p), n_out, None)
+    if rc != n_out:
+        raise ScvodError(f"scvod_stack_offsets: status {rc}")
+    return out, mid
+
+
+def pose_from_matrix(M):
+    """{x, y, z, roll, pitch, yaw} of a row-major 3x4 (or 12-vector) pose matrix (scvod_pose_from_matrix; host only)"""
+    m = np.ascontiguousarray(M, np.float32).reshape(12)
+    out = np.zeros(6, np.float32)
+    load_lib().scvod_pose_from_matrix(m.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    return out

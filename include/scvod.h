@@ -897,6 +897,61 @@ int64_t scvod_score_classes_pass2_queries(scvod_ctx* ctx);
 /* bytes of device scratch the class scores hold on this ctx (0 before the first call) */
 int64_t scvod_score_classes_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- scan stacking: neighbouring scans moved into the middle scan's frame, on the device (opt-in: nothing runs or is allocated
+ * unless it is called) -------------------------------------------------------------------------------------------------------------
+ * Reference analogue: src/makeScan.cpp:153-244, the stacker in front of the path for sparse, non-repetitive sensors.  Output scan
+ * ("group") g is built from the `window` consecutive input scans g * interval .. g * interval + window - 1: the MIDDLE scan
+ * mid = g * interval + window / 2 first, its records bit for bit (the reference never transforms cloud2), then the other scans of the
+ * window in ascending scan index, each in input order, each point moved by T = scvod_pose_delta(pose_k, pose_mid) (trans_mid^-1 *
+ * trans_k, makeScan.cpp:187-188) with T0*x + T1*y + T2*z + T3 per row, evaluated left to right in fp32 without contraction (the map
+ * kernel's expression; makeScan.cpp:83-85); the intensity word is copied bit for bit.  The group hands on the middle scan's pose.
+ * Group g exists iff g * interval + window <= n_in; with SCVOD_STACK_REFERENCE_BOUND also g * interval < n_in - interval, the loop
+ * bound of makeScan.cpp:156 (`i < size - interval`), which drops the last complete group when n_in is a multiple of interval.
+ * n_in < window gives no group (the reference's unsigned underflow there is not modelled).  window is odd, 1..9 (the reference: 3);
+ * interval >= 1 (the reference: 3); interval < window stacks overlapping windows. */
+#define SCVOD_STACK_REFERENCE_BOUND 1
+#define SCVOD_STACK_MAX_WINDOW 9
+/* Host only, no device.  Returns the number of groups n_out, or a negative status.  h_in_offsets [n_in + 1] point offsets of the input
+ * scans (may be NULL when neither h_out_offsets nor largest_scan is asked for); h_out_offsets [n_out + 1] the point offsets of the
+ * stacked scans; h_mid [n_out] the middle scan of every group; *largest_scan the largest stacked scan (to be checked against
+ * SCVOD_MAX_SCAN_POINTS before scvod_batch_process).  Any of the three may be NULL: count only.  cap_out: the groups h_out_offsets
+ * (cap_out + 1 words) and h_mid hold -- SCVOD_ERR_CAPACITY when a non-NULL array is too small, and when the stacked points outgrow
+ * int32 offsets.  SCVOD_ERR_INVALID for a window that is even or outside 1..9, interval < 1, an unknown flag bit, n_in < 0 or
+ * offsets that decrease. */
+int scvod_stack_offsets(const int32_t* h_in_offsets, int32_t n_in, int32_t window, int32_t interval, int32_t flags,
+                        int32_t* h_out_offsets, int32_t* h_mid, int32_t cap_out, int32_t* largest_scan);
+/* Host only.  Row-major 3x4 in, {x, y, z, roll, pitch, yaw} out: rotationMatrixToEulerAngles of makeScan.cpp:57-74 with the float
+ * overloads of sqrt / atan2 (sy < 1e-6, compared in double, takes the singular branch: yaw 0) and the translation column, as
+ * makeScan.cpp:164-183 fills the pose it hands on.  scvod_pose_matrix of the result is the matrix the reference stacks with. */
+void scvod_pose_from_matrix(const float M[12], float pose_out[6]);
+/* The stacking on scans resident in HBM.  d_xyzi_in: all input scans concatenated (h_in_offsets [n_in + 1], starting anywhere:
+ * point index h_in_offsets[k] + i is record h_in_offsets[k] + i of d_xyzi_in); h_poses [n_in][6].  Outputs, all in the order above:
+ *   d_xyzi_out     [cap_points] packed float4 records
+ *   d_payload_out  [cap_points] or NULL: one uint32 per point (e.g. SemanticKITTI labels for the evaluation calls) carried along from
+ *   d_payload_in   [input points] or NULL
+ *   d_src_out      [cap_points] or NULL: the input index h_in_offsets[k] + i of every output point
+ * Stream-ordered (stream NULL = the ctx's stream), never synchronises with the host.  h_in_offsets and h_poses are turned into matrices
+ * and a segment / tile table and staged before the call returns: the arrays are the caller's again at once (a later call with other
+ * values waits for the staging copy in flight only when it needs the same staging slot again).  The stacking calls of one ctx must be
+ * ordered among themselves (they share the table's device copy).  Unlike scvod_batch_voxelgrid the call does NOT invalidate the results
+ * of the last batch: it touches neither the arena nor any batch state.  Scratch (64 bytes per segment, 8 bytes per 2048-point tile) is a
+ * grow-only allocation of its own, freed by scvod_destroy, NOT part of scvod_arena_bytes, and does not exist before the first call.
+ * Refused before anything is launched: SCVOD_ERR_INVALID for a bad window / interval / flag bit, offsets that decrease or start below
+ * 0, a NULL array that is needed, a pointer that is not 16-byte (xyzi) or 4-byte (payload, src) aligned, d_payload_out without
+ * d_payload_in, and an output range that overlaps its input range; SCVOD_ERR_CAPACITY when the stacked points exceed cap_points (the
+ * host knows the size from the offsets: nothing is ever written at or behind the capacity).  No group (n_out == 0) is success and
+ * launches nothing.  The sizes are scvod_stack_offsets' with the same arguments. */
+int scvod_batch_stack_scans(scvod_ctx* ctx, const void* d_xyzi_in, const int32_t* h_in_offsets, int32_t n_in, const float* h_poses,
+                            int32_t window, int32_t interval, int32_t flags, const uint32_t* d_payload_in, void* d_xyzi_out,
+                            uint32_t* d_payload_out, int32_t* d_src_out, int64_t cap_points, void* stream);
+/* The same for scans in host memory (what the C++ facade calls: it links this library only): the clouds are uploaded, stacked on the
+ * device and downloaded into h_xyzi_out [cap_points]; h_xyzi_in holds the scans' records at their offsets.  Synchronous.  The device
+ * buffers live for the duration of the call. */
+int scvod_stack_scans(scvod_ctx* ctx, const float* h_xyzi_in, const int32_t* h_in_offsets, int32_t n_in, const float* h_poses,
+                      int32_t window, int32_t interval, int32_t flags, float* h_xyzi_out, int64_t cap_points);
+/* bytes of device scratch the stacking holds on this ctx (0 before the first call) */
+int64_t scvod_stack_scratch_bytes(scvod_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
