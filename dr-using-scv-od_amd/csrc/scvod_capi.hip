@@ -1283,6 +1283,8 @@ extern "C" int scvod__ctx_view(scvod_ctx* c, Arena* arena, int* device, int* tra
     *max_scan_pts = c->A.max_scan_pts;
     return 0;
 }
+// the stream a stream-ordered batch call runs on: the caller's, or (NULL) the stream of the ctx's last batch call
+extern "C" void* scvod__ctx_stream(scvod_ctx* c, void* stream) { return stream ? stream : (void*)(c->last_stream ? c->last_stream : c->stream); }
 
 extern "C" {
 

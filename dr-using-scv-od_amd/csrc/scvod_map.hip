@@ -11,9 +11,15 @@
 // Insertion is one 64-bit atomicMin per point on an open-addressing table in HBM (linear probing, 16-byte records), so
 // accumulating scans in any order, on any number of shards, and merging the shards' record lists (scvod_map_merge, the
 // payload of the RCCL all_gather) gives bit-identical maps.
+//
+// A map of kind SCVOD_MAP_KIND_LABELLED is the same table with another packing of the value: the low 16 bits hold
+// {label, intensity}, 8 bits each, instead of the 16-bit intensity -- `instance_map` in the colour of the recognised class
+// (ssc.cpp:501-554).  The label is the representative point's OWN byte: the smallest (offset, label, intensity) wins, so the
+// leading 48 bits, hence the point's xyz, are the plain map's for the same kept set.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -25,7 +31,7 @@ using namespace scvod;
 
 struct MapRec {
     unsigned long long key;  // ~0 = empty
-    unsigned long long val;  // packed {qx, qy, qz, qi}, 16 bits each, smallest wins
+    unsigned long long val;  // packed {qx, qy, qz, qi}, 16 bits each, smallest wins (labelled kind: {qx, qy, qz} 16 bits each, label 8, qi 8)
 };
 static_assert(sizeof(MapRec) == 16, "map record");
 
@@ -38,6 +44,13 @@ struct scvod_map {
     float* d_pose = nullptr;                 // [pose_cap][12]
     long long pose_cap = 0;
     std::vector<float> up_pose;
+    int kind = SCVOD_MAP_KIND_PLAIN;
+    // labelled kind only: scan offsets of the ctx-free accumulate (staged like the poses) and the class bytes of the batch form
+    int32_t* d_offs = nullptr;  // [offs_cap]
+    long long offs_cap = 0;
+    std::vector<int32_t> up_offs;
+    uint8_t* d_cls = nullptr;  // [cls_cap] one byte per input point of the largest batch seen (grow-only)
+    long long cls_cap = 0;
     std::string err;
 };
 
@@ -243,6 +256,76 @@ __global__ __launch_bounds__(256) void k_map_mark_lists(Arena A) {
     }
 }
 
+// is `label` set in the 256-bit table k0..k3?  The four words are kernel arguments: they live in scalar registers
+__device__ __forceinline__ bool map_bit256(unsigned long long k0, unsigned long long k1, unsigned long long k2, unsigned long long k3,
+                                           unsigned int label) {
+    const unsigned long long lo = (label & 64u) ? k1 : k0, hi = (label & 64u) ? k3 : k2;
+    return (((label & 128u) ? hi : lo) >> (label & 63u)) & 1ull;
+}
+
+// the labelled kind's value: map_encode's three offsets, then the caller's byte, then (int)clamp(intensity, 0, 255)
+__device__ __forceinline__ unsigned long long map_val_labelled(unsigned long long plain_val, unsigned int label, float intensity) {
+    float in = intensity;
+    in = in < 0.f ? 0.f : (in > 255.f ? 255.f : in);
+    return (plain_val & ~0xffffull) | ((unsigned long long)label << 8) | (unsigned long long)(int)in;
+}
+
+// k_map_accumulate for a caller's own cloud and label bytes (no batch context): scan blockIdx.y + s_first is the points
+// [scan_off[s], scan_off[s + 1]) of `pts`, the point at scan_off[s] + i carries labels[scan_off[s] + i] and is kept iff that byte is
+// set in the table k0..k3.  Same streaming (input order, 16-byte non-temporal loads, one byte beside each), same pose expression, same
+// wave-level reduction of runs of equal keys -- a dropped point has key kEmpty and splits a run -- and the same insertion; the value
+// is the labelled kind's.  One point per thread and round, kMapPts points per workgroup: k_map_accumulate's measured choices.
+__global__ __launch_bounds__(256) void k_map_accumulate_labelled(int s_first, const float4* __restrict__ pts, const uint8_t* __restrict__ labels,
+                                                                 const int32_t* __restrict__ scan_off, const float* __restrict__ pose, MapRec* table,
+                                                                 unsigned long long mask, float inv_leaf, unsigned long long k0, unsigned long long k1,
+                                                                 unsigned long long k2, unsigned long long k3, unsigned long long* counters) {
+    const int s = s_first + blockIdx.y;
+    const int base = scan_off[s];
+    const int n = scan_off[s + 1] - base;
+    const int lane = threadIdx.x & 63;
+    float T[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = pose[12 * s + i];
+    int dropped = 0;
+    for (int i0 = blockIdx.x * 256; i0 < n; i0 += gridDim.x * 256) {
+        const int i = i0 + (int)threadIdx.x;
+        const size_t at = (size_t)base + (size_t)min(i, n - 1);
+        // the scan is read once: non-temporal loads keep it out of the way of the table's sectors in L2
+        const unsigned int label = __builtin_nontemporal_load(&labels[at]);
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v q = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(&pts[at]));
+        unsigned long long key = kEmpty, val = kEmpty;
+        if (i < n && map_bit256(k0, k1, k2, k3, label)) {
+            const float x = T[0] * q.x + T[1] * q.y + T[2] * q.z + T[3];
+            const float y = T[4] * q.x + T[5] * q.y + T[6] * q.z + T[7];
+            const float z = T[8] * q.x + T[9] * q.y + T[10] * q.z + T[11];
+            if (map_encode(x, y, z, q.w, inv_leaf, key, val)) {
+                val = map_val_labelled(val, label, q.w);
+            } else {
+                ++dropped;
+                key = kEmpty;
+                val = kEmpty;
+            }
+        }
+        // runs of equal keys among consecutive lanes: the head of a run takes the smallest value of the run
+        const unsigned long long prev = __shfl_up(key, 1);
+        const bool head = (lane == 0) || (prev != key);
+        const unsigned long long heads = __ballot(head);
+        const unsigned long long after = heads & ~((2ull << lane) - 1ull);
+        const int run_end = after ? (__ffsll((long long)after) - 1) : 64;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long o = __shfl_down(val, d);
+            if (lane + d < run_end && o < val) val = o;
+        }
+        const bool need = head && key != kEmpty;
+        const unsigned long long h = map_home(key, mask);
+        const MapRec first = map_peek(table, need ? h : 0ull);
+        if (need && !map_insert_from(table, mask, key, val, h, first)) ++dropped;
+    }
+    if (dropped) atomicAdd(&counters[1], (unsigned long long)dropped);
+}
+
 __global__ __launch_bounds__(256) void k_map_merge(const MapRec* __restrict__ recs, long long n, MapRec* table, unsigned long long mask,
                                                    unsigned long long* counters) {
     int dropped = 0;
@@ -254,9 +337,13 @@ __global__ __launch_bounds__(256) void k_map_merge(const MapRec* __restrict__ re
     if (dropped) atomicAdd(&counters[1], (unsigned long long)dropped);
 }
 
-// occupied records -> dense list (order = whatever the atomics give: consumers that need a canonical order sort by key)
+// occupied records -> dense list (order = whatever the atomics give: consumers that need a canonical order sort by key).
+// LABELLED: the value is the labelled kind's -- the intensity is its low 8 bits, the label byte goes to out_label, and only the cells
+// whose label is set in the table k0..k3 are listed (and counted).  The plain instantiation is the kernel as it always was.
+template <bool LABELLED>
 __global__ __launch_bounds__(256) void k_map_export(const MapRec* __restrict__ table, long long capacity, MapRec* out, long long cap_out,
-                                                    float4* out_xyzi, float leaf, unsigned long long* counters) {
+                                                    float4* out_xyzi, float leaf, unsigned long long* counters, uint8_t* out_label,
+                                                    unsigned long long k0, unsigned long long k1, unsigned long long k2, unsigned long long k3) {
     __shared__ unsigned int cnt;
     __shared__ unsigned long long gstart;
     constexpr int IT = 8;  // slots per thread and round: one reservation on the shared counter per 2048 slots, not per wave
@@ -279,7 +366,8 @@ __global__ __launch_bounds__(256) void k_map_export(const MapRec* __restrict__ t
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
-            const bool occ = r[it].key != kEmpty;
+            bool occ = r[it].key != kEmpty;
+            if (LABELLED) occ = occ && map_bit256(k0, k1, k2, k3, (unsigned int)(r[it].val >> 8) & 0xffu);
             const unsigned long long bal = __ballot(occ);
             unsigned int wbase = 0;
             if (lane == 0 && bal) wbase = atomicAdd(&cnt, (unsigned int)__popcll(bal));
@@ -301,8 +389,10 @@ __global__ __launch_bounds__(256) void k_map_export(const MapRec* __restrict__ t
                           cz = (int)(q.key & ((1u << kCellBits) - 1u)) - kCellBias;
                 const float qx = (float)((q.val >> 48) & 0xffffu), qy = (float)((q.val >> 32) & 0xffffu), qz = (float)((q.val >> 16) & 0xffffu);
                 out_xyzi[o] = make_float4(((float)cx + (qx + 0.5f) / 65536.0f) * leaf, ((float)cy + (qy + 0.5f) / 65536.0f) * leaf,
-                                          ((float)cz + (qz + 0.5f) / 65536.0f) * leaf, (float)(q.val & 0xffffu) / 256.0f);
+                                          ((float)cz + (qz + 0.5f) / 65536.0f) * leaf,
+                                          LABELLED ? (float)(q.val & 0xffu) : (float)(q.val & 0xffffu) / 256.0f);
             }
+            if (LABELLED && out_label) out_label[o] = (uint8_t)((q.val >> 8) & 0xffu);
         }
         __syncthreads();
     }
@@ -430,17 +520,24 @@ struct scvod_ctx;
 extern "C" int scvod__ctx_types_valid(scvod_ctx* c);
 extern "C" int scvod__ctx_view(scvod_ctx* ctx, Arena* arena, int* device, int* track_valid, int* batch_valid, int* n_scans,
                                int* max_scan_pts, int* batch_mode, int* num_min_pts);
+extern "C" void* scvod__ctx_stream(scvod_ctx* ctx, void* stream);
 
 extern "C" {
 
 int scvod_map_create(int device, int64_t capacity_cells, float leaf, scvod_map** out) {
+    return scvod_map_create_kind(device, capacity_cells, leaf, SCVOD_MAP_KIND_PLAIN, out);
+}
+
+int scvod_map_create_kind(int device, int64_t capacity_cells, float leaf, int32_t kind, scvod_map** out) {
     if (!out || capacity_cells < 1024 || !(leaf > 0.f)) return SCVOD_ERR_INVALID;
     *out = nullptr;
+    if (kind != SCVOD_MAP_KIND_PLAIN && kind != SCVOD_MAP_KIND_LABELLED) return SCVOD_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SCVOD_ERR_NO_DEVICE;
     scvod_map* m = new scvod_map();
     m->device = device;
     m->leaf = leaf;
+    m->kind = kind;
     long long cap = 1024;
     while (cap < capacity_cells) cap <<= 1;
     m->capacity = cap;
@@ -463,9 +560,13 @@ void scvod_map_destroy(scvod_map* m) {
     if (m->table) hipFree(m->table);
     if (m->counters) hipFree(m->counters);
     if (m->d_pose) hipFree(m->d_pose);
+    if (m->d_offs) hipFree(m->d_offs);
+    if (m->d_cls) hipFree(m->d_cls);
     delete m;
 }
 
+int32_t scvod_map_kind(const scvod_map* m) { return m ? m->kind : SCVOD_ERR_INVALID; }
+int64_t scvod_map_scratch_bytes(const scvod_map* m) { return m ? (int64_t)m->cls_cap : 0; }
 const char* scvod_map_last_error(const scvod_map* m) { return m ? m->err.c_str() : "null map"; }
 int64_t scvod_map_capacity(const scvod_map* m) { return m ? (int64_t)m->capacity : 0; }
 
@@ -502,6 +603,7 @@ int scvod_batch_map_accumulate(scvod_ctx* ctx, scvod_map* m, const float* h_pose
 
 int scvod_batch_map_accumulate_range(scvod_ctx* ctx, scvod_map* m, const float* h_poses, int32_t flags, int32_t first, int32_t count, void* stream) {
     if (!ctx || !m || !h_poses) return mfail(m, SCVOD_ERR_INVALID, "bad arguments");
+    if (m->kind != SCVOD_MAP_KIND_PLAIN) return mfail(m, SCVOD_ERR_INVALID, "a labelled map is accumulated by scvod_batch_map_accumulate_classes / scvod_map_accumulate_labelled");
     Arena A;
     int device = 0, track_valid = 0, batch_valid = 0, n_scans = 0, max_pts = 0, mode = 0, min_pts = 0;
     scvod__ctx_view(ctx, &A, &device, &track_valid, &batch_valid, &n_scans, &max_pts, &mode, &min_pts);
@@ -545,28 +647,172 @@ int scvod_batch_map_accumulate_range(scvod_ctx* ctx, scvod_map* m, const float* 
     return SCVOD_OK;
 }
 
-static int map_export(scvod_map* m, void* d_records, void* d_xyzi, int64_t cap, int64_t* n_out, void* stream) {
+// the 256 keep / select bytes as the four words the kernels take; NULL = every label
+static void map_table256(const uint8_t* h256, unsigned long long k[4]) {
+    for (int w = 0; w < 4; ++w) {
+        k[w] = h256 ? 0ull : ~0ull;
+        if (h256)
+            for (int b = 0; b < 64; ++b)
+                if (h256[64 * w + b]) k[w] |= 1ull << b;
+    }
+}
+
+// the poses of a call as matrices on the device (h_poses NULL: the zero pose, n times).  The staging vector may still feed an earlier
+// asynchronous copy: values that differ from the previous call's wait for `st` first.
+static int map_stage_poses(scvod_map* m, const float* h_poses, int n, hipStream_t st) {
+    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    std::vector<float> T((size_t)12 * n);
+    for (int s = 0; s < n; ++s) scvod_pose_matrix(h_poses ? h_poses + 6 * s : zero, T.data() + 12 * s);
+    if (m->pose_cap < n) {
+        MHIP(m, hipStreamSynchronize(st));
+        if (m->d_pose) hipFree(m->d_pose);
+        m->d_pose = nullptr;
+        m->pose_cap = 0;
+        m->up_pose.clear();
+        MHIP(m, hipMalloc(&m->d_pose, sizeof(float) * 12 * (size_t)n));
+        m->pose_cap = n;
+    }
+    if (m->up_pose != T) {
+        MHIP(m, hipStreamSynchronize(st));
+        m->up_pose = T;
+        MHIP(m, hipMemcpyAsync(m->d_pose, m->up_pose.data(), sizeof(float) * T.size(), hipMemcpyHostToDevice, st));
+    }
+    return SCVOD_OK;
+}
+
+// scans [first, first + count) of a cloud whose offsets and poses are on the device already
+static int map_launch_labelled(scvod_map* m, const void* d_xyzi, const uint8_t* d_labels, const int32_t* d_offs, int first, int count, int max_pts,
+                               const unsigned long long k[4], hipStream_t st) {
+    constexpr int kMaxGridY = 65535;
+    for (int s0 = 0; s0 < count && max_pts > 0; s0 += kMaxGridY) {
+        const int ny = count - s0 < kMaxGridY ? count - s0 : kMaxGridY;
+        hipLaunchKernelGGL(k_map_accumulate_labelled, dim3((max_pts + kMapPts - 1) / kMapPts, ny), dim3(256), 0, st, first + s0, (const float4*)d_xyzi,
+                           d_labels, d_offs, m->d_pose, m->table, (unsigned long long)(m->capacity - 1), 1.0f / m->leaf, k[0], k[1], k[2], k[3],
+                           m->counters);
+        MHIP(m, hipGetLastError());
+    }
+    return SCVOD_OK;
+}
+
+int scvod_map_accumulate_labelled(scvod_map* m, const void* d_xyzi, const uint8_t* d_labels, const int32_t* h_scan_offsets, int32_t n_scans,
+                                  const float* h_poses, const uint8_t* h_keep256, void* stream) {
+    if (!m || n_scans < 0 || (n_scans > 0 && !h_scan_offsets)) return mfail(m, SCVOD_ERR_INVALID, "bad arguments");
+    if (m->kind != SCVOD_MAP_KIND_LABELLED) return mfail(m, SCVOD_ERR_INVALID, "scvod_map_accumulate_labelled needs a map of kind SCVOD_MAP_KIND_LABELLED");
+    if (n_scans == 0) return SCVOD_OK;
+    if (h_scan_offsets[0] < 0) return mfail(m, SCVOD_ERR_INVALID, "scan offsets start below 0");
+    int max_pts = 0;
+    for (int s = 0; s < n_scans; ++s) {
+        if (h_scan_offsets[s + 1] < h_scan_offsets[s]) return mfail(m, SCVOD_ERR_INVALID, "scan offsets decrease at scan %d", s);
+        if (h_scan_offsets[s + 1] - h_scan_offsets[s] > max_pts) max_pts = h_scan_offsets[s + 1] - h_scan_offsets[s];
+    }
+    if (max_pts > 0 && (!d_xyzi || !d_labels)) return mfail(m, SCVOD_ERR_INVALID, "NULL points or labels of a cloud that is not empty");
+    if ((uintptr_t)d_xyzi & 15u) return mfail(m, SCVOD_ERR_INVALID, "d_xyzi is not 16-byte aligned");
+    if (max_pts == 0) return SCVOD_OK;
+    MHIP(m, hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = map_stage_poses(m, h_poses, n_scans, st)) return rc;
+    const std::vector<int32_t> offs(h_scan_offsets, h_scan_offsets + n_scans + 1);
+    if (m->offs_cap < n_scans + 1) {
+        MHIP(m, hipStreamSynchronize(st));
+        if (m->d_offs) hipFree(m->d_offs);
+        m->d_offs = nullptr;
+        m->offs_cap = 0;
+        m->up_offs.clear();
+        MHIP(m, hipMalloc(&m->d_offs, sizeof(int32_t) * ((size_t)n_scans + 1)));
+        m->offs_cap = (long long)n_scans + 1;
+    }
+    if (m->up_offs != offs) {  // (the same hazard as the poses' staging vector)
+        MHIP(m, hipStreamSynchronize(st));
+        m->up_offs = offs;
+        MHIP(m, hipMemcpyAsync(m->d_offs, m->up_offs.data(), sizeof(int32_t) * offs.size(), hipMemcpyHostToDevice, st));
+    }
+    unsigned long long k[4];
+    map_table256(h_keep256, k);
+    return map_launch_labelled(m, d_xyzi, d_labels, m->d_offs, 0, n_scans, max_pts, k, st);
+}
+
+int scvod_batch_map_accumulate_classes(scvod_ctx* ctx, scvod_map* m, const float* h_poses, int32_t flags, int32_t first, int32_t count, void* stream) {
+    if (!ctx || !m || !h_poses) return mfail(m, SCVOD_ERR_INVALID, "bad arguments");
+    if (m->kind != SCVOD_MAP_KIND_LABELLED) return mfail(m, SCVOD_ERR_INVALID, "scvod_batch_map_accumulate_classes needs a map of kind SCVOD_MAP_KIND_LABELLED");
+    constexpr int32_t kAll = SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED | SCVOD_MAP_IGNORE_DYNAMIC | SCVOD_MAP_PART_UNTRACKED | SCVOD_MAP_PART_TRACKED;
+    if (flags & ~kAll) return mfail(m, SCVOD_ERR_INVALID, "unknown flag bits (flags %d)", flags);
+    if ((flags & SCVOD_MAP_PART_UNTRACKED) && (flags & SCVOD_MAP_PART_TRACKED)) return mfail(m, SCVOD_ERR_INVALID, "the two part flags exclude each other");
+    const int part = (flags & SCVOD_MAP_PART_UNTRACKED) ? 1 : ((flags & SCVOD_MAP_PART_TRACKED) ? 2 : 0);
+    Arena A;
+    int device = 0, track_valid = 0, batch_valid = 0, n_scans = 0, max_pts = 0, mode = 0, min_pts = 0;
+    scvod__ctx_view(ctx, &A, &device, &track_valid, &batch_valid, &n_scans, &max_pts, &mode, &min_pts);
+    if (!batch_valid || !A.pts) return mfail(m, SCVOD_ERR_STATE, "scvod_batch_map_accumulate_classes needs a processed batch of input clouds");
+    if (device != m->device) return mfail(m, SCVOD_ERR_INVALID, "map and ctx live on different devices");
+    if (count < 0) count = n_scans - first;
+    if (first < 0 || count < 0 || first + count > n_scans) return mfail(m, SCVOD_ERR_INVALID, "scan range [%d, %d) outside the batch of %d", first, first + count, n_scans);
+    MHIP(m, hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)scvod__ctx_stream(ctx, stream);
+    const long long total = (long long)A.total_pts > 0 ? (long long)A.total_pts : 1;
+    if (m->cls_cap < total) {  // (a batch larger than any before: the old bytes may still be read by a kernel in flight)
+        MHIP(m, hipStreamSynchronize(st));
+        if (m->d_cls) hipFree(m->d_cls);
+        m->d_cls = nullptr;
+        m->cls_cap = 0;
+        MHIP(m, hipMalloc(&m->d_cls, (size_t)total));
+        m->cls_cap = total;
+    }
+    // the bytes: part UNTRACKED reads no tracking result (every car-cluster member is 5 then, and left out); everything else wants a
+    // current one, SCVOD_MAP_IGNORE_DYNAMIC too -- the raw labelled map keeps its dynamic points under their own label 6
+    if (int rc = scvod_batch_point_classes(ctx, m->d_cls, m->cls_cap, part == 1 ? SCVOD_MAP_IGNORE_DYNAMIC : 0, st))
+        return mfail(m, rc, "%s", scvod_last_error(ctx));
+    uint8_t keep[256] = {0};
+    if (part != 2) {
+        keep[SCVOD_PT_GROUND] = (flags & SCVOD_MAP_NO_GROUND) ? 0 : 1;
+        keep[SCVOD_PT_REJECTED] = (flags & SCVOD_MAP_NO_REJECTED) ? 0 : 1;
+        keep[SCVOD_PT_UNCLUSTERED] = keep[SCVOD_PT_STATIC_OTHER] = keep[SCVOD_PT_STATIC_BUILDING] = 1;
+    }
+    if (part != 1) {
+        keep[SCVOD_PT_STATIC_CAR] = 1;
+        keep[SCVOD_PT_DYNAMIC] = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 1 : 0;
+    }
+    if (int rc = map_stage_poses(m, h_poses, n_scans, st)) return rc;
+    unsigned long long k[4];
+    map_table256(keep, k);
+    return map_launch_labelled(m, A.pts, m->d_cls, A.scan_off, first, count, max_pts, k, st);
+}
+
+// select256 (labelled maps only): the cells listed and counted; NULL = all
+static int map_export(scvod_map* m, void* d_records, void* d_xyzi, uint8_t* d_labels, const uint8_t* h_select256, int64_t cap, int64_t* n_out,
+                      void* stream) {
     if (!m || !n_out || cap < 0) return mfail(m, SCVOD_ERR_INVALID, "bad arguments");
     MHIP(m, hipSetDevice(m->device));
     hipStream_t st = (hipStream_t)stream;
     MHIP(m, hipMemsetAsync(m->counters, 0, 8, st));
-    hipLaunchKernelGGL(k_map_export, dim3(256 * 8), dim3(256), 0, st, m->table, m->capacity, (MapRec*)d_records, (long long)cap, (float4*)d_xyzi,
-                       m->leaf, m->counters);
+    if (m->kind == SCVOD_MAP_KIND_LABELLED && (d_xyzi || d_labels || h_select256)) {
+        unsigned long long k[4];
+        map_table256(h_select256, k);
+        hipLaunchKernelGGL(k_map_export<true>, dim3(256 * 8), dim3(256), 0, st, m->table, m->capacity, (MapRec*)d_records, (long long)cap,
+                           (float4*)d_xyzi, m->leaf, m->counters, d_labels, k[0], k[1], k[2], k[3]);
+    } else {
+        hipLaunchKernelGGL(k_map_export<false>, dim3(256 * 8), dim3(256), 0, st, m->table, m->capacity, (MapRec*)d_records, (long long)cap,
+                           (float4*)d_xyzi, m->leaf, m->counters, (uint8_t*)nullptr, 0ull, 0ull, 0ull, 0ull);
+    }
     MHIP(m, hipGetLastError());
     unsigned long long h[2] = {0, 0};
     MHIP(m, hipMemcpyAsync(h, m->counters, 16, hipMemcpyDeviceToHost, st));
     MHIP(m, hipStreamSynchronize(st));
     *n_out = (int64_t)h[0];
     if (h[1]) return mfail(m, SCVOD_ERR_CAPACITY, "%llu points did not fit the map (table of %lld cells full or coordinates out of range)", h[1], m->capacity);
-    if ((d_records || d_xyzi) && (int64_t)h[0] > cap) return mfail(m, SCVOD_ERR_CAPACITY, "output buffer too small (%lld < %llu cells)", (long long)cap, h[0]);
+    if ((d_records || d_xyzi || d_labels) && (int64_t)h[0] > cap) return mfail(m, SCVOD_ERR_CAPACITY, "output buffer too small (%lld < %llu cells)", (long long)cap, h[0]);
     return SCVOD_OK;
 }
 
 int scvod_map_export(scvod_map* m, void* d_records, int64_t cap_records, int64_t* n_out, void* stream) {
-    return map_export(m, d_records, nullptr, cap_records, n_out, stream);
+    return map_export(m, d_records, nullptr, nullptr, nullptr, cap_records, n_out, stream);
 }
 int scvod_map_points(scvod_map* m, void* d_xyzi, void* d_keys_records, int64_t cap, int64_t* n_out, void* stream) {
-    return map_export(m, d_keys_records, d_xyzi, cap, n_out, stream);
+    return map_export(m, d_keys_records, d_xyzi, nullptr, nullptr, cap, n_out, stream);
+}
+int scvod_map_points_labelled(scvod_map* m, void* d_xyzi, uint8_t* d_labels, void* d_records, int64_t cap, const uint8_t* h_select256,
+                              int64_t* n_out, void* stream) {
+    if (!m || !n_out || cap < 0) return mfail(m, SCVOD_ERR_INVALID, "bad arguments");
+    if (m->kind != SCVOD_MAP_KIND_LABELLED) return mfail(m, SCVOD_ERR_INVALID, "scvod_map_points_labelled needs a map of kind SCVOD_MAP_KIND_LABELLED");
+    return map_export(m, d_records, d_xyzi, d_labels, h_select256, cap, n_out, stream);
 }
 
 int scvod_map_export_parts(scvod_map* m, int32_t n_parts, void* d_records, int64_t cap_records, int64_t* h_counts, void* stream) {

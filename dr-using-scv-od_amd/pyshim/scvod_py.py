@@ -237,6 +237,12 @@ def load_lib():
         "scvod_map_export_parts": (C.c_int, [vp, i32, vp, i64, vp, vp]),
         "scvod_map_export_parts_padded": (C.c_int, [vp, i32, vp, i64, vp, vp]),
         "scvod_map_points": (C.c_int, [vp, vp, vp, i64, C.POINTER(i64), vp]),
+        "scvod_map_create_kind": (C.c_int, [C.c_int, i64, f32, i32, C.POINTER(vp)]),
+        "scvod_map_kind": (i32, [vp]),
+        "scvod_map_scratch_bytes": (i64, [vp]),
+        "scvod_map_accumulate_labelled": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
+        "scvod_batch_map_accumulate_classes": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+        "scvod_map_points_labelled": (C.c_int, [vp, vp, vp, vp, i64, vp, C.POINTER(i64), vp]),
         "scvod_batch_point_labels": (C.c_int, [vp, vp, i64, i32, vp]),
         "scvod_batch_export_points": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
         "scvod_batch_export_stats": (C.c_int, [vp, vp]),
@@ -294,6 +300,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_set_region_growing", "scvod_batch_fetch_cluster_classes", "scvod_batch_fetch_region_growing", "scvod_batch_region_growing_stats", "scvod_set_intensity_calibration", "scvod_batch_fetch_intensity_calibration", "scvod_batch_intensity_calibration_stats", "scvod_batch_intensity_calibration_candidates", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
                     "scvod_map_create", "scvod_map_destroy", "scvod_map_last_error", "scvod_map_capacity", "scvod_map_clear",
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
+                    "scvod_map_create_kind", "scvod_map_kind", "scvod_map_scratch_bytes", "scvod_map_accumulate_labelled",
+                    "scvod_batch_map_accumulate_classes", "scvod_map_points_labelled",
                     "scvod_batch_point_labels", "scvod_batch_export_points", "scvod_batch_export_stats",
                     "scvod_batch_objects", "scvod_batch_objects_stats", "scvod_batch_objects_scratch_bytes",
                     "scvod_feature_params_default", "scvod_set_object_features", "scvod_batch_object_shapes", "scvod_batch_object_shapes_stats",
@@ -1127,6 +1135,8 @@ class Ctx:
 
 
 MAP_NO_GROUND, MAP_NO_REJECTED, MAP_IGNORE_DYNAMIC = 1, 2, 4
+MAP_PART_UNTRACKED, MAP_PART_TRACKED = 8, 16
+MAP_KIND_PLAIN, MAP_KIND_LABELLED = 0, 1  # SCVOD_MAP_KIND_*
 # scvod_batch_point_labels: one byte per input point (include/scvod.h, SCVOD_PT_*)
 PT_DROPPED, PT_GROUND, PT_REJECTED, PT_UNCLUSTERED, PT_STATIC_OTHER, PT_STATIC_CAR, PT_DYNAMIC = range(7)
 PT_STATIC_BUILDING = 7  # scvod_batch_point_classes only
@@ -1135,15 +1145,17 @@ PT_STATIC_BUILDING = 7  # scvod_batch_point_classes only
 class StaticMap:
     """World-frame static map (include/scvod.h, scvod_map_*): device-resident set of occupied cells, mergeable across shards."""
 
-    def __init__(self, capacity_cells, leaf=0.2, device=0):
+    def __init__(self, capacity_cells, leaf=0.2, device=0, kind=MAP_KIND_PLAIN):
+        """kind: MAP_KIND_PLAIN, or MAP_KIND_LABELLED for the recognised map (a label byte per cell)"""
         self.lib = load_lib()
         h = C.c_void_p()
-        rc = self.lib.scvod_map_create(int(device), int(capacity_cells), float(leaf), C.byref(h))
+        rc = self.lib.scvod_map_create_kind(int(device), int(capacity_cells), float(leaf), int(kind), C.byref(h))
         if rc != 0:
-            raise ScvodError(f"scvod_map_create failed with status {rc}")
+            raise ScvodError(f"status {rc}: scvod_map_create_kind failed")
         self.h = h
         self.leaf = float(leaf)
         self.device = int(device)
+        self.kind = int(kind)
 
     def _chk(self, rc):
         if rc != 0:
@@ -1167,6 +1179,53 @@ class StaticMap:
         p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
         assert p.shape[0] == ctx._n_scans
         self._chk(self.lib.scvod_batch_map_accumulate_range(ctx.h, self.h, p.ctypes.data_as(C.c_void_p), int(flags), int(first), int(count), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def _table256(t):
+        """a keep / select table as 256 bytes: None (all), a [256] array, or the labels that are set"""
+        if t is None:
+            return None, None
+        a = np.asarray(t)
+        if a.shape != (256,):
+            a = np.zeros(256, np.uint8)
+            a[np.asarray(t, np.int64).reshape(-1)] = 1
+        a = np.ascontiguousarray(a != 0, np.uint8)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def accumulate_labelled(self, d_xyzi, d_labels, scan_offsets, poses=None, keep=None, stream=None):
+        """labelled maps: the caller's own cloud (torch float32 [n, 4]) and label bytes (torch uint8 [n]); keep: see _table256"""
+        off = np.ascontiguousarray(scan_offsets, np.int32)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == len(off) - 1
+        k, pk = self._table256(keep)
+        self._chk(self.lib.scvod_map_accumulate_labelled(self.h, C.c_void_p(d_xyzi.data_ptr()), C.c_void_p(d_labels.data_ptr()),
+                                                         off.ctypes.data_as(C.c_void_p), len(off) - 1,
+                                                         None if p is None else p.ctypes.data_as(C.c_void_p), pk, C.c_void_p(stream or 0)))
+
+    def accumulate_classes(self, ctx, poses, flags=0, first=0, count=-1, stream=None):
+        """labelled maps: the recognised map of the ctx's last batch (scvod_batch_map_accumulate_classes)"""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p.shape[0] == ctx._n_scans
+        self._chk(self.lib.scvod_batch_map_accumulate_classes(ctx.h, self.h, p.ctypes.data_as(C.c_void_p), int(flags), int(first), int(count),
+                                                              C.c_void_p(stream or 0)))
+
+    def scratch_bytes(self):
+        return int(self.lib.scvod_map_scratch_bytes(self.h))
+
+    def points_labelled(self, select=None, stream=None):
+        """labelled maps: (xyzi float32 [n, 4], labels uint8 [n], records int64 [n, 2]) of the cells whose label is selected (see
+        _table256; None: all), device tensors in the same (unspecified) order"""
+        import torch
+        n0 = max(self.count(stream), 1)
+        dev = torch.device("cuda", self.device)
+        xyzi = torch.empty((n0, 4), dtype=torch.float32, device=dev)
+        lab = torch.empty((n0,), dtype=torch.uint8, device=dev)
+        rec = torch.empty((n0, 2), dtype=torch.int64, device=dev)
+        n = C.c_int64()
+        k, pk = self._table256(select)
+        self._chk(self.lib.scvod_map_points_labelled(self.h, C.c_void_p(xyzi.data_ptr()), C.c_void_p(lab.data_ptr()), C.c_void_p(rec.data_ptr()), n0,
+                                                     pk, C.byref(n), C.c_void_p(stream or 0)))
+        return xyzi[:int(n.value)], lab[:int(n.value)], rec[:int(n.value)]
 
     def count(self, stream=None):
         n = C.c_int64()

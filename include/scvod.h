@@ -575,6 +575,26 @@ typedef struct scvod_map scvod_map;
 #define SCVOD_MAP_PART_UNTRACKED 8  /* every kept point that is not a member of a car cluster (needs no tracking result) */
 #define SCVOD_MAP_PART_TRACKED 16   /* the car-cluster members scvod_batch_track left static                            */
 int scvod_map_create(int device, int64_t capacity_cells, float leaf, scvod_map** out);
+/* Two kinds of map share the table, the hash, the probing and every export / merge / clear call; only the packing of a record's
+ * 64-bit value differs.
+ *   SCVOD_MAP_KIND_PLAIN     val = qx << 48 | qy << 32 | qz << 16 | qi16: the map described above (what scvod_map_create creates)
+ *   SCVOD_MAP_KIND_LABELLED  val = qx << 48 | qy << 32 | qz << 16 | label << 8 | qi8: the RECOGNISED map -- `instance_map` in the colour
+ *                            of each cluster's class (SSC::saveSegCloud mode 3, src/ssc.cpp:501-554, the ground clouds beside it,
+ *                            ssc.cpp:1461-1486), the cloud src/plotObject.cpp reads back class by class.  qx, qy, qz are the plain
+ *                            map's 16-bit offsets, label is the caller's byte (0..255), qi8 = (int)clamp(intensity, 0.f, 255.f):
+ *                            truncated, not scaled (a NaN intensity is not specified, as above).  Insertion is the same single 64-bit
+ *                            atomicMin, so a cell's representative is the point with the smallest (offset, label, intensity): a
+ *                            measured point with ITS OWN label.  The rule is order-independent, and because the leading 48 bits are
+ *                            the plain map's, the representative's xyz equals the plain map's for the same kept set, bit for bit.
+ * One representative per cell is this library's design (the reference appends every point).
+ * scvod_map_export, _export_parts, _export_parts_padded, _merge and _clear treat the value as opaque and work on both kinds; records
+ * carry no mark of their kind, so merging the records of a map of the other kind CANNOT be detected -- keep the kinds apart.
+ * scvod_map_create_kind: SCVOD_ERR_INVALID for an unknown kind (before a device is looked for). */
+#define SCVOD_MAP_KIND_PLAIN 0
+#define SCVOD_MAP_KIND_LABELLED 1
+int scvod_map_create_kind(int device, int64_t capacity_cells, float leaf, int32_t kind, scvod_map** out);
+/* the kind of the map (SCVOD_ERR_INVALID for NULL) */
+int32_t scvod_map_kind(const scvod_map* map);
 void scvod_map_destroy(scvod_map* map);
 const char* scvod_map_last_error(const scvod_map* map);
 int64_t scvod_map_capacity(const scvod_map* map);
@@ -585,7 +605,8 @@ void scvod_pose_matrix(const float pose[6], float T_out[12]);
  * into matrices and copied before the call returns (poses that differ from the previous call's wait for `stream` first: the
  * map's one staging copy may still be in flight). */
 int scvod_batch_map_accumulate(scvod_ctx* ctx, scvod_map* map, const float* h_poses, int32_t flags, void* stream);
-/* the same for scans [first, first + count) of the batch only (a shard's own block, without its halo); h_poses still [n_scans][6] */
+/* the same for scans [first, first + count) of the batch only (a shard's own block, without its halo); h_poses still [n_scans][6].
+ * Both refuse a labelled map with SCVOD_ERR_INVALID before anything is launched. */
 int scvod_batch_map_accumulate_range(scvod_ctx* ctx, scvod_map* map, const float* h_poses, int32_t flags, int32_t first, int32_t count, void* stream);
 /* occupied cells as 16-byte records {uint64 cell key, uint64 packed point} into device memory (NULL: count only);
  * *n_out = number of cells.  Synchronises `stream`.  Record order is unspecified (sort by key for a canonical order). */
@@ -604,8 +625,50 @@ int scvod_map_export_parts(scvod_map* map, int32_t n_parts, void* d_records, int
 int scvod_map_export_parts_padded(scvod_map* map, int32_t n_parts, void* d_records, int64_t cap_per_part, void* d_counts, void* stream);
 /* inserts records exported by another shard (a record with key ~0 is padding and skipped).  Asynchronous. */
 int scvod_map_merge(scvod_map* map, const void* d_records, int64_t n, void* stream);
-/* the map as points: d_xyzi [cap][4] floats (cell origin + stored offset, intensity), optionally the records beside them */
+/* the map as points: d_xyzi [cap][4] floats (cell origin + stored offset, intensity), optionally the records beside them.  On a
+ * labelled map the intensity is the record's low 8 bits (an integer 0..255). */
 int scvod_map_points(scvod_map* map, void* d_xyzi, void* d_records, int64_t cap, int64_t* n_out, void* stream);
+
+/* ---- the recognised map: a label per cell (maps of kind SCVOD_MAP_KIND_LABELLED) ---------------------------------------------------
+ * Adds a caller's own cloud, no batch context needed: the point at h_scan_offsets[s] + i of d_xyzi (packed float4, 16-byte aligned)
+ * carries the byte d_labels[h_scan_offsets[s] + i], is moved by scvod_pose_matrix(h_poses + 6 s) with the expression of
+ * scvod_batch_map_accumulate (T0*x + T1*y + T2*z + T3 per row, fp32, left to right, no contraction; h_poses NULL: the zero pose for
+ * every scan, through the same expression) and is kept iff h_keep256[label] != 0 (h_keep256 NULL: every label is kept).
+ * Stream-ordered; offsets, poses and the keep table are copied before the call returns, and the call never synchronises -- except
+ * that offsets or poses which differ from the previous call's wait for `stream` first (the map's one staging copy of each may still
+ * be in flight).  Refused with SCVOD_ERR_INVALID before anything is launched: a plain map, n_scans < 0, NULL offsets, offsets that
+ * decrease or start below 0, NULL points or labels of a cloud that is not empty, a d_xyzi that is not 16-byte aligned.  A point whose
+ * cell leaves the map's range, a NaN coordinate and a full table are counted and reported by the next scvod_map_export* call, as
+ * for the plain map. */
+int scvod_map_accumulate_labelled(scvod_map* map, const void* d_xyzi, const uint8_t* d_labels, const int32_t* h_scan_offsets, int32_t n_scans,
+                                  const float* h_poses, const uint8_t* h_keep256, void* stream);
+/* The recognised map of the ctx's last batch: every kept input point of scans [first, first + count) (count -1: to the end) under its
+ * byte of scvod_batch_point_classes -- 1 ground, 2 rejected, 3 unclustered, 4 tree / other, 5 static car, 6 dynamic, 7 building (only
+ * with the region growing on; without it no cell carries a 7).  The bytes of the whole batch are written into scratch of the map's own
+ * (one byte per point, grow-only, scvod_map_scratch_bytes; scvod_arena_bytes does not move), then the kernel of
+ * scvod_map_accumulate_labelled runs on the ctx's input cloud.  flags are the five SCVOD_MAP_* flags as a keep table over the byte:
+ *   0 (SCVOD_PT_DROPPED) never; 1 unless SCVOD_MAP_NO_GROUND; 2 unless SCVOD_MAP_NO_REJECTED; 3, 4, 5, 7 always; 6 only with
+ *   SCVOD_MAP_IGNORE_DYNAMIC -- the raw map, from which "everything but 6" is the static and "6" the dynamic cloud
+ *   (scvod_map_points_labelled): unlike the plain raw map it needs the tracking result, which is what tells a 6 from a 5
+ *   SCVOD_MAP_PART_UNTRACKED  keeps {1, 2, 3, 4, 7} (less the two NO_ flags) of bytes computed WITHOUT a tracking result
+ *   SCVOD_MAP_PART_TRACKED    keeps {5}, and 6 with SCVOD_MAP_IGNORE_DYNAMIC, of bytes computed with one
+ * The cell rule is order-independent: part UNTRACKED + part TRACKED == one call without a part flag, bit for bit.  With the same
+ * flags the cells are those of scvod_batch_map_accumulate on a plain map, and so are the leading 48 bits of every value.
+ * State rules and errors are those of scvod_batch_point_classes (flags SCVOD_MAP_IGNORE_DYNAMIC for part UNTRACKED, 0 otherwise):
+ * SCVOD_ERR_STATE without a batch of scvod_batch_process, its clustering and its types, SCVOD_ERR_INVALID when the tracking result
+ * is missing or stale.  SCVOD_ERR_INVALID also for a plain map, both part flags, an unknown flag bit, a scan range outside the batch
+ * and a map on another device -- each before anything is launched.  Stream-ordered (stream NULL = the stream of the ctx's last
+ * batch call); synchronises only as scvod_map_accumulate_labelled does for poses that changed, and when the scratch has to grow. */
+int scvod_batch_map_accumulate_classes(scvod_ctx* ctx, scvod_map* map, const float* h_poses, int32_t flags, int32_t first, int32_t count,
+                                       void* stream);
+/* bytes of device scratch the batch form holds on this map (0 before its first call, and for NULL) */
+int64_t scvod_map_scratch_bytes(const scvod_map* map);
+/* scvod_map_points of a labelled map with the label byte of every cell beside it, restricted to the cells whose label is selected
+ * (h_select256[label] != 0; NULL: all): d_xyzi [cap][4] floats, d_labels [cap] bytes, d_records [cap] 16-byte records, any of them
+ * NULL; *n_out = the number of SELECTED cells.  SCVOD_ERR_CAPACITY when they outgrow cap (nothing is written at or behind cap);
+ * SCVOD_ERR_INVALID for a plain map.  Synchronises `stream`.  Row i of the three outputs is the same cell; the order is unspecified. */
+int scvod_map_points_labelled(scvod_map* map, void* d_xyzi, uint8_t* d_labels, void* d_records, int64_t cap, const uint8_t* h_select256,
+                              int64_t* n_out, void* stream);
 
 /* ---- the result of a batch handed on: per-point labels and the cleaned scans, on the device -------------------------------
  * Reference analogue: the `static_pt` / `dynamic_pt` lists of SSC::saveSegCloud mode 3 (src/ssc.cpp:477-554) and the clouds of the
