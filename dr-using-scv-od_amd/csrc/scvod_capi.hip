@@ -212,6 +212,13 @@ struct scvod_ctx {
     hipStream_t stk_stream = nullptr;  // stream of the last stacking call (a growing block waits for it)
     bool stk_ran = false;
     std::vector<unsigned char> stk_host;  // the tables as built on the host (scratch of the call; the upload is staged from a copy)
+    // map split by nearest-neighbour hits (scvod_map_split_device, scvod_split.hip): a grow-only block and 8 stats words of their own,
+    // allocated by the first call; not part of the arena, not the evaluation's and not the class scores'
+    void* sp_buf = nullptr;
+    size_t sp_cap = 0;
+    unsigned long long* sp_stats = nullptr;
+    hipStream_t sp_stream = nullptr;   // stream of the last split (scvod_map_split_stats waits for it; a growing block too)
+    bool sp_ran = false;
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1477,6 +1484,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->cs_buf) hipFree(c->cs_buf);
     if (c->cs_counters) hipFree(c->cs_counters);
     if (c->stk_buf) hipFree(c->stk_buf);
+    if (c->sp_buf) hipFree(c->sp_buf);
+    if (c->sp_stats) hipFree(c->sp_stats);
     if (c->stage) hipHostFree(c->stage);
     for (void* b : c->nn_buf)
         if (b) hipFree(b);
@@ -3473,5 +3482,146 @@ int scvod_stack_scans(scvod_ctx* c, const float* h_xyzi_in, const int32_t* h_in_
 }
 
 int64_t scvod_stack_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)c->stk_cap : 0; }
+
+// ---- a map split by nearest-neighbour hits (scvod_split.hip) ----
+void scvod_split_params_default(scvod_split_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->cell = 0.2f;
+    p->max_rings = 3;
+    p->base_stride = 3;
+    p->query_stride = 3;
+}
+
+int scvod_map_split_device(scvod_ctx* c, const float* d_base, const uint32_t* d_base_label, int32_t n_base, const float* d_query,
+                           int32_t n_query, const scvod_split_params* params, uint8_t* d_mark, int32_t* d_order, int64_t* d_seg4,
+                           float* d_base_out, const uint32_t* d_payload_in, uint32_t* d_payload_out, int32_t* d_nn_idx, float* d_nn_sqdist,
+                           void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_base < 0 || n_query < 0 || (n_base > 0 && !d_base) || (n_query > 0 && !d_query)) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    scvod_split_params p;  // a copy: the caller's struct is the caller's again when the call returns
+    if (params)
+        p = *params;
+    else
+        scvod_split_params_default(&p);
+    if ((p.base_stride != 3 && p.base_stride != 4) || (p.query_stride != 3 && p.query_stride != 4))
+        return fail(c, SCVOD_ERR_INVALID, "strides %d / %d: 3 (packed xyz) or 4 (xyzi)", p.base_stride, p.query_stride);
+    if ((p.base_stride == 4 && (((uintptr_t)d_base & 15) || ((uintptr_t)d_base_out & 15))) || (p.query_stride == 4 && ((uintptr_t)d_query & 15)))
+        return fail(c, SCVOD_ERR_INVALID, "a cloud of 4 floats per record must be 16-byte aligned");
+    if (d_payload_out && !d_payload_in) return fail(c, SCVOD_ERR_INVALID, "a payload output needs a payload input");
+    if (p.n_reject_classes < 0 || p.n_reject_classes > 16) return fail(c, SCVOD_ERR_INVALID, "%d reject classes (0..16)", p.n_reject_classes);
+    if (p.n_reject_classes > 0 && n_base > 0 && !d_base_label) return fail(c, SCVOD_ERR_INVALID, "a reject list needs the base labels");
+    if (!(p.cell > 0.f) || !std::isfinite(p.cell)) return fail(c, SCVOD_ERR_INVALID, "cell must be positive and finite");
+    if (p.max_rings < 1 || p.max_rings > 8) return fail(c, SCVOD_ERR_INVALID, "max_rings %d (1..8)", p.max_rings);
+    if (d_base_out && n_base > 0) {
+        const uintptr_t a0 = (uintptr_t)d_base, b0 = (uintptr_t)d_base_out, bytes = (uintptr_t)4 * (uintptr_t)p.base_stride * (uintptr_t)n_base;
+        if (a0 < b0 + bytes && b0 < a0 + bytes) return fail(c, SCVOD_ERR_INVALID, "the record output overlaps the base cloud");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (!c->sp_stats) {
+        HIPCHK(c, hipMalloc(&c->sp_stats, sizeof(unsigned long long) * 8));
+        HIPCHK(c, hipMemset(c->sp_stats, 0, sizeof(unsigned long long) * 8));
+    }
+    const int32_t buckets = ev_buckets(n_base);
+    const size_t bytes = sp_work_bytes(buckets, n_base, n_query);
+    if (bytes > c->sp_cap) {  // (the old block may still be read by a split in flight)
+        if (c->sp_buf) {
+            if (c->sp_ran) HIPCHK(c, hipStreamSynchronize(c->sp_stream));
+            hipFree(c->sp_buf);
+            c->sp_buf = nullptr;
+            c->sp_cap = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->sp_buf, bytes + bytes / 4));
+        c->sp_cap = bytes + bytes / 4;
+    }
+    SpJob J;
+    memset(&J, 0, sizeof(J));
+    J.base = d_base;
+    J.base_label = d_base_label;
+    J.query = d_query;
+    J.n_base = n_base;
+    J.n_query = n_query;
+    J.base_stride = p.base_stride;
+    J.query_stride = p.query_stride;
+    J.max_rings = p.max_rings;
+    J.n_reject = p.n_reject_classes;
+    for (int k = 0; k < 16; ++k) J.reject[k] = p.reject_classes[k];
+    J.mark = d_mark;
+    J.order = d_order;
+    J.seg4 = d_seg4;
+    J.base_out = d_base_out;
+    J.payload_in = d_payload_in;
+    J.payload_out = d_payload_out;
+    J.nn_idx = d_nn_idx;
+    J.nn_sq = d_nn_sqdist;
+    launch_map_split(J, p.cell, buckets, c->sp_buf, c->sp_stats, st);
+    HIPCHK(c, hipGetLastError());
+    c->sp_stream = st;
+    c->sp_ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_map_split_stats(scvod_ctx* c, int64_t* h_out8) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->sp_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_map_split_device on this ctx yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, c->sp_stats, sizeof(h), hipMemcpyDeviceToHost, c->sp_stream));
+    HIPCHK(c, hipStreamSynchronize(c->sp_stream));
+    for (int k = 0; k < 8; ++k) h_out8[k] = (int64_t)h[k];
+    return SCVOD_OK;
+}
+
+int64_t scvod_map_split_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->sp_cap + (c->sp_stats ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+}
+
+int scvod_map_split(scvod_ctx* c, const float* h_base, const uint32_t* h_base_label, int32_t n_base, const float* h_query, int32_t n_query,
+                    const scvod_split_params* params, uint8_t* h_mark, int32_t* h_order, int64_t* h_seg4, float* h_base_out) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_base < 0 || n_query < 0 || (n_base > 0 && !h_base) || (n_query > 0 && !h_query)) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    scvod_split_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_split_params_default(&p);
+    if ((p.base_stride != 3 && p.base_stride != 4) || (p.query_stride != 3 && p.query_stride != 4))
+        return fail(c, SCVOD_ERR_INVALID, "strides %d / %d: 3 (packed xyz) or 4 (xyzi)", p.base_stride, p.query_stride);
+    if (p.n_reject_classes > 0 && n_base > 0 && !h_base_label) return fail(c, SCVOD_ERR_INVALID, "a reject list needs the base labels");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)(n_base > 0 ? n_base : 1), nq = (size_t)(n_query > 0 ? n_query : 1);
+    const size_t b_bytes = 4 * (size_t)p.base_stride * nb, q_bytes = 4 * (size_t)p.query_stride * nq;
+    // base | query | labels | records out | order | mark | seg4, each 256-byte aligned
+    const size_t o_q = align_up(b_bytes, 256), o_lab = o_q + align_up(q_bytes, 256), o_out = o_lab + align_up(4 * nb, 256),
+                 o_ord = o_out + align_up(b_bytes, 256), o_mark = o_ord + align_up(4 * nb, 256), o_seg = o_mark + align_up(nb, 256);
+    unsigned char* d = nullptr;
+    if (hipMalloc(&d, o_seg + 32) != hipSuccess) return fail(c, SCVOD_ERR_HIP, "scvod_map_split: no device memory for %d + %d points", n_base, n_query);
+    int rc = SCVOD_OK;
+    hipStream_t st = c->stream;
+    if (n_base > 0 && hipMemcpyAsync(d, h_base, 4 * (size_t)p.base_stride * n_base, hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(c, SCVOD_ERR_HIP, "scvod_map_split: upload failed");
+    if (rc == SCVOD_OK && n_query > 0 && hipMemcpyAsync(d + o_q, h_query, 4 * (size_t)p.query_stride * n_query, hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(c, SCVOD_ERR_HIP, "scvod_map_split: upload failed");
+    if (rc == SCVOD_OK && n_base > 0 && h_base_label && hipMemcpyAsync(d + o_lab, h_base_label, 4 * (size_t)n_base, hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(c, SCVOD_ERR_HIP, "scvod_map_split: upload failed");
+    if (rc == SCVOD_OK)
+        rc = scvod_map_split_device(c, (const float*)d, h_base_label ? (const uint32_t*)(d + o_lab) : nullptr, n_base, (const float*)(d + o_q),
+                                    n_query, &p, d + o_mark, (int32_t*)(d + o_ord), (int64_t*)(d + o_seg), (float*)(d + o_out), nullptr, nullptr,
+                                    nullptr, nullptr, st);
+    if (rc == SCVOD_OK && n_base > 0) {
+        bool ok = true;
+        if (h_mark) ok &= hipMemcpyAsync(h_mark, d + o_mark, (size_t)n_base, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (h_order) ok &= hipMemcpyAsync(h_order, d + o_ord, 4 * (size_t)n_base, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (h_base_out) ok &= hipMemcpyAsync(h_base_out, d + o_out, 4 * (size_t)p.base_stride * n_base, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (!ok) rc = fail(c, SCVOD_ERR_HIP, "scvod_map_split: download failed");
+    }
+    if (rc == SCVOD_OK && h_seg4 && hipMemcpyAsync(h_seg4, d + o_seg, 32, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = fail(c, SCVOD_ERR_HIP, "scvod_map_split: download failed");
+    if (hipStreamSynchronize(st) != hipSuccess && rc == SCVOD_OK) rc = fail(c, SCVOD_ERR_HIP, "scvod_map_split: the stream failed");
+    hipFree(d);
+    return rc;
+}
 
 }  // extern "C"

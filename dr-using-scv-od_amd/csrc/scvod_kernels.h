@@ -440,5 +440,31 @@ void launch_class_score(const float* gt_xyz, const uint32_t* gt_label, int32_t n
                         const uint8_t* est_keep, int32_t n_est, const CsLists& L, float cell, float max_dist, int32_t rings, int32_t buckets,
                         int* work, unsigned long long* counters, uint8_t* point_result, hipStream_t st);
 
+// a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the evaluation's (ev_buckets, ev_grid_ints)
+// over the base cloud with the caller's cell edge; work: sp_work_bytes bytes; stats: the 8 words of scvod_map_split_stats, written by
+// every launch.  The optional outputs of SpJob are nullptr when not asked for; mark == nullptr: a byte array inside `work`
+constexpr int kSpTile = 2048;  // base points per tile of the partition (k_exp_count's)
+struct SpJob {
+    const float* base;
+    const uint32_t* base_label;
+    const float* query;
+    int32_t n_base, n_query, base_stride, query_stride, max_rings, n_reject;
+    uint16_t reject[16];
+    uint8_t* mark;
+    int32_t* order;
+    int64_t* seg4;
+    float* base_out;
+    const uint32_t* payload_in;
+    uint32_t* payload_out;
+    int32_t* nn_idx;
+    float* nn_sq;
+    // filled by launch_map_split: the lists of the second and the third pass
+    int *n_list1, *list1_q, *list1_bi;
+    float* list1_best;
+    int *n_list2, *list2_q;
+};
+size_t sp_work_bytes(int32_t buckets, int32_t n_base, int32_t n_query);
+void launch_map_split(SpJob J, float cell, int32_t buckets, void* work, unsigned long long* stats, hipStream_t st);
+
 }  // namespace scvod
 #endif

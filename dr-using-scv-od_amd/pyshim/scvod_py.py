@@ -105,6 +105,17 @@ CLASS_ESTIMATE = ("other", "ground", "building", "tree", "none")
 CLASS_P = 32
 
 
+class SplitParams(C.Structure):
+    """struct scvod_split_params (include/scvod.h)"""
+    _fields_ = [("cell", C.c_float), ("max_rings", C.c_int32), ("base_stride", C.c_int32), ("query_stride", C.c_int32),
+                ("n_reject_classes", C.c_int32), ("reject_classes", C.c_uint16 * 16)]
+
+
+# scvod_map_split_device's byte per base point; the partition's segments come in the order HIT, MISS, GATED
+SPLIT_MISS, SPLIT_HIT, SPLIT_GATED = 0, 1, 2
+SPLIT_STATS = ("n_hit", "n_miss", "n_gated", "pass1_queries", "ring_queries", "exhaustive_queries")
+
+
 class ScanResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_points", "n_ground", "n_nonground", "n_dropped", "n_apri", "n_rejected",
                                           "n_voxels", "n_patches")] + \
@@ -276,6 +287,11 @@ def load_lib():
         "scvod_score_classes_stats": (C.c_int, [vp, C.POINTER(ClassResult)]),
         "scvod_score_classes_pass2_queries": (i64, [vp]),
         "scvod_score_classes_scratch_bytes": (i64, [vp]),
+        "scvod_split_params_default": (None, [C.POINTER(SplitParams)]),
+        "scvod_map_split_device": (C.c_int, [vp, vp, vp, i32, vp, i32, C.POINTER(SplitParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "scvod_map_split_stats": (C.c_int, [vp, vp]),
+        "scvod_map_split_scratch_bytes": (i64, [vp]),
+        "scvod_map_split": (C.c_int, [vp, vp, vp, i32, vp, i32, C.POINTER(SplitParams), vp, vp, vp, vp]),
         "scvod_batch_voxelgrid": (C.c_int, [vp, vp, vp, vp, i32, vp, f32, vp, i64, vp, vp]),
         "scvod_voxelgrid": (C.c_int, [vp, vp, vp, i32, vp, f32, vp, i32, vp]),
         "scvod_stack_offsets": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp]),
@@ -313,7 +329,9 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_batch_score_classes", "scvod_score_classes_stats", "scvod_score_classes_pass2_queries",
                     "scvod_score_classes_scratch_bytes",
                     "scvod_stack_offsets", "scvod_pose_from_matrix", "scvod_batch_stack_scans", "scvod_stack_scans",
-                    "scvod_stack_scratch_bytes"]
+                    "scvod_stack_scratch_bytes",
+                    "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
+                    "scvod_map_split"]
 
 
 def eval_params_default(voxelsize=None, dynamic_classes=None):
@@ -373,6 +391,24 @@ def class_finish(conf_and_far):
     r = ClassResult()
     load_lib().scvod_class_finish(cnt.ctypes.data_as(C.c_void_p), C.byref(r))
     return _class_dict(r)
+
+
+def split_params_default(cell=None, max_rings=None, base_stride=None, query_stride=None, reject_classes=None):
+    """scvod_split_params with the defaults (cell 0.2, max_rings 3, packed xyz on both sides, no reject class), overridden by keyword;
+    reject_classes=(252,) is the gate of SSC::segDF's evaluation block"""
+    p = SplitParams()
+    load_lib().scvod_split_params_default(C.byref(p))
+    if cell is not None:
+        p.cell = float(cell)
+    for name, v in (("max_rings", max_rings), ("base_stride", base_stride), ("query_stride", query_stride)):
+        if v is not None:
+            setattr(p, name, int(v))
+    if reject_classes is not None:
+        cl = [int(v) for v in reject_classes]
+        p.n_reject_classes = len(cl)  # (more than 16: the library refuses the call)
+        for k in range(16):
+            p.reject_classes[k] = cl[k] if k < len(cl) else 0
+    return p
 
 
 def feature_params(**kw):
@@ -1025,6 +1061,47 @@ class Ctx:
     def score_classes_scratch_bytes(self):
         """device scratch of the class scores on this ctx (not part of arena_bytes or evaluate_scratch_bytes)"""
         return int(self.lib.scvod_score_classes_scratch_bytes(self.h))
+
+    # ---- a map split by nearest-neighbour hits on the device (include/scvod.h: scvod_map_split_device ...) ----
+    def map_split_device(self, d_base, d_query, params=None, d_base_label=None, d_mark=None, d_order=None, d_seg4=None, d_base_out=None,
+                         d_payload_in=None, d_payload_out=None, d_nn_idx=None, d_nn_sqdist=None, stream=None):
+        """every query point marks its nearest base point; the base cloud is handed out as HIT | MISS | GATED segments in base order.
+        d_base / d_query: contiguous torch float32 [n, 3] or [n, 4] CUDA tensors (the strides of `params` are set from their shapes);
+        d_base_label and the payloads 4-byte words per base point; d_mark uint8 [n_base], d_order int32 [n_base], d_seg4 int64 [4],
+        d_base_out like d_base, d_nn_idx int32 / d_nn_sqdist float32 [n_query]; every output may be None.  Asynchronous on `stream`:
+        map_split_stats()"""
+        p = SplitParams()
+        if params is not None:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+        else:
+            self.lib.scvod_split_params_default(C.byref(p))
+        for t, name in ((d_base, "base_stride"), (d_query, "query_stride")):
+            assert t.is_contiguous() and t.element_size() == 4 and t.dim() == 2 and t.shape[1] in (3, 4)
+            setattr(p, name, int(t.shape[1]))
+        n_base, n_query = int(d_base.shape[0]), int(d_query.shape[0])
+        for t, size in ((d_base_label, 4), (d_payload_in, 4), (d_payload_out, 4), (d_mark, 1), (d_order, 4)):
+            assert t is None or (t.numel() >= n_base and t.element_size() == size and t.is_contiguous())
+        for t in (d_nn_idx, d_nn_sqdist):
+            assert t is None or (t.numel() >= n_query and t.element_size() == 4 and t.is_contiguous())
+        assert d_seg4 is None or (d_seg4.numel() >= 4 and d_seg4.element_size() == 8)
+        assert d_base_out is None or (d_base_out.numel() >= d_base.numel() and d_base_out.element_size() == 4 and d_base_out.is_contiguous())
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        self._chk(self.lib.scvod_map_split_device(self.h, ptr(d_base), ptr(d_base_label), n_base, ptr(d_query), n_query, C.byref(p),
+                                                  ptr(d_mark), ptr(d_order), ptr(d_seg4), ptr(d_base_out), ptr(d_payload_in),
+                                                  ptr(d_payload_out), ptr(d_nn_idx), ptr(d_nn_sqdist), C.c_void_p(stream or 0)))
+
+    def map_split_stats(self):
+        """n_hit, n_miss, n_gated and the queries finished by the 27-cell, the ring and the exhaustive pass of the last
+        map_split_device; synchronises its stream"""
+        out = np.zeros(8, np.int64)
+        self._chk(self.lib.scvod_map_split_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(zip(SPLIT_STATS, (int(v) for v in out)))
+
+    def map_split_scratch_bytes(self):
+        """device scratch of the split on this ctx (not part of arena_bytes, evaluate_scratch_bytes or score_classes_scratch_bytes)"""
+        return int(self.lib.scvod_map_split_scratch_bytes(self.h))
 
     def classify_map_device(self, d_orig_xyz, d_pred_static, d_static_xyz, d_dynamic_xyz, r15=0.15, r10=0.1, d_class=None, stream=None):
         """metric.classify_map_points on the device: contiguous torch float32 [n, 3] clouds, d_pred_static one byte per point of the

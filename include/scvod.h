@@ -893,6 +893,77 @@ int scvod_classify_map_device(scvod_ctx* ctx, const float* d_orig_xyz, const uin
  * first call. */
 int scvod_classify_map_stats(scvod_ctx* ctx, int64_t* h_out5);
 
+/* ---- a map split by the nearest-neighbour hits of a cleaned cloud, on the device (opt-in: nothing runs or is allocated unless it is
+ * called) ---------------------------------------------------------------------------------------------------------------------------
+ * Reference analogue: src/erasor_dynamic.cpp:16-35 (the original points that no point of a remover's static map has as its nearest
+ * neighbour are the dynamic cloud) and the evaluation block of SSC::segDF, ssc.cpp:1511-1540 (the same look-up from cloud_eva_static
+ * into the labelled original cloud; the hit points, without those labelled 252, are the _static.pcd analysis.py reads).  It builds what
+ * scvod_evaluate_device, scvod_classify_map_device and scvod_score_classes_device take when the cleaned cloud comes from outside.
+ *   per query       its nearest base point over the WHOLE base cloud -- no radius -- by the squared distance d = (dx*dx + dy*dy) + dz*dz in
+ *                   fp32 with dx = base.x - query.x (the evaluation's expression, no contraction), ties to the lowest base index; an
+ *                   empty base gives index -1 and distance +inf.  The result does not depend on cell, on max_rings, on the order inside
+ *                   a bucket or on which pass finished the query
+ *   per base point  one byte: SCVOD_SPLIT_MISS when no query chose it; otherwise SCVOD_SPLIT_GATED when n_reject_classes > 0 and
+ *                   (d_base_label[i] & 0xFFFF) is in reject_classes; otherwise SCVOD_SPLIT_HIT.  A function of the point alone, never of
+ *                   how many queries chose it or in which order.  mark == SCVOD_SPLIT_HIT is scvod_classify_map_device's d_pred_static
+ *   partition       the base indices of the HIT points ascending, then of the MISS points ascending, then of the GATED points ascending
+ *                   (a stable three-way partition).  Without a reject list the MISS segment is erasor_dynamic.cpp's dynamic_cloud
+ *                   (ExtractIndices, negative); with {252} the HIT segment is evaluate_static of ssc.cpp:1533-1534 (sampleVec: sort +
+ *                   unique, so ascending too)
+ * The look-up is a hash grid of cell edge `cell` over the base cloud in three passes: the 27 cells around a query (finished when its
+ * candidate is closer than 0.99 cell edges), the rings 2 .. max_rings of cells (finished after ring r when closer than 0.99 r cell
+ * edges), and for what is left an exhaustive scan of the base cloud, n_base records per such query: exact for any input, counted by
+ * scvod_map_split_stats, and not a design target -- a cleaned map, where every query has a base point within a cell or two, never
+ * reaches it.  All counters are integer sums and the partition is stable: the same bytes on every run. */
+#define SCVOD_SPLIT_MISS 0   /* no query chose this base point                                   */
+#define SCVOD_SPLIT_HIT 1    /* the nearest base point of at least one query                      */
+#define SCVOD_SPLIT_GATED 2  /* hit, but its label & 0xFFFF is in reject_classes (ssc.cpp:1524)   */
+typedef struct scvod_split_params {
+    float cell;                  /* edge of the hash grid's cells; default 0.2; positive, finite  */
+    int32_t max_rings;           /* last ring of cells the ring pass walks; default 3; 1..8       */
+    int32_t base_stride;         /* floats per base record: 3 (packed xyz) or 4 (xyzi, 16-byte aligned); default 3 */
+    int32_t query_stride;        /* the same for the query cloud; default 3                       */
+    int32_t n_reject_classes;    /* 0..16; default 0 (erasor_dynamic.cpp); segDF's block: {252}   */
+    uint16_t reject_classes[16];
+} scvod_split_params;
+/* cell 0.2, max_rings 3, both strides 3, no reject class */
+void scvod_split_params_default(scvod_split_params* p);
+/* d_base [n_base] and d_query [n_query] records of base_stride / query_stride floats; d_base_label [n_base] uint32, NULL exactly when
+ * n_reject_classes == 0.  params NULL = the defaults; the struct is copied before the call returns.  Outputs, each optional (NULL):
+ *   d_mark         [n_base] the byte above
+ *   d_order        [n_base] int32: the partition
+ *   d_seg4         four int64 ON THE DEVICE: {0, n_hit, n_hit + n_miss, n_base}, the bounds of the three segments -- a consumer on the
+ *                  same stream needs no host read
+ *   d_base_out     [n_base * base_stride] floats: the base records in the partition's order, bit for bit (with stride 4 the intensity
+ *                  word travels: NaN payload bits survive); must not overlap d_base
+ *   d_payload_out  [n_base] one uint32 per base point in that order, from d_payload_in [n_base] (e.g. SemanticKITTI labels)
+ *   d_nn_idx, d_nn_sqdist  [n_query] the neighbour of every query and its squared distance
+ * Every output holds exactly n_base (n_query) entries: there is no capacity argument and no overflow state.  Stream-ordered (stream
+ * NULL = the ctx's stream), never synchronises with the host; each call overwrites the stats of the one before, and the split calls
+ * of one ctx must be ordered among themselves (they share their scratch).  Argument errors (NULL ctx, negative sizes, a NULL array
+ * of a non-empty cloud, a stride other than 3 or 4, a stride-4 pointer that is not 16-byte aligned, d_payload_out without
+ * d_payload_in, d_base_out overlapping d_base, more than 16 classes, a reject list without labels, a cell that is not positive and
+ * finite, max_rings outside 1..8) are SCVOD_ERR_INVALID before any device is looked for; non-finite coordinates are unspecified.
+ * Scratch (the grid, 20 bytes per query for the lists of the second and third pass, a mark byte per base point, 24 bytes per
+ * 2048-point tile, 8 stats words) is an allocation of its own, grow-only, freed by scvod_destroy and NOT part of scvod_arena_bytes,
+ * scvod_evaluate_scratch_bytes or scvod_score_classes_scratch_bytes; no result of the last batch changes.  Only a call that needs more
+ * than any before waits for the split in flight before it grows. */
+int scvod_map_split_device(scvod_ctx* ctx, const float* d_base, const uint32_t* d_base_label, int32_t n_base, const float* d_query,
+                           int32_t n_query, const scvod_split_params* params, uint8_t* d_mark, int32_t* d_order, int64_t* d_seg4,
+                           float* d_base_out, const uint32_t* d_payload_in, uint32_t* d_payload_out, int32_t* d_nn_idx,
+                           float* d_nn_sqdist, void* stream);
+/* h_out8 = {n_hit, n_miss, n_gated, queries finished by the 27-cell pass, by the ring pass, by the exhaustive pass, 0, 0} of the last
+ * scvod_map_split_device.  Synchronises that call's stream.  SCVOD_ERR_STATE before the first split. */
+int scvod_map_split_stats(scvod_ctx* ctx, int64_t* h_out8);
+/* bytes of device scratch the split holds on this ctx (0 before the first call) */
+int64_t scvod_map_split_scratch_bytes(scvod_ctx* ctx);
+/* The same for clouds in host memory (what the host tool scvod_map_split calls: it links this library only): the clouds are uploaded,
+ * split on the device and the outputs asked for (h_mark, h_order, h_seg4 [4], h_base_out; each may be NULL) downloaded.  Synchronous.
+ * The device buffers live for the duration of the call. */
+int scvod_map_split(scvod_ctx* ctx, const float* h_base, const uint32_t* h_base_label, int32_t n_base, const float* h_query,
+                    int32_t n_query, const scvod_split_params* params, uint8_t* h_mark, int32_t* h_order, int64_t* h_seg4,
+                    float* h_base_out);
+
 /* ---- the recognised ground / building / tree classes against labelled truth, on the device (opt-in: nothing runs or is allocated
  * unless it is called) ----------------------------------------------------------------------------------------------------------------
  * Reference analogue: src/plotObject.cpp:87-146, the tool behind the per-class table of doc/note.txt:57-78.  Every ground-truth point
