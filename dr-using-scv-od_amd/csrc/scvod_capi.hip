@@ -8,6 +8,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -32,6 +34,14 @@ struct UploadSlot {
     size_t cap = 0;
     hipEvent_t ev = nullptr;
     bool used = false;
+};
+
+// a grow-only device block and the stream of the last call that used it (scratch_reserve waits for it before the block moves)
+struct Scratch {
+    void* buf = nullptr;
+    size_t cap = 0;
+    hipStream_t stream = nullptr;
+    bool ran = false;
 };
 
 struct scvod_ctx {
@@ -192,33 +202,21 @@ struct scvod_ctx {
     bool shape_ran = false;
     // evaluation against labelled truth (scvod_evaluate_device / scvod_batch_evaluate / scvod_classify_map_device, scvod_eval.hip): one
     // grow-only scratch block and 16 counter words of their own (a grown block must not take an unread result with it); not part of the arena
-    void* ev_buf = nullptr;
-    size_t ev_cap = 0;
+    Scratch ev;      // stream / ran: the last evaluation (scvod_evaluate_stats waits for it)
+    Scratch ev_cls;  // stream / ran of the last scvod_classify_map_device alone: it works in ev's block
     unsigned long long* ev_counters = nullptr;  // [8] evaluation, [8] map classes
-    hipStream_t ev_stream = nullptr;   // stream of the last evaluation (scvod_evaluate_stats waits for it; a growing block too)
-    hipStream_t ev_cls_stream = nullptr;
-    bool ev_ran = false, ev_cls_ran = false;
     // class scores against labelled truth (scvod_score_classes_device / scvod_batch_score_classes, scvod_classes.hip): a grow-only block
     // and 24 counter words of their own, allocated by the first call
-    void* cs_buf = nullptr;
-    size_t cs_cap = 0;
+    Scratch cs;  // stream / ran: the last scoring call (scvod_score_classes_stats waits for it)
     unsigned long long* cs_counters = nullptr;
-    hipStream_t cs_stream = nullptr;   // stream of the last scoring call (scvod_score_classes_stats waits for it; a growing block too)
-    bool cs_ran = false;
     // scan stacking (scvod_batch_stack_scans, scvod_stack.hip): the segment and tile tables, one grow-only block of their own allocated
     // by the first call; not part of the arena
-    void* stk_buf = nullptr;
-    size_t stk_cap = 0;
-    hipStream_t stk_stream = nullptr;  // stream of the last stacking call (a growing block waits for it)
-    bool stk_ran = false;
+    Scratch stk;
     std::vector<unsigned char> stk_host;  // the tables as built on the host (scratch of the call; the upload is staged from a copy)
     // map split by nearest-neighbour hits (scvod_map_split_device, scvod_split.hip): a grow-only block and 8 stats words of their own,
     // allocated by the first call; not part of the arena, not the evaluation's and not the class scores'
-    void* sp_buf = nullptr;
-    size_t sp_cap = 0;
+    Scratch sp;  // stream / ran: the last split (scvod_map_split_stats waits for it)
     unsigned long long* sp_stats = nullptr;
-    hipStream_t sp_stream = nullptr;   // stream of the last split (scvod_map_split_stats waits for it; a growing block too)
-    bool sp_ran = false;
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -248,8 +246,7 @@ struct scvod_ctx {
     bool types_valid = false;
     hipStream_t last_stream = nullptr;
     // host staging for scvod_scan_result
-    void* nn_buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // scvod_nn_search scratch (grow-only)
-    size_t nn_cap[6] = {0, 0, 0, 0, 0, 0};
+    Scratch nn[6];  // scvod_nn_search scratch; `ran` stays false: the host forms synchronise before they return
     void* stage = nullptr;       // pinned host block holding the arrays of the last scvod_scan_result
     size_t stage_bytes = 0;
     // timing
@@ -1479,16 +1476,16 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->obj_words) hipFree(c->obj_words);
     if (c->obj_sort_tmp) hipFree(c->obj_sort_tmp);
     if (c->shape_stats) hipFree(c->shape_stats);
-    if (c->ev_buf) hipFree(c->ev_buf);
+    if (c->ev.buf) hipFree(c->ev.buf);
     if (c->ev_counters) hipFree(c->ev_counters);
-    if (c->cs_buf) hipFree(c->cs_buf);
+    if (c->cs.buf) hipFree(c->cs.buf);
     if (c->cs_counters) hipFree(c->cs_counters);
-    if (c->stk_buf) hipFree(c->stk_buf);
-    if (c->sp_buf) hipFree(c->sp_buf);
+    if (c->stk.buf) hipFree(c->stk.buf);
+    if (c->sp.buf) hipFree(c->sp.buf);
     if (c->sp_stats) hipFree(c->sp_stats);
     if (c->stage) hipHostFree(c->stage);
-    for (void* b : c->nn_buf)
-        if (b) hipFree(b);
+    for (const Scratch& s : c->nn)
+        if (s.buf) hipFree(s.buf);
     delete c;
 }
 
@@ -2903,16 +2900,40 @@ int scvod_voxelgrid(scvod_ctx* c, const float* h_xyzi, const uint32_t* h_labels,
     return SCVOD_OK;
 }
 
-// grow-only device scratch owned by the ctx (no allocation on the steady-state path, nothing to leak on an error return)
-static int nn_reserve(scvod_ctx* c, int slot, size_t bytes, void** out) {
-    if (bytes > c->nn_cap[slot]) {
-        if (c->nn_buf[slot]) hipFree(c->nn_buf[slot]);
-        c->nn_buf[slot] = nullptr;
-        c->nn_cap[slot] = 0;
-        HIPCHK(c, hipMalloc(&c->nn_buf[slot], bytes + bytes / 4));
-        c->nn_cap[slot] = bytes + bytes / 4;
+// grow-only device scratch owned by the ctx (no allocation on the steady-state path, nothing to leak on an error return): at least
+// `bytes` in s.  A block that grows is freed first, after the calls in flight that may still read it: the last one on s, and on
+// also_wait where a second kind of call works in the same block
+static int scratch_reserve(scvod_ctx* c, Scratch& s, size_t bytes, const Scratch* also_wait = nullptr) {
+    if (bytes <= s.cap) return SCVOD_OK;
+    if (s.buf) {
+        if (s.ran) HIPCHK(c, hipStreamSynchronize(s.stream));
+        if (also_wait && also_wait->ran) HIPCHK(c, hipStreamSynchronize(also_wait->stream));
+        hipFree(s.buf);
+        s.buf = nullptr;
+        s.cap = 0;
     }
-    *out = c->nn_buf[slot];
+    const size_t grown = bytes + bytes / 4;
+    HIPCHK(c, hipMalloc(&s.buf, grown));
+    s.cap = grown;
+    return SCVOD_OK;
+}
+
+// the counter words of a stage, allocated and cleared by its first call.  An allocation of their own: a grown scratch block must not
+// take an unread result with it
+static int counter_block(scvod_ctx* c, unsigned long long** words, int n) {
+    if (*words) return SCVOD_OK;
+    HIPCHK(c, hipMalloc(words, sizeof(unsigned long long) * n));
+    HIPCHK(c, hipMemset(*words, 0, sizeof(unsigned long long) * n));
+    return SCVOD_OK;
+}
+
+// n (<= 24) counter words as they are once the work on `stream` is done
+static int read_counters(scvod_ctx* c, const unsigned long long* d_words, int n, hipStream_t stream, int64_t* out) {
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long h[24] = {0};
+    HIPCHK(c, hipMemcpyAsync(h, d_words, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    for (int k = 0; k < n; ++k) out[k] = (int64_t)h[k];
     return SCVOD_OK;
 }
 
@@ -2920,14 +2941,11 @@ static int nn_run(scvod_ctx* c, const float* d_map, int32_t n_map, const float* 
                   int32_t* d_idx, float* d_sq, uint8_t* d_w, const float origin[3], int bounded, hipStream_t st) {
     // grid: cell edge >= radius (so `within` is decided by the 27-cell probe); the origin only shifts the hash
     const float cell = radius > 0.2f ? radius : 0.2f;
-    int32_t buckets = 1024;
-    while (buckets < 2 * n_map && buckets < (1 << 26)) buckets <<= 1;
+    const int32_t buckets = grid_buckets(n_map);
     const size_t nm = n_map ? n_map : 1, nq = n_query ? n_query : 1;
     const size_t work_ints = 3 * (size_t)buckets + nm + nq + 8 + (size_t)buckets / 1024 + 1;
-    void* d_work = nullptr;
-    int rc = nn_reserve(c, 5, work_ints * sizeof(int), &d_work);
-    if (rc) return rc;
-    launch_nn(d_map, n_map, d_q, n_query, radius, d_idx, d_sq, d_w, origin, cell, buckets, (int*)d_work, bounded, st);
+    if (int rc = scratch_reserve(c, c->nn[5], work_ints * sizeof(int))) return rc;
+    launch_nn(d_map, n_map, d_q, n_query, radius, d_idx, d_sq, d_w, origin, cell, buckets, (int*)c->nn[5].buf, bounded, st);
     HIPCHK(c, hipGetLastError());
     return SCVOD_OK;
 }
@@ -2942,11 +2960,11 @@ static int nn_search_host(scvod_ctx* c, const float* h_map_xyz, int32_t n_map, c
     for (int i = 0; i < n_map; ++i)
         for (int k = 0; k < 3; ++k)
             if (i == 0 || h_map_xyz[3 * (size_t)i + k] < origin[k]) origin[k] = h_map_xyz[3 * (size_t)i + k];
-    void *d_map, *d_q, *d_sq, *d_idx, *d_w;
+    const size_t bytes[5] = {nm * 12, nq * 12, nq * 4, nq * 4, nq};
     int rc;
-    if ((rc = nn_reserve(c, 0, nm * 12, &d_map)) || (rc = nn_reserve(c, 1, nq * 12, &d_q)) || (rc = nn_reserve(c, 2, nq * 4, &d_sq)) ||
-        (rc = nn_reserve(c, 3, nq * 4, &d_idx)) || (rc = nn_reserve(c, 4, nq, &d_w)))
-        return rc;
+    for (int k = 0; k < 5; ++k)
+        if ((rc = scratch_reserve(c, c->nn[k], bytes[k]))) return rc;
+    void *d_map = c->nn[0].buf, *d_q = c->nn[1].buf, *d_sq = c->nn[2].buf, *d_idx = c->nn[3].buf, *d_w = c->nn[4].buf;
     hipStream_t st = c->stream;
     if (n_map) HIPCHK(c, hipMemcpyAsync(d_map, h_map_xyz, (size_t)n_map * 12, hipMemcpyHostToDevice, st));
     if (n_query) HIPCHK(c, hipMemcpyAsync(d_q, h_query_xyz, (size_t)n_query * 12, hipMemcpyHostToDevice, st));
@@ -2958,6 +2976,8 @@ static int nn_search_host(scvod_ctx* c, const float* h_map_xyz, int32_t n_map, c
         if (h_nn_idx) HIPCHK(c, hipMemcpy(h_nn_idx, d_idx, (size_t)n_query * 4, hipMemcpyDeviceToHost));
         if (h_nn_sqdist) HIPCHK(c, hipMemcpy(h_nn_sqdist, d_sq, (size_t)n_query * 4, hipMemcpyDeviceToHost));
         if (h_within) HIPCHK(c, hipMemcpy(h_within, d_w, (size_t)n_query, hipMemcpyDeviceToHost));
+        // (an empty map: k_nn_brute leaves distance 0 beside index -1; the radius search promises +inf)
+        if (bounded && n_map == 0 && h_nn_sqdist) std::fill(h_nn_sqdist, h_nn_sqdist + n_query, std::numeric_limits<float>::infinity());
     }
     return SCVOD_OK;
 }
@@ -3028,29 +3048,71 @@ static int ev_params(scvod_ctx* c, const scvod_eval_params* params, EvClasses* K
     return SCVOD_OK;
 }
 
-// the evaluation's scratch block of at least `bytes` (grow-only; growing waits for the evaluations in flight, which read the old one)
+// the evaluation's scratch block of at least `bytes` (growing waits for the evaluations and the map classifications in flight)
 static int ev_reserve(scvod_ctx* c, size_t bytes) {
-    if (!c->ev_counters) {
-        HIPCHK(c, hipMalloc(&c->ev_counters, sizeof(unsigned long long) * 16));
-        HIPCHK(c, hipMemset(c->ev_counters, 0, sizeof(unsigned long long) * 16));
-    }
-    if (bytes > c->ev_cap) {
-        if (c->ev_buf) {
-            if (c->ev_ran) HIPCHK(c, hipStreamSynchronize(c->ev_stream));
-            if (c->ev_cls_ran) HIPCHK(c, hipStreamSynchronize(c->ev_cls_stream));
-            hipFree(c->ev_buf);
-            c->ev_buf = nullptr;
-            c->ev_cap = 0;
-        }
-        HIPCHK(c, hipMalloc(&c->ev_buf, bytes + bytes / 4));
-        c->ev_cap = bytes + bytes / 4;
-    }
-    return SCVOD_OK;
+    if (int rc = counter_block(c, &c->ev_counters, 16)) return rc;
+    return scratch_reserve(c, c->ev, bytes, &c->ev_cls);
 }
 
-static float ev_cell(double radius) {  // nn_run's rule
+static float ev_cell(double radius) {  // the cell edge is at least the radius, so the 27-cell probe of scvod_grid.h decides it
     const float r = (float)radius;
     return r > 0.2f ? r : 0.2f;
+}
+
+// the batch as a cloud against itself, what scvod_batch_evaluate and scvod_batch_score_classes (`who`) share: the world position of
+// every input point of the batch, its keep byte (scvod_batch_export_points' rule for `flags`, and the bits of keep_extra) and its
+// SCVOD_PT_* byte (class_byte: the class byte where the region growing ran), in the stage's scratch block:
+//     world xyz | keep byte | label or class byte | pose matrices | the stage's work area of work_bytes(buckets, n)
+// The checks come in the order arguments, flags, parameters (parse_params), state of the batch, device.
+struct BatchCloud {
+    float* world;
+    uint8_t *keep, *byte;
+    int* work;
+    int32_t n, buckets;
+    hipStream_t st;
+};
+static int batch_cloud(scvod_ctx* c, const char* who, const uint32_t* d_gt_label, const float* h_poses, int32_t flags,
+                       const std::function<int()>& parse_params, uint32_t keep_extra, bool class_byte, Scratch& block, int (*reserve)(scvod_ctx*, size_t),
+                       size_t (*work_bytes)(int32_t buckets, int32_t n), void* stream, BatchCloud* out) {
+    if (!d_gt_label || !h_poses) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (flags & ~(SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED | SCVOD_MAP_IGNORE_DYNAMIC))
+        return fail(c, SCVOD_ERR_INVALID, "%s takes SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED and SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", who, flags);
+    if (int rc = parse_params()) return rc;
+    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
+    if (int rc = export_check(c, use_dyn, who)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    const int B = c->A.n_scans;
+    const int32_t N = (int32_t)c->A.total_pts;
+    const int32_t buckets = grid_buckets(N);
+    const size_t n1 = (size_t)(N > 0 ? N : 1);
+    const size_t off_keep = align_up(12 * n1, 256), off_byte = off_keep + align_up(n1, 256), off_pose = off_byte + align_up(n1, 256),
+                 off_work = off_pose + align_up(sizeof(float) * 12 * (size_t)(B > 0 ? B : 1), 256);
+    if (int rc = reserve(c, off_work + work_bytes(buckets, N))) return rc;
+    unsigned char* base = (unsigned char*)block.buf;
+    float* world = (float*)base;
+    uint8_t* keep = base + off_keep;
+    uint8_t* byte = base + off_byte;
+    float* pose = (float*)(base + off_pose);
+    if (B > 0) {  // pcl::getTransformation per scan, staged before the call returns: h_poses is the caller's again at once
+        std::vector<float> T((size_t)12 * B);
+        for (int s = 0; s < B; ++s) scvod_pose_matrix(h_poses + 6 * s, T.data() + 12 * s);
+        if (int rc = staged_upload(c, T.data(), sizeof(float) * T.size(), pose, st)) return rc;
+    }
+    uint32_t keep_mask = (1u << SCVOD_PT_UNCLUSTERED) | (1u << SCVOD_PT_STATIC_OTHER) | (1u << SCVOD_PT_STATIC_CAR) | keep_extra;
+    if (!(flags & SCVOD_MAP_NO_GROUND)) keep_mask |= 1u << SCVOD_PT_GROUND;
+    if (!(flags & SCVOD_MAP_NO_REJECTED)) keep_mask |= 1u << SCVOD_PT_REJECTED;
+    if (!use_dyn) keep_mask |= 1u << SCVOD_PT_DYNAMIC;
+    if (N > 0) {
+        HIPCHK(c, hipMemsetAsync(byte, SCVOD_PT_DROPPED, (size_t)N, st));
+        if (class_byte && c->rg_done)
+            launch_point_classes(c->A, c->rg.cls, byte, use_dyn, st);
+        else
+            launch_point_labels(c->A, byte, use_dyn, st);
+        launch_eval_world(c->A, byte, keep_mask, pose, world, keep, st);  // (k_ev_world: the export's expression and keep rule)
+    }
+    *out = BatchCloud{world, keep, byte, (int*)(base + off_work), N, buckets, st};
+    return SCVOD_OK;
 }
 
 int scvod_evaluate_device(scvod_ctx* c, const float* d_gt_xyz, const uint32_t* d_gt_label, int32_t n_gt, const float* d_est_xyz,
@@ -3063,80 +3125,45 @@ int scvod_evaluate_device(scvod_ctx* c, const float* d_gt_xyz, const uint32_t* d
     if (int rc = ev_params(c, params, &K, &vs)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const int32_t buckets = ev_buckets(n_est);
-    if (int rc = ev_reserve(c, sizeof(int) * ev_grid_ints(buckets, n_est))) return rc;
+    const int32_t buckets = grid_buckets(n_est);
+    if (int rc = ev_reserve(c, sizeof(int) * grid_work_ints(buckets, n_est))) return rc;
     launch_eval(d_gt_xyz, d_gt_label, n_gt, d_est_xyz, d_est_label, nullptr, n_est, vs * std::sqrt(3.0) / 2, K, ev_cell(vs), buckets,
-                (int*)c->ev_buf, c->ev_counters, d_point_result, st);
+                (int*)c->ev.buf, c->ev_counters, d_point_result, st);
     HIPCHK(c, hipGetLastError());
-    c->ev_stream = st;
-    c->ev_ran = true;
+    c->ev.stream = st;
+    c->ev.ran = true;
     return SCVOD_OK;
 }
 
 int scvod_batch_evaluate(scvod_ctx* c, const uint32_t* d_gt_label, const float* h_poses, int32_t flags, const scvod_eval_params* params,
                          uint8_t* d_point_result, void* stream) {
     if (!c) return SCVOD_ERR_INVALID;
-    if (!d_gt_label || !h_poses) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
-    if (flags & ~(SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED | SCVOD_MAP_IGNORE_DYNAMIC))
-        return fail(c, SCVOD_ERR_INVALID, "scvod_batch_evaluate takes SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED and SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", flags);
     EvClasses K;
     double vs;
-    if (int rc = ev_params(c, params, &K, &vs)) return rc;
-    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
-    if (int rc = export_check(c, use_dyn, "scvod_batch_evaluate")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
-    const int B = c->A.n_scans;
-    const int32_t N = (int32_t)c->A.total_pts;
-    const int32_t buckets = ev_buckets(N);
-    // world xyz | keep byte | label byte | pose matrices | grid
-    const size_t n1 = (size_t)(N > 0 ? N : 1);
-    const size_t off_keep = align_up(12 * n1, 256), off_lab = off_keep + align_up(n1, 256), off_pose = off_lab + align_up(n1, 256),
-                 off_grid = off_pose + align_up(sizeof(float) * 12 * (size_t)(B > 0 ? B : 1), 256);
-    if (int rc = ev_reserve(c, off_grid + sizeof(int) * ev_grid_ints(buckets, N))) return rc;
-    unsigned char* base = (unsigned char*)c->ev_buf;
-    float* world = (float*)base;
-    uint8_t* keep = base + off_keep;
-    uint8_t* lab = base + off_lab;
-    float* pose = (float*)(base + off_pose);
-    if (B > 0) {  // pcl::getTransformation per scan, staged before the call returns: h_poses is the caller's again at once
-        std::vector<float> T((size_t)12 * B);
-        for (int s = 0; s < B; ++s) scvod_pose_matrix(h_poses + 6 * s, T.data() + 12 * s);
-        if (int rc = staged_upload(c, T.data(), sizeof(float) * T.size(), pose, st)) return rc;
-    }
-    uint32_t keep_mask = (1u << SCVOD_PT_UNCLUSTERED) | (1u << SCVOD_PT_STATIC_OTHER) | (1u << SCVOD_PT_STATIC_CAR);  // scvod_batch_export_points' rule
-    if (!(flags & SCVOD_MAP_NO_GROUND)) keep_mask |= 1u << SCVOD_PT_GROUND;
-    if (!(flags & SCVOD_MAP_NO_REJECTED)) keep_mask |= 1u << SCVOD_PT_REJECTED;
-    if (!use_dyn) keep_mask |= 1u << SCVOD_PT_DYNAMIC;
-    if (N > 0) {
-        HIPCHK(c, hipMemsetAsync(lab, SCVOD_PT_DROPPED, (size_t)N, st));
-        launch_point_labels(c->A, lab, use_dyn, st);
-        launch_eval_world(c->A, lab, keep_mask, pose, world, keep, st);
-    }
-    launch_eval(world, d_gt_label, N, world, d_gt_label, keep, N, vs * std::sqrt(3.0) / 2, K, ev_cell(vs), buckets, (int*)(base + off_grid),
-                c->ev_counters, d_point_result, st);
+    BatchCloud W;
+    if (int rc = batch_cloud(c, "scvod_batch_evaluate", d_gt_label, h_poses, flags, [&] { return ev_params(c, params, &K, &vs); }, 0u, false, c->ev,
+                             ev_reserve, [](int32_t buckets, int32_t n) { return sizeof(int) * grid_work_ints(buckets, n); }, stream, &W))
+        return rc;
+    launch_eval(W.world, d_gt_label, W.n, W.world, d_gt_label, W.keep, W.n, vs * std::sqrt(3.0) / 2, K, ev_cell(vs), W.buckets, W.work,
+                c->ev_counters, d_point_result, W.st);
     HIPCHK(c, hipGetLastError());
-    c->ev_stream = st;
-    c->ev_ran = true;
+    c->ev.stream = W.st;
+    c->ev.ran = true;
     return SCVOD_OK;
 }
 
 int scvod_evaluate_stats(scvod_ctx* c, scvod_eval_result* out) {
     if (!c) return SCVOD_ERR_INVALID;
     if (!out) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
-    if (!c->ev_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_evaluate_device or scvod_batch_evaluate on this ctx yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h, c->ev_counters, sizeof(h), hipMemcpyDeviceToHost, c->ev_stream));
-    HIPCHK(c, hipStreamSynchronize(c->ev_stream));
+    if (!c->ev.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_evaluate_device or scvod_batch_evaluate on this ctx yet");
     int64_t counts[7];
-    for (int k = 0; k < 7; ++k) counts[k] = (int64_t)h[k];
+    if (int rc = read_counters(c, c->ev_counters, 7, c->ev.stream, counts)) return rc;
     scvod_eval_finish(counts, out);
     return SCVOD_OK;
 }
 
 int64_t scvod_evaluate_scratch_bytes(scvod_ctx* c) {
-    return c ? (int64_t)c->ev_cap + (c->ev_counters ? (int64_t)sizeof(unsigned long long) * 16 : 0) : 0;
+    return c ? (int64_t)c->ev.cap + (c->ev_counters ? (int64_t)sizeof(unsigned long long) * 16 : 0) : 0;
 }
 
 int scvod_classify_map_device(scvod_ctx* c, const float* d_orig_xyz, const uint8_t* d_pred_static, int32_t n, const float* d_static_xyz,
@@ -3150,28 +3177,23 @@ int scvod_classify_map_device(scvod_ctx* c, const float* d_orig_xyz, const uint8
         return fail(c, SCVOD_ERR_INVALID, "radii %g / %g: positive and at most 0.99 cell edges of 0.2", (double)r15, (double)r10);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const int32_t bs = ev_buckets(n_static), bd = ev_buckets(n_dynamic);
-    const size_t off_d = align_up(sizeof(int) * ev_grid_ints(bs, n_static), 256);
-    if (int rc = ev_reserve(c, off_d + sizeof(int) * ev_grid_ints(bd, n_dynamic))) return rc;
-    unsigned char* base = (unsigned char*)c->ev_buf;
+    const int32_t bs = grid_buckets(n_static), bd = grid_buckets(n_dynamic);
+    const size_t off_d = align_up(sizeof(int) * grid_work_ints(bs, n_static), 256);
+    if (int rc = ev_reserve(c, off_d + sizeof(int) * grid_work_ints(bd, n_dynamic))) return rc;
+    unsigned char* base = (unsigned char*)c->ev.buf;
     launch_classify(d_orig_xyz, d_pred_static, n, d_static_xyz, n_static, d_dynamic_xyz, n_dynamic, r15, r10, cell, bs, (int*)base, bd,
                     (int*)(base + off_d), c->ev_counters + 8, d_class, st);
     HIPCHK(c, hipGetLastError());
-    c->ev_cls_stream = st;
-    c->ev_cls_ran = true;
+    c->ev_cls.stream = st;
+    c->ev_cls.ran = true;
     return SCVOD_OK;
 }
 
 int scvod_classify_map_stats(scvod_ctx* c, int64_t* h_out5) {
     if (!c) return SCVOD_ERR_INVALID;
     if (!h_out5) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
-    if (!c->ev_cls_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_classify_map_device on this ctx yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h, c->ev_counters + 8, sizeof(h), hipMemcpyDeviceToHost, c->ev_cls_stream));
-    HIPCHK(c, hipStreamSynchronize(c->ev_cls_stream));
-    for (int k = 0; k < 5; ++k) h_out5[k] = (int64_t)h[k];
-    return SCVOD_OK;
+    if (!c->ev_cls.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_classify_map_device on this ctx yet");
+    return read_counters(c, c->ev_counters + 8, 5, c->ev_cls.stream, h_out5);
 }
 
 // ---- class scores against labelled truth (scvod_classes.hip) ----
@@ -3237,23 +3259,10 @@ static int cs_params(scvod_ctx* c, const scvod_class_params* params, CsLists* L,
     return SCVOD_OK;
 }
 
-// the scoring's scratch block of at least `bytes` (grow-only; growing waits for the scoring in flight, which reads the old one)
+// the scoring's scratch block of at least `bytes` (growing waits for the scoring in flight)
 static int cs_reserve(scvod_ctx* c, size_t bytes) {
-    if (!c->cs_counters) {
-        HIPCHK(c, hipMalloc(&c->cs_counters, sizeof(unsigned long long) * 24));
-        HIPCHK(c, hipMemset(c->cs_counters, 0, sizeof(unsigned long long) * 24));
-    }
-    if (bytes > c->cs_cap) {
-        if (c->cs_buf) {
-            if (c->cs_ran) HIPCHK(c, hipStreamSynchronize(c->cs_stream));
-            hipFree(c->cs_buf);
-            c->cs_buf = nullptr;
-            c->cs_cap = 0;
-        }
-        HIPCHK(c, hipMalloc(&c->cs_buf, bytes + bytes / 4));
-        c->cs_cap = bytes + bytes / 4;
-    }
-    return SCVOD_OK;
+    if (int rc = counter_block(c, &c->cs_counters, 24)) return rc;
+    return scratch_reserve(c, c->cs, bytes);
 }
 
 int scvod_score_classes_device(scvod_ctx* c, const float* d_gt_xyz, const uint32_t* d_gt_label, int32_t n_gt, const float* d_est_xyz,
@@ -3268,95 +3277,56 @@ int scvod_score_classes_device(scvod_ctx* c, const float* d_gt_xyz, const uint32
     if (int rc = cs_params(c, params, &L, &cell, &max_dist, &rings)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const int32_t buckets = ev_buckets(n_est);
+    const int32_t buckets = grid_buckets(n_est);
     if (int rc = cs_reserve(c, cs_work_bytes(buckets, n_est, n_gt))) return rc;
-    launch_class_score(d_gt_xyz, d_gt_label, n_gt, d_est_xyz, d_est_class, nullptr, n_est, L, cell, max_dist, rings, buckets, (int*)c->cs_buf,
+    launch_class_score(d_gt_xyz, d_gt_label, n_gt, d_est_xyz, d_est_class, nullptr, n_est, L, cell, max_dist, rings, buckets, (int*)c->cs.buf,
                        c->cs_counters, d_point_result, st);
     HIPCHK(c, hipGetLastError());
-    c->cs_stream = st;
-    c->cs_ran = true;
+    c->cs.stream = st;
+    c->cs.ran = true;
     return SCVOD_OK;
 }
 
 int scvod_batch_score_classes(scvod_ctx* c, const uint32_t* d_gt_label, const float* h_poses, int32_t flags, const scvod_class_params* params,
                               uint8_t* d_point_result, void* stream) {
     if (!c) return SCVOD_ERR_INVALID;
-    if (!d_gt_label || !h_poses) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
-    if (flags & ~(SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED | SCVOD_MAP_IGNORE_DYNAMIC))
-        return fail(c, SCVOD_ERR_INVALID, "scvod_batch_score_classes takes SCVOD_MAP_NO_GROUND, SCVOD_MAP_NO_REJECTED and SCVOD_MAP_IGNORE_DYNAMIC only (flags %d)", flags);
     CsLists L;
     float cell, max_dist;
     int32_t rings;
-    if (int rc = cs_params(c, params, &L, &cell, &max_dist, &rings)) return rc;
-    const int use_dyn = (flags & SCVOD_MAP_IGNORE_DYNAMIC) ? 0 : 1;
-    if (int rc = export_check(c, use_dyn, "scvod_batch_score_classes")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
-    const int B = c->A.n_scans;
-    const int32_t N = (int32_t)c->A.total_pts;
-    const int32_t buckets = ev_buckets(N);
-    // world xyz | keep byte | class byte | pose matrices | grid and list
-    const size_t n1 = (size_t)(N > 0 ? N : 1);
-    const size_t off_keep = align_up(12 * n1, 256), off_cls = off_keep + align_up(n1, 256), off_pose = off_cls + align_up(n1, 256),
-                 off_grid = off_pose + align_up(sizeof(float) * 12 * (size_t)(B > 0 ? B : 1), 256);
-    if (int rc = cs_reserve(c, off_grid + cs_work_bytes(buckets, N, N))) return rc;
-    unsigned char* base = (unsigned char*)c->cs_buf;
-    float* world = (float*)base;
-    uint8_t* keep = base + off_keep;
-    uint8_t* cls = base + off_cls;
-    float* pose = (float*)(base + off_pose);
-    if (B > 0) {  // pcl::getTransformation per scan, staged before the call returns: h_poses is the caller's again at once
-        std::vector<float> T((size_t)12 * B);
-        for (int s = 0; s < B; ++s) scvod_pose_matrix(h_poses + 6 * s, T.data() + 12 * s);
-        if (int rc = staged_upload(c, T.data(), sizeof(float) * T.size(), pose, st)) return rc;
-    }
-    // scvod_batch_export_points' rule; a building point is kept as the STATIC_OTHER point it is for the export
-    uint32_t keep_mask = (1u << SCVOD_PT_UNCLUSTERED) | (1u << SCVOD_PT_STATIC_OTHER) | (1u << SCVOD_PT_STATIC_CAR) | (1u << SCVOD_PT_STATIC_BUILDING);
-    if (!(flags & SCVOD_MAP_NO_GROUND)) keep_mask |= 1u << SCVOD_PT_GROUND;
-    if (!(flags & SCVOD_MAP_NO_REJECTED)) keep_mask |= 1u << SCVOD_PT_REJECTED;
-    if (!use_dyn) keep_mask |= 1u << SCVOD_PT_DYNAMIC;
-    if (N > 0) {
-        HIPCHK(c, hipMemsetAsync(cls, SCVOD_PT_DROPPED, (size_t)N, st));
-        if (c->rg_done)
-            launch_point_classes(c->A, c->rg.cls, cls, use_dyn, st);
-        else
-            launch_point_labels(c->A, cls, use_dyn, st);
-        launch_eval_world(c->A, cls, keep_mask, pose, world, keep, st);  // (k_ev_world: the export's expression and keep rule)
-    }
-    launch_class_score(world, d_gt_label, N, world, cls, keep, N, L, cell, max_dist, rings, buckets, (int*)(base + off_grid), c->cs_counters,
-                       d_point_result, st);
+    BatchCloud W;
+    // a building point is kept as the STATIC_OTHER point it is for the export
+    if (int rc = batch_cloud(c, "scvod_batch_score_classes", d_gt_label, h_poses, flags, [&] { return cs_params(c, params, &L, &cell, &max_dist, &rings); },
+                             1u << SCVOD_PT_STATIC_BUILDING, true, c->cs, cs_reserve, [](int32_t buckets, int32_t n) { return cs_work_bytes(buckets, n, n); },
+                             stream, &W))
+        return rc;
+    launch_class_score(W.world, d_gt_label, W.n, W.world, W.byte, W.keep, W.n, L, cell, max_dist, rings, W.buckets, W.work, c->cs_counters,
+                       d_point_result, W.st);
     HIPCHK(c, hipGetLastError());
-    c->cs_stream = st;
-    c->cs_ran = true;
+    c->cs.stream = W.st;
+    c->cs.ran = true;
     return SCVOD_OK;
 }
 
 int scvod_score_classes_stats(scvod_ctx* c, scvod_class_result* out) {
     if (!c) return SCVOD_ERR_INVALID;
     if (!out) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
-    if (!c->cs_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_score_classes_device or scvod_batch_score_classes on this ctx yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long h[24] = {0};
-    HIPCHK(c, hipMemcpyAsync(h, c->cs_counters, sizeof(h), hipMemcpyDeviceToHost, c->cs_stream));
-    HIPCHK(c, hipStreamSynchronize(c->cs_stream));
+    if (!c->cs.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_score_classes_device or scvod_batch_score_classes on this ctx yet");
     int64_t counts[21];
-    for (int k = 0; k < 21; ++k) counts[k] = (int64_t)h[k];
+    if (int rc = read_counters(c, c->cs_counters, 21, c->cs.stream, counts)) return rc;
     scvod_class_finish(counts, out);
     return SCVOD_OK;
 }
 
 int64_t scvod_score_classes_pass2_queries(scvod_ctx* c) {
     if (!c) return SCVOD_ERR_INVALID;
-    if (!c->cs_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_score_classes_device or scvod_batch_score_classes on this ctx yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long h = 0;
-    HIPCHK(c, hipMemcpyAsync(&h, c->cs_counters + 21, sizeof(h), hipMemcpyDeviceToHost, c->cs_stream));
-    HIPCHK(c, hipStreamSynchronize(c->cs_stream));
-    return (int64_t)h;
+    if (!c->cs.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_score_classes_device or scvod_batch_score_classes on this ctx yet");
+    int64_t n = 0;
+    if (int rc = read_counters(c, c->cs_counters + 21, 1, c->cs.stream, &n)) return rc;
+    return n;
 }
 
 int64_t scvod_score_classes_scratch_bytes(scvod_ctx* c) {
-    return c ? (int64_t)c->cs_cap + (c->cs_counters ? (int64_t)sizeof(unsigned long long) * 24 : 0) : 0;
+    return c ? (int64_t)c->cs.cap + (c->cs_counters ? (int64_t)sizeof(unsigned long long) * 24 : 0) : 0;
 }
 
 // ---- scan stacking (scvod_stack.hip) ----
@@ -3429,22 +3399,13 @@ int scvod_batch_stack_scans(scvod_ctx* c, const void* d_xyzi_in, const int32_t* 
             ++seg;
         }
     }
-    if (bytes > c->stk_cap) {  // (the old tables may still be read by a stacking call in flight)
-        if (c->stk_buf) {
-            if (c->stk_ran) HIPCHK(c, hipStreamSynchronize(c->stk_stream));
-            hipFree(c->stk_buf);
-            c->stk_buf = nullptr;
-            c->stk_cap = 0;
-        }
-        HIPCHK(c, hipMalloc(&c->stk_buf, bytes + bytes / 4));
-        c->stk_cap = bytes + bytes / 4;
-    }
-    if (int rc = staged_upload(c, c->stk_host.data(), bytes, c->stk_buf, st)) return rc;
-    launch_stack((const StackSeg*)c->stk_buf, (const StackTile*)((const unsigned char*)c->stk_buf + off_tiles), (int)n_tiles,
+    if (int rc = scratch_reserve(c, c->stk, bytes)) return rc;  // (the old tables may still be read by a stacking call in flight)
+    if (int rc = staged_upload(c, c->stk_host.data(), bytes, c->stk.buf, st)) return rc;
+    launch_stack((const StackSeg*)c->stk.buf, (const StackTile*)((const unsigned char*)c->stk.buf + off_tiles), (int)n_tiles,
                  (const float4*)d_xyzi_in, (float4*)d_xyzi_out, d_payload_in, d_payload_out, d_src_out, st);
     HIPCHK(c, hipGetLastError());
-    c->stk_stream = st;
-    c->stk_ran = true;
+    c->stk.stream = st;
+    c->stk.ran = true;
     return SCVOD_OK;
 }
 
@@ -3481,7 +3442,7 @@ int scvod_stack_scans(scvod_ctx* c, const float* h_xyzi_in, const int32_t* h_in_
     return rc;
 }
 
-int64_t scvod_stack_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)c->stk_cap : 0; }
+int64_t scvod_stack_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)c->stk.cap : 0; }
 
 // ---- a map split by nearest-neighbour hits (scvod_split.hip) ----
 void scvod_split_params_default(scvod_split_params* p) {
@@ -3519,22 +3480,9 @@ int scvod_map_split_device(scvod_ctx* c, const float* d_base, const uint32_t* d_
     }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (!c->sp_stats) {
-        HIPCHK(c, hipMalloc(&c->sp_stats, sizeof(unsigned long long) * 8));
-        HIPCHK(c, hipMemset(c->sp_stats, 0, sizeof(unsigned long long) * 8));
-    }
-    const int32_t buckets = ev_buckets(n_base);
-    const size_t bytes = sp_work_bytes(buckets, n_base, n_query);
-    if (bytes > c->sp_cap) {  // (the old block may still be read by a split in flight)
-        if (c->sp_buf) {
-            if (c->sp_ran) HIPCHK(c, hipStreamSynchronize(c->sp_stream));
-            hipFree(c->sp_buf);
-            c->sp_buf = nullptr;
-            c->sp_cap = 0;
-        }
-        HIPCHK(c, hipMalloc(&c->sp_buf, bytes + bytes / 4));
-        c->sp_cap = bytes + bytes / 4;
-    }
+    if (int rc = counter_block(c, &c->sp_stats, 8)) return rc;
+    const int32_t buckets = grid_buckets(n_base);
+    if (int rc = scratch_reserve(c, c->sp, sp_work_bytes(buckets, n_base, n_query))) return rc;  // (the old block may still be read by a split in flight)
     SpJob J;
     memset(&J, 0, sizeof(J));
     J.base = d_base;
@@ -3555,27 +3503,22 @@ int scvod_map_split_device(scvod_ctx* c, const float* d_base, const uint32_t* d_
     J.payload_out = d_payload_out;
     J.nn_idx = d_nn_idx;
     J.nn_sq = d_nn_sqdist;
-    launch_map_split(J, p.cell, buckets, c->sp_buf, c->sp_stats, st);
+    launch_map_split(J, p.cell, buckets, c->sp.buf, c->sp_stats, st);
     HIPCHK(c, hipGetLastError());
-    c->sp_stream = st;
-    c->sp_ran = true;
+    c->sp.stream = st;
+    c->sp.ran = true;
     return SCVOD_OK;
 }
 
 int scvod_map_split_stats(scvod_ctx* c, int64_t* h_out8) {
     if (!c) return SCVOD_ERR_INVALID;
     if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
-    if (!c->sp_ran) return fail(c, SCVOD_ERR_STATE, "no scvod_map_split_device on this ctx yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h, c->sp_stats, sizeof(h), hipMemcpyDeviceToHost, c->sp_stream));
-    HIPCHK(c, hipStreamSynchronize(c->sp_stream));
-    for (int k = 0; k < 8; ++k) h_out8[k] = (int64_t)h[k];
-    return SCVOD_OK;
+    if (!c->sp.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_map_split_device on this ctx yet");
+    return read_counters(c, c->sp_stats, 8, c->sp.stream, h_out8);
 }
 
 int64_t scvod_map_split_scratch_bytes(scvod_ctx* c) {
-    return c ? (int64_t)c->sp_cap + (c->sp_stats ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+    return c ? (int64_t)c->sp.cap + (c->sp_stats ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
 }
 
 int scvod_map_split(scvod_ctx* c, const float* h_base, const uint32_t* h_base_label, int32_t n_base, const float* h_query, int32_t n_query,

@@ -3,8 +3,7 @@
 //
 // Reference analogue: src/plotObject.cpp:87-146, the tool behind the per-class table of doc/note.txt:57-78 -- a 1-NN look-up from every
 // ground-truth point into the class-coloured map, four rules, P and N per class.  Here:
-//     grid     the CSR hash grid of scvod_eval.hip / scvod_k_nn_grid.inc (same cell rule, same hash, the same scan kernels, an optional
-//              keep byte per estimate point) with the caller's cell edge
+//     grid     the shared CSR hash grid of scvod_grid.h (an optional keep byte per estimate point) with the caller's cell edge
 //     pass 1   k_cs_probe: one thread per truth point, the 27 cells around it.  A query whose best candidate lies closer than 0.99 cell
 //              edges is FINISHED (nothing nearer can lie outside the cells it looked at; scvod_eval.hip's margin) and scored at once; the
 //              others are appended to a list with their candidate, one atomic per wave (ballot / popcount rank)
@@ -14,66 +13,12 @@
 //              all (2R + 1)^3 cells, ties (lowest estimate index) included, whatever the order of the list
 //     scores   a neighbour counts only when d < max_dist * max_dist; per block an LDS histogram of 21 ints (20 confusion cells + pd_far,
 //              integer atomicAdd), then one 64-bit global atomic per non-zero cell and block: integer sums, the same on every run
-// Several cells of a ring may hash to one bucket, and a bucket may hold points of far cells: every candidate is a real estimate point
-// with its real distance, so a superset of the cells asked for changes nothing.
 #include <hip/hip_runtime.h>
 
-#include "scvod_dev.h"
+#include "scvod_grid.h"
 
 namespace scvod {
 namespace {
-
-struct CsGrid {
-    float inv_h;
-    uint32_t mask;  // buckets - 1 (power of two)
-    const int* start;
-    const int* count;
-    const int* entries;
-};
-// the hash and the cell of scvod_k_nn_grid.inc with the origin at 0
-__device__ __forceinline__ uint32_t cs_bucket(uint32_t mask, int cx, int cy, int cz) {
-    return ((uint32_t)cx * 73856093u ^ (uint32_t)cy * 19349663u ^ (uint32_t)cz * 83492791u) & mask;
-}
-__device__ __forceinline__ void cs_cell(float inv_h, float x, float y, float z, int& cx, int& cy, int& cz) {
-    cx = (int)floorf(x * inv_h);
-    cy = (int)floorf(y * inv_h);
-    cz = (int)floorf(z * inv_h);
-}
-
-// keep: nullptr, or one byte per estimate point: a point whose byte is 0 is not entered
-__global__ __launch_bounds__(256) void k_cs_count(float inv_h, uint32_t mask, const float* __restrict__ est_xyz, const uint8_t* __restrict__ keep,
-                                                  int n_est, int* count) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_est || (keep && !keep[i])) return;
-    int cx, cy, cz;
-    cs_cell(inv_h, est_xyz[3 * (size_t)i], est_xyz[3 * (size_t)i + 1], est_xyz[3 * (size_t)i + 2], cx, cy, cz);
-    atomicAdd(&count[cs_bucket(mask, cx, cy, cz)], 1);
-}
-
-__global__ __launch_bounds__(256) void k_cs_fill(float inv_h, uint32_t mask, const float* __restrict__ est_xyz, const uint8_t* __restrict__ keep,
-                                                 int n_est, const int* start, int* cursor, int* entries) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_est || (keep && !keep[i])) return;
-    int cx, cy, cz;
-    cs_cell(inv_h, est_xyz[3 * (size_t)i], est_xyz[3 * (size_t)i + 1], est_xyz[3 * (size_t)i + 2], cx, cy, cz);
-    const uint32_t b = cs_bucket(mask, cx, cy, cz);
-    entries[start[b] + atomicAdd(&cursor[b], 1)] = (int)i;  // (the order inside a bucket varies; the tie rule does not depend on it)
-}
-
-// the candidates of one bucket against (best, bi): the evaluation's expression and tie rule
-__device__ __forceinline__ void cs_visit(const CsGrid& g, const float* __restrict__ est_xyz, uint32_t b, float qx, float qy, float qz, float& best,
-                                         int& bi) {
-    const int s0 = g.start[b], c = g.count[b];
-    for (int k = 0; k < c; ++k) {
-        const int m = g.entries[s0 + k];
-        const float ex = est_xyz[3 * (size_t)m] - qx, ey = est_xyz[3 * (size_t)m + 1] - qy, ez = est_xyz[3 * (size_t)m + 2] - qz;
-        const float d = (ex * ex + ey * ey) + ez * ez;
-        if (bi < 0 || d < best || (d == best && m < bi)) {
-            best = d;
-            bi = m;
-        }
-    }
-}
 
 // truth class of a label: the lists in the order of plotObject.cpp's check(); in no list: pd
 __device__ __forceinline__ int cs_truth(const CsLists& L, uint32_t label) {
@@ -122,7 +67,7 @@ struct CsTodo {  // the pass-2 list: per slot the query and the candidate pass 1
     float* best;
 };
 
-__global__ __launch_bounds__(256) void k_cs_probe(CsGrid g, const float* __restrict__ est_xyz, const uint8_t* __restrict__ est_class, int probe,
+__global__ __launch_bounds__(256) void k_cs_probe(PointGrid g, const float* __restrict__ est_xyz, const uint8_t* __restrict__ est_class, int probe,
                                                   const float* __restrict__ q_xyz, const uint32_t* __restrict__ q_label, int n_q, CsLists L,
                                                   float thr1, float max2, int rings, CsTodo todo, unsigned long long* counters,
                                                   uint8_t* __restrict__ result) {
@@ -137,33 +82,22 @@ __global__ __launch_bounds__(256) void k_cs_probe(CsGrid g, const float* __restr
     if (valid) {
         if (probe) {
             const float qx = q_xyz[3 * (size_t)q], qy = q_xyz[3 * (size_t)q + 1], qz = q_xyz[3 * (size_t)q + 2];
-            int cx, cy, cz;
-            cs_cell(g.inv_h, qx, qy, qz, cx, cy, cz);
-            for (int dz = -1; dz <= 1; ++dz)
-                for (int dy = -1; dy <= 1; ++dy)
-                    for (int dx = -1; dx <= 1; ++dx) cs_visit(g, est_xyz, cs_bucket(g.mask, cx + dx, cy + dy, cz + dz), qx, qy, qz, best, bi);
+            grid_probe27(g, est_xyz, 3, qx, qy, qz, best, bi);
             later = rings > 1 && !(bi >= 0 && best < thr1);
         }
         if (!later) cs_score(cs_truth(L, q_label[q]), bi, best, max2, est_class, q, result, hist);
     }
     // the unfinished queries of the wave take consecutive slots: one atomic per wave
-    const unsigned long long bal = __ballot(later);
-    if (bal) {
-        const int lane = threadIdx.x & 63;
-        int base = 0;
-        if (lane == 0) base = atomicAdd(todo.n, __popcll(bal));
-        base = __shfl(base, 0, 64);
-        if (later) {
-            const int slot = base + __popcll(bal & ((1ull << lane) - 1ull));
-            todo.q[slot] = (int)q;
-            todo.bi[slot] = bi;
-            todo.best[slot] = best;
-        }
+    const int slot = wave_list_slot(later, todo.n);
+    if (later) {
+        todo.q[slot] = (int)q;
+        todo.bi[slot] = bi;
+        todo.best[slot] = best;
     }
     cs_flush(hist, counters);
 }
 
-__global__ __launch_bounds__(256) void k_cs_rings(CsGrid g, const float* __restrict__ est_xyz, const uint8_t* __restrict__ est_class,
+__global__ __launch_bounds__(256) void k_cs_rings(PointGrid g, const float* __restrict__ est_xyz, const uint8_t* __restrict__ est_class,
                                                   const float* __restrict__ q_xyz, const uint32_t* __restrict__ q_label, CsLists L, float g1,
                                                   float max2, int rings, CsTodo todo, unsigned long long* counters,
                                                   uint8_t* __restrict__ result) {
@@ -177,14 +111,9 @@ __global__ __launch_bounds__(256) void k_cs_rings(CsGrid g, const float* __restr
         float best = todo.best[t];
         const float qx = q_xyz[3 * (size_t)q], qy = q_xyz[3 * (size_t)q + 1], qz = q_xyz[3 * (size_t)q + 2];
         int cx, cy, cz;
-        cs_cell(g.inv_h, qx, qy, qz, cx, cy, cz);
+        grid_cell(g, qx, qy, qz, cx, cy, cz);
         for (int r = 2; r <= rings; ++r) {
-            for (int dz = -r; dz <= r; ++dz)
-                for (int dy = -r; dy <= r; ++dy) {
-                    const bool face = dz == -r || dz == r || dy == -r || dy == r;
-                    // a row of the ring's faces is walked whole, any other row only touches the ring at its two ends
-                    for (int dx = -r; dx <= r; dx += face ? 1 : 2 * r) cs_visit(g, est_xyz, cs_bucket(g.mask, cx + dx, cy + dy, cz + dz), qx, qy, qz, best, bi);
-                }
+            grid_shell(g, est_xyz, 3, cx, cy, cz, r, qx, qy, qz, best, bi);
             const float reach = g1 * (float)r;
             if (bi >= 0 && best < reach * reach) break;
         }
@@ -198,41 +127,23 @@ inline unsigned cs_blocks(int n) { return (unsigned)(((long long)n + 255) / 256)
 }  // namespace
 
 size_t cs_work_bytes(int32_t buckets, int32_t n_est, int32_t n_gt) {
-    // grid ints (ev_grid_ints' layout) | list length | list: query, candidate, distance
-    return sizeof(int) * (ev_grid_ints(buckets, n_est) + 1 + 3 * (size_t)(n_gt > 0 ? n_gt : 1));
+    // grid ints | list length | list: query, candidate, distance
+    return sizeof(int) * (grid_work_ints(buckets, n_est) + 1 + 3 * (size_t)(n_gt > 0 ? n_gt : 1));
 }
 
 void launch_class_score(const float* gt_xyz, const uint32_t* gt_label, int32_t n_gt, const float* est_xyz, const uint8_t* est_class,
                         const uint8_t* est_keep, int32_t n_est, const CsLists& L, float cell, float max_dist, int32_t rings, int32_t buckets,
                         int* work, unsigned long long* counters, uint8_t* point_result, hipStream_t st) {
-    int* count = work;
-    int* start = count + buckets;
-    int* cursor = start + buckets;
-    int* entries = cursor + buckets;
-    int* grand = entries + (n_est > 0 ? n_est : 1);
-    int* block_tot = grand + 1;
-    int* tail = work + ev_grid_ints(buckets, n_est);
+    int* tail = work + grid_work_ints(buckets, n_est);
     CsTodo todo;
     todo.n = tail;
     todo.q = tail + 1;
     todo.bi = todo.q + (n_gt > 0 ? n_gt : 1);
     todo.best = reinterpret_cast<float*>(todo.bi + (n_gt > 0 ? n_gt : 1));
-    CsGrid g;
-    g.inv_h = 1.0f / cell;
-    g.mask = (uint32_t)buckets - 1u;
-    g.start = start;
-    g.count = count;
-    g.entries = entries;
     hipMemsetAsync(counters, 0, sizeof(unsigned long long) * 24, st);  // [0..20] the scores, [21] the pass-2 list's length
     hipMemsetAsync(todo.n, 0, sizeof(int), st);
     if (n_gt <= 0) return;
-    if (n_est > 0) {
-        hipMemsetAsync(count, 0, sizeof(int) * (size_t)buckets, st);
-        hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)buckets, st);
-        hipLaunchKernelGGL(k_cs_count, dim3(cs_blocks(n_est)), dim3(256), 0, st, g.inv_h, g.mask, est_xyz, est_keep, n_est, count);
-        launch_scan_ints(count, start, block_tot, grand, buckets, st);
-        hipLaunchKernelGGL(k_cs_fill, dim3(cs_blocks(n_est)), dim3(256), 0, st, g.inv_h, g.mask, est_xyz, est_keep, n_est, start, cursor, entries);
-    }
+    const PointGrid g = grid_build(est_xyz, 3, est_keep, n_est, kGridOrigin0, cell, buckets, work, st);
     const float g1 = 0.99f * cell, max2 = max_dist * max_dist;
     hipLaunchKernelGGL(k_cs_probe, dim3(cs_blocks(n_gt)), dim3(256), 0, st, g, est_xyz, est_class, n_est > 0 ? 1 : 0, gt_xyz, gt_label, n_gt, L,
                        g1 * g1, max2, rings, todo, counters, point_result);

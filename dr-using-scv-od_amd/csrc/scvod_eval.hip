@@ -5,83 +5,23 @@
 // estimate point lies within voxelsize * sqrt(3) / 2 and both carry a static, resp. a dynamic, label) and the colour classes of the map
 // viewer (src/evaluate.cpp:79-145).  pyshim/metric.py states both on the host over a 1-NN look-up; here the look-up, the tests and the
 // counters are one kernel per ground-truth cloud.
-//     grid     the CSR hash grid of scvod_k_nn_grid.inc (same cell rule, same hash, the same scan kernels) over the estimate cloud, with an
-//              optional keep byte per point: the estimate of a batch is a mask over the batch's world points, never a compaction
+//     grid     the shared CSR hash grid of scvod_grid.h over the estimate cloud, with an optional keep byte per point: the estimate of
+//              a batch is a mask over the batch's world points, never a compaction
 //     query    one thread per ground-truth point, the 27-cell probe, nearest candidate, ties to the lowest estimate index.  Every radius
 //              that is asked about is below 0.99 cell edges, so a neighbour inside it is among the candidates: no second pass
 //     counters ballot / popcount per wave, LDS per block, one 64-bit atomicAdd per counter and block: integer sums, the same on every run
 #include <hip/hip_runtime.h>
 
-#include "scvod_dev.h"
+#include "scvod_grid.h"
 
 namespace scvod {
 namespace {
 
-struct EvGrid {
-    float inv_h;
-    uint32_t mask;  // buckets - 1 (power of two)
-    const int* start;
-    const int* count;
-    const int* entries;
-};
-// the hash and the cell of scvod_k_nn_grid.inc with the origin at 0 (scvod_nn_search_device's)
-__device__ __forceinline__ uint32_t ev_bucket(uint32_t mask, int cx, int cy, int cz) {
-    return ((uint32_t)cx * 73856093u ^ (uint32_t)cy * 19349663u ^ (uint32_t)cz * 83492791u) & mask;
-}
-__device__ __forceinline__ void ev_cell(float inv_h, float x, float y, float z, int& cx, int& cy, int& cz) {
-    cx = (int)floorf(x * inv_h);
-    cy = (int)floorf(y * inv_h);
-    cz = (int)floorf(z * inv_h);
-}
 __device__ __forceinline__ bool ev_is_dyn(const EvClasses& K, uint32_t label) {
     const uint32_t sem = label & 0xFFFFu;  // analysis.py:8-12
     bool d = false;
     for (int k = 0; k < K.n; ++k) d |= sem == (uint32_t)K.c[k];
     return d;
-}
-
-// keep: nullptr, or one byte per map point: a point whose byte is 0 is not entered
-__global__ __launch_bounds__(256) void k_ev_count(float inv_h, uint32_t mask, const float* __restrict__ map_xyz, const uint8_t* __restrict__ keep,
-                                                  int n_map, int* count) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_map || (keep && !keep[i])) return;
-    int cx, cy, cz;
-    ev_cell(inv_h, map_xyz[3 * (size_t)i], map_xyz[3 * (size_t)i + 1], map_xyz[3 * (size_t)i + 2], cx, cy, cz);
-    atomicAdd(&count[ev_bucket(mask, cx, cy, cz)], 1);
-}
-
-__global__ __launch_bounds__(256) void k_ev_fill(float inv_h, uint32_t mask, const float* __restrict__ map_xyz, const uint8_t* __restrict__ keep,
-                                                 int n_map, const int* start, int* cursor, int* entries) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_map || (keep && !keep[i])) return;
-    int cx, cy, cz;
-    ev_cell(inv_h, map_xyz[3 * (size_t)i], map_xyz[3 * (size_t)i + 1], map_xyz[3 * (size_t)i + 2], cx, cy, cz);
-    const uint32_t b = ev_bucket(mask, cx, cy, cz);
-    entries[start[b] + atomicAdd(&cursor[b], 1)] = (int)i;  // (the order inside a bucket varies; the query's tie rule does not depend on it)
-}
-
-// nearest candidate of the 27 cells around (qx, qy, qz): k_nn_query's loop.  bi = -1: no candidate
-__device__ __forceinline__ void ev_probe(const EvGrid& g, const float* __restrict__ map_xyz, float qx, float qy, float qz, float& best, int& bi) {
-    int cx, cy, cz;
-    ev_cell(g.inv_h, qx, qy, qz, cx, cy, cz);
-    best = 0.f;
-    bi = -1;
-    for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                const uint32_t b = ev_bucket(g.mask, cx + dx, cy + dy, cz + dz);
-                const int s0 = g.start[b], c = g.count[b];
-                for (int k = 0; k < c; ++k) {
-                    const int m = g.entries[s0 + k];
-                    const float ex = map_xyz[3 * (size_t)m] - qx, ey = map_xyz[3 * (size_t)m + 1] - qy, ez = map_xyz[3 * (size_t)m + 2] - qz;
-                    const float d = (ex * ex + ey * ey) + ez * ez;
-                    if (bi < 0 || d < best || (d == best && m < bi)) {
-                        best = d;
-                        bi = m;
-                    }
-                }
-            }
-    // several of the 27 probes may hash to the same bucket: harmless (same candidates again)
 }
 
 // NF flags per thread -> counters[slot[f]] += how many threads of the block raised flag f.  Every thread of the block calls it.
@@ -103,7 +43,7 @@ __device__ __forceinline__ void ev_block_count(const bool (&flag)[NF], const int
 // counter words of an evaluation, in the order of metric.preservation_rejection's counts
 enum { kEvGtStatic = 0, kEvGtDynamic, kEvEstStatic, kEvEstDynamic, kEvPreserved, kEvStaticPreserved, kEvDynamicPreserved };
 
-__global__ __launch_bounds__(256) void k_ev_query(EvGrid g, const float* __restrict__ map_xyz, const uint32_t* __restrict__ map_label, int probe,
+__global__ __launch_bounds__(256) void k_ev_query(PointGrid g, const float* __restrict__ map_xyz, const uint32_t* __restrict__ map_label, int probe,
                                                   const float* __restrict__ q_xyz, const uint32_t* __restrict__ q_label, int n_q, double limit,
                                                   EvClasses K, unsigned long long* counters, uint8_t* __restrict__ result) {
     __shared__ int wcnt[4][5];
@@ -113,9 +53,9 @@ __global__ __launch_bounds__(256) void k_ev_query(EvGrid g, const float* __restr
     if (valid) {
         gdyn = ev_is_dyn(K, q_label[q]);
         if (probe) {
-            float best;
-            int bi;
-            ev_probe(g, map_xyz, q_xyz[3 * (size_t)q], q_xyz[3 * (size_t)q + 1], q_xyz[3 * (size_t)q + 2], best, bi);
+            float best = 0.f;
+            int bi = -1;  // (no candidate)
+            grid_probe27(g, map_xyz, 3, q_xyz[3 * (size_t)q], q_xyz[3 * (size_t)q + 1], q_xyz[3 * (size_t)q + 2], best, bi);
             inl = bi >= 0 && sqrt((double)best) < limit;  // metric.py:22-23
             if (inl) edyn = ev_is_dyn(K, map_label[bi]);
         }
@@ -165,7 +105,7 @@ __global__ __launch_bounds__(256) void k_ev_world(Arena A, const uint8_t* __rest
 
 // evaluate() of src/evaluate.cpp:79-145 per point of the original map: one probe into the grid over the static cloud, one into the grid
 // over the dynamic cloud; the class is metric.classify_map_points' four assignments in its order
-__global__ __launch_bounds__(256) void k_ev_classify(EvGrid gs, const float* __restrict__ s_xyz, int probe_s, EvGrid gd, const float* __restrict__ d_xyz,
+__global__ __launch_bounds__(256) void k_ev_classify(PointGrid gs, const float* __restrict__ s_xyz, int probe_s, PointGrid gd, const float* __restrict__ d_xyz,
                                                      int probe_d, const float* __restrict__ o_xyz, const uint8_t* __restrict__ pred_static, int n,
                                                      float r15, float r10, uint8_t* __restrict__ cls, unsigned long long* counters) {
     __shared__ int wcnt[4][5];
@@ -176,15 +116,17 @@ __global__ __launch_bounds__(256) void k_ev_classify(EvGrid gs, const float* __r
         const float qx = o_xyz[3 * (size_t)q], qy = o_xyz[3 * (size_t)q + 1], qz = o_xyz[3 * (size_t)q + 2];
         const float r15sq = r15 * r15, r10sq = r10 * r10;
         bool s15 = false, s10 = false, d15 = false, d10 = false;  // an empty cloud matches nothing
-        float best;
-        int bi;
         if (probe_s) {
-            ev_probe(gs, s_xyz, qx, qy, qz, best, bi);
+            float best = 0.f;
+            int bi = -1;
+            grid_probe27(gs, s_xyz, 3, qx, qy, qz, best, bi);
             s15 = bi >= 0 && best < r15sq;
             s10 = bi >= 0 && best < r10sq;
         }
         if (probe_d) {
-            ev_probe(gd, d_xyz, qx, qy, qz, best, bi);
+            float best = 0.f;
+            int bi = -1;
+            grid_probe27(gd, d_xyz, 3, qx, qy, qz, best, bi);
             d15 = bi >= 0 && best < r15sq;
             d10 = bi >= 0 && best < r10sq;
         }
@@ -203,45 +145,13 @@ __global__ __launch_bounds__(256) void k_ev_classify(EvGrid gs, const float* __r
 
 inline unsigned ev_blocks(int n) { return (unsigned)(((long long)n + 255) / 256); }
 
-// the grid over map_xyz[keep] in `work` (ev_grid_ints ints); returns what the query reads
-EvGrid ev_build(const float* map_xyz, const uint8_t* keep, int n_map, float cell, int buckets, int* work, hipStream_t st) {
-    int* count = work;
-    int* start = count + buckets;
-    int* cursor = start + buckets;
-    int* entries = cursor + buckets;
-    int* grand = entries + (n_map > 0 ? n_map : 1);
-    int* block_tot = grand + 1;
-    EvGrid g;
-    g.inv_h = 1.0f / cell;
-    g.mask = (uint32_t)buckets - 1u;
-    g.start = start;
-    g.count = count;
-    g.entries = entries;
-    if (n_map <= 0) return g;
-    hipMemsetAsync(count, 0, sizeof(int) * (size_t)buckets, st);
-    hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)buckets, st);
-    hipLaunchKernelGGL(k_ev_count, dim3(ev_blocks(n_map)), dim3(256), 0, st, g.inv_h, g.mask, map_xyz, keep, n_map, count);
-    launch_scan_ints(count, start, block_tot, grand, buckets, st);
-    hipLaunchKernelGGL(k_ev_fill, dim3(ev_blocks(n_map)), dim3(256), 0, st, g.inv_h, g.mask, map_xyz, keep, n_map, start, cursor, entries);
-    return g;
-}
-
 }  // namespace
-
-int32_t ev_buckets(int32_t n_map) {  // nn_run's rule
-    int32_t buckets = 1024;
-    while (buckets < 2 * (long long)n_map && buckets < (1 << 26)) buckets <<= 1;
-    return buckets;
-}
-size_t ev_grid_ints(int32_t buckets, int32_t n_map) {
-    return 3 * (size_t)buckets + (size_t)(n_map > 0 ? n_map : 1) + 2 + (size_t)buckets / 1024 + 1;
-}
 
 void launch_eval(const float* gt_xyz, const uint32_t* gt_label, int32_t n_gt, const float* est_xyz, const uint32_t* est_label,
                  const uint8_t* est_keep, int32_t n_est, double limit, const EvClasses& K, float cell, int32_t buckets, int* work,
                  unsigned long long* counters, uint8_t* point_result, hipStream_t st) {
     hipMemsetAsync(counters, 0, sizeof(unsigned long long) * 8, st);
-    const EvGrid g = ev_build(est_xyz, est_keep, n_est, cell, buckets, work, st);
+    const PointGrid g = grid_build(est_xyz, 3, est_keep, n_est, kGridOrigin0, cell, buckets, work, st);
     if (n_est > 0) hipLaunchKernelGGL(k_ev_est_count, dim3(ev_blocks(n_est)), dim3(256), 0, st, est_label, est_keep, n_est, K, counters);
     if (n_gt > 0)
         hipLaunchKernelGGL(k_ev_query, dim3(ev_blocks(n_gt)), dim3(256), 0, st, g, est_xyz, est_label, n_est > 0 ? 1 : 0, gt_xyz, gt_label, n_gt,
@@ -260,8 +170,8 @@ void launch_classify(const float* orig_xyz, const uint8_t* pred_static, int32_t 
                      int32_t buckets_d, int* work_d, unsigned long long* counters, uint8_t* cls, hipStream_t st) {
     hipMemsetAsync(counters, 0, sizeof(unsigned long long) * 8, st);
     if (n <= 0) return;
-    const EvGrid gs = ev_build(static_xyz, nullptr, n_static, cell, buckets_s, work_s, st);
-    const EvGrid gd = ev_build(dynamic_xyz, nullptr, n_dynamic, cell, buckets_d, work_d, st);
+    const PointGrid gs = grid_build(static_xyz, 3, nullptr, n_static, kGridOrigin0, cell, buckets_s, work_s, st);
+    const PointGrid gd = grid_build(dynamic_xyz, 3, nullptr, n_dynamic, kGridOrigin0, cell, buckets_d, work_d, st);
     hipLaunchKernelGGL(k_ev_classify, dim3(ev_blocks(n)), dim3(256), 0, st, gs, static_xyz, n_static > 0 ? 1 : 0, gd, dynamic_xyz,
                        n_dynamic > 0 ? 1 : 0, orig_xyz, pred_static, n, r15, r10, cls, counters);
 }

@@ -1,30 +1,10 @@
 // scvod_k_nn_grid.inc -- uniform-grid correspondence search (A7).
 // Part of the kernels translation unit: included by scvod_kernels.hip (inside namespace scvod), never compiled on its own.
 // ---- uniform-grid correspondence search ------------------------------------------------------------
-// Map points are hashed by cell (edge h >= radius) into a CSR table; a query probes the 27 cells around it.
+// Map points are entered into the shared hash grid of scvod_grid.h (cell edge h >= radius); a query probes the 27 cells around it.
 // If the best candidate is within h it is the true nearest neighbour (anything outside the 27 cells is farther
 // than h); otherwise the query goes to the exact brute-force kernel.  Distances and tie-breaking (lowest map
 // index) are those of the brute-force kernel, so both paths return identical results.
-struct NnGrid {
-    float ox, oy, oz, inv_h, h2;
-    uint32_t mask;  // buckets - 1 (power of two)
-};
-__device__ __forceinline__ uint32_t nn_bucket(const NnGrid& g, int cx, int cy, int cz) {
-    return ((uint32_t)cx * 73856093u ^ (uint32_t)cy * 19349663u ^ (uint32_t)cz * 83492791u) & g.mask;
-}
-__device__ __forceinline__ void nn_cell(const NnGrid& g, float x, float y, float z, int& cx, int& cy, int& cz) {
-    cx = (int)floorf((x - g.ox) * g.inv_h);
-    cy = (int)floorf((y - g.oy) * g.inv_h);
-    cz = (int)floorf((z - g.oz) * g.inv_h);
-}
-
-__global__ __launch_bounds__(256) void k_nn_count(NnGrid g, const float* __restrict__ map_xyz, int n_map, int* count) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_map) return;
-    int cx, cy, cz;
-    nn_cell(g, map_xyz[3 * (size_t)i], map_xyz[3 * (size_t)i + 1], map_xyz[3 * (size_t)i + 2], cx, cy, cz);
-    atomicAdd(&count[nn_bucket(g, cx, cy, cz)], 1);
-}
 
 // exclusive scan of `n` ints, three launches: per-block (1024) scans + block totals, scan of totals, add-back
 __global__ __launch_bounds__(1024) void k_scan_blocks(const int* in, int* out, int* block_tot, int n) {
@@ -54,44 +34,16 @@ __global__ __launch_bounds__(1024) void k_scan_add(int* out, const int* block_to
     if (i < n) out[i] += block_tot[blockIdx.x];
 }
 
-__global__ __launch_bounds__(256) void k_nn_fill(NnGrid g, const float* __restrict__ map_xyz, int n_map, const int* start,
-                                                 int* cursor, int* entries) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_map) return;
-    int cx, cy, cz;
-    nn_cell(g, map_xyz[3 * (size_t)i], map_xyz[3 * (size_t)i + 1], map_xyz[3 * (size_t)i + 2], cx, cy, cz);
-    const uint32_t b = nn_bucket(g, cx, cy, cz);
-    entries[start[b] + atomicAdd(&cursor[b], 1)] = i;
-}
-
-__global__ __launch_bounds__(256) void k_nn_query(NnGrid g, const float* __restrict__ map_xyz, const float* __restrict__ q_xyz,
-                                                  int n_q, float r2, const int* start, const int* count, const int* entries,
-                                                  int32_t* nn_idx, float* nn_sq, uint8_t* within, int* todo, int* n_todo, int bounded) {
+__global__ __launch_bounds__(256) void k_nn_query(PointGrid g, float h2, const float* __restrict__ map_xyz, const float* __restrict__ q_xyz,
+                                                  int n_q, float r2, int32_t* nn_idx, float* nn_sq, uint8_t* within, int* todo, int* n_todo,
+                                                  int bounded) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_q) return;
     const float qx = q_xyz[3 * (size_t)q], qy = q_xyz[3 * (size_t)q + 1], qz = q_xyz[3 * (size_t)q + 2];
-    int cx, cy, cz;
-    nn_cell(g, qx, qy, qz, cx, cy, cz);
     float best = 0.f;
     int bi = -1;
-    for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                const uint32_t b = nn_bucket(g, cx + dx, cy + dy, cz + dz);
-                const int s0 = start[b], c = count[b];
-                for (int k = 0; k < c; ++k) {
-                    const int m = entries[s0 + k];
-                    const float ex = map_xyz[3 * (size_t)m] - qx, ey = map_xyz[3 * (size_t)m + 1] - qy,
-                                ez = map_xyz[3 * (size_t)m + 2] - qz;
-                    const float d = (ex * ex + ey * ey) + ez * ez;
-                    if (bi < 0 || d < best || (d == best && m < bi)) {
-                        best = d;
-                        bi = m;
-                    }
-                }
-            }
-    // several of the 27 probes may hash to the same bucket: harmless (same candidates again)
-    if (bi >= 0 && best <= g.h2) {
+    grid_probe27(g, map_xyz, 3, qx, qy, qz, best, bi);
+    if (bi >= 0 && best <= h2) {
         nn_idx[q] = bi;
         nn_sq[q] = best;
         within[q] = best < r2 ? 1 : 0;

@@ -403,18 +403,26 @@ void launch_export_table(const Arena& A, int s, int4* out, long long cap_records
 void launch_nn(const float* map_xyz, int32_t n_map, const float* q_xyz, int32_t n_q, float radius, int32_t* nn_idx,
                float* nn_sq, uint8_t* within, const float origin[3], float cell, int32_t buckets, int* work, int bounded,
                hipStream_t st);
-// exclusive scan of `n` ints on `st` (the three k_scan_* launches of the grid search): out[i] = in[0] + .. + in[i - 1], *grand_total = the sum;
-// block_tot: (n + 1023) / 1024 ints of scratch.  For the units that build a CSR grid of their own (scvod_eval.hip)
+// exclusive scan of `n` ints on `st` (three k_scan_* launches): out[i] = in[0] + .. + in[i - 1], *grand_total = the sum;
+// block_tot: (n + 1023) / 1024 ints of scratch
 void launch_scan_ints(const int* in, int* out, int* block_tot, int* grand_total, int n, hipStream_t st);
 
+// the CSR hash grid that the nearest-neighbour stages share (scvod_grid.h).  grid_buckets: the power of two for a cloud of n points;
+// grid_work_ints: the ints of `work` behind a grid.  grid_build enters the points xyz[stride * i] (keep: nullptr, or a point whose byte
+// is 0 is not entered) on `st` -- two memsets, k_grid_count, launch_scan_ints, k_grid_fill -- and returns what a query kernel reads;
+// n <= 0: the view alone, nothing is launched and no query may read it
+struct PointGrid;
+int32_t grid_buckets(int32_t n);
+size_t grid_work_ints(int32_t buckets, int32_t n);
+PointGrid grid_build(const float* xyz, int stride, const uint8_t* keep, int32_t n, const float origin[3], float cell, int32_t buckets, int* work,
+                     hipStream_t st);
+
 // evaluation against labelled truth (scvod_evaluate_device / scvod_batch_evaluate / scvod_classify_map_device; scvod_eval.hip).  A grid is
-// the CSR hash grid of launch_nn over the estimate cloud, in `work` (ev_grid_ints ints); counters: 8 words, cleared by every launch
+// the shared one over the estimate cloud, in `work` (grid_work_ints ints); counters: 8 words, cleared by every launch
 struct EvClasses {  // the semantic classes (label & 0xFFFF) that count as dynamic
     int32_t n;
     uint16_t c[16];
 };
-int32_t ev_buckets(int32_t n_map);
-size_t ev_grid_ints(int32_t buckets, int32_t n_map);
 // counters: gt static, gt dynamic, est static, est dynamic, preserved, static preserved, dynamic preserved, 0.  est_keep: nullptr or one
 // byte per estimate point (0: not part of the estimate).  point_result: nullptr or one byte per gt point
 void launch_eval(const float* gt_xyz, const uint32_t* gt_label, int32_t n_gt, const float* est_xyz, const uint32_t* est_label,
@@ -429,7 +437,7 @@ void launch_classify(const float* orig_xyz, const uint8_t* pred_static, int32_t 
                      int32_t buckets_d, int* work_d, unsigned long long* counters, uint8_t* cls, hipStream_t st);
 
 // class scores against labelled truth (scvod_score_classes_device / scvod_batch_score_classes; scvod_classes.hip).  The grid is the
-// evaluation's (ev_buckets, ev_grid_ints) with the caller's cell edge; work: cs_work_bytes bytes; counters: 24 words, cleared by every
+// shared one (grid_buckets, grid_work_ints) with the caller's cell edge; work: cs_work_bytes bytes; counters: 24 words, cleared by every
 // launch: conf[4][5] row-major, pd_far, the pass-2 list's length, 0, 0.  est_class: one SCVOD_PT_* byte per estimate point
 struct CsLists {  // the semantic classes (label & 0xFFFF) of ground / building / tree truth points
     int32_t n_ground, n_building, n_tree;
@@ -440,7 +448,7 @@ void launch_class_score(const float* gt_xyz, const uint32_t* gt_label, int32_t n
                         const uint8_t* est_keep, int32_t n_est, const CsLists& L, float cell, float max_dist, int32_t rings, int32_t buckets,
                         int* work, unsigned long long* counters, uint8_t* point_result, hipStream_t st);
 
-// a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the evaluation's (ev_buckets, ev_grid_ints)
+// a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the shared one (grid_buckets, grid_work_ints)
 // over the base cloud with the caller's cell edge; work: sp_work_bytes bytes; stats: the 8 words of scvod_map_split_stats, written by
 // every launch.  The optional outputs of SpJob are nullptr when not asked for; mark == nullptr: a byte array inside `work`
 constexpr int kSpTile = 2048;  // base points per tile of the partition (k_exp_count's)

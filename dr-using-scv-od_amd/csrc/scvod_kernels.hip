@@ -13,7 +13,7 @@
 //   SSC::clusterAndCreateFrame (next row f-1)      ssc.cpp:299-393             -> k_cc_scan (one workgroup per scan, union-find in LDS)
 //   refineClusterByBoundingBox + recognize rules   ssc.cpp:437-467,849-872     -> k_cc_scan (same workgroup, boxes in LDS)
 //   SSC::getCloud filter + pcl::VoxelGrid (f-3)    ssc.cpp:1063-1076,1103-1106 -> k_vg_minmax/keys/lut/outoff/final, k_vx_bucket<..., 1>
-//   kd-tree look-ups of evaluate.cpp:79-145                                    -> k_nn_count/fill/query, k_nn_brute_list
+//   kd-tree look-ups of evaluate.cpp:79-145                                    -> k_grid_count/fill, k_nn_query, k_nn_brute_list
 //
 // Design notes: the path is gather/scatter + histogramming + short serial
 // fp32 chains; there is no dense contraction, so no MFMA.  Bit-exact parity with the CPU
@@ -24,7 +24,7 @@
 // tree reductions of those sums.
 #include <type_traits>
 
-#include "scvod_dev.h"
+#include "scvod_grid.h"
 #include "scvod_sortnet.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -785,7 +785,7 @@ void launch_track(const DevParams& P, const Arena& A, const TrackJob& J, int bat
 }
 
 #include "scvod_k_nn_grid.inc"  // uniform-grid correspondence search (A7)
-// work: ints, size >= 3 * buckets + n_map + n_q + 4 + (buckets / 1024 + 1)
+// work: ints, size >= grid_work_ints(buckets, n_map) + n_q + 1
 void launch_nn(const float* map_xyz, int32_t n_map, const float* q_xyz, int32_t n_q, float radius, int32_t* nn_idx,
                float* nn_sq, uint8_t* within, const float origin[3], float cell, int32_t buckets, int* work, int bounded,
                hipStream_t st) {
@@ -795,35 +795,67 @@ void launch_nn(const float* map_xyz, int32_t n_map, const float* q_xyz, int32_t 
                            q_xyz, n_q, radius * radius, nn_idx, nn_sq, within);
         return;
     }
-    NnGrid g;
-    g.ox = origin[0];
-    g.oy = origin[1];
-    g.oz = origin[2];
-    g.inv_h = 1.0f / cell;
-    g.h2 = (0.99f * cell) * (0.99f * cell);  // acceptance radius, a hair inside the cell edge (cell rounding)
-    g.mask = (uint32_t)buckets - 1u;
+    const float h2 = (0.99f * cell) * (0.99f * cell);  // acceptance radius, a hair inside the cell edge (cell rounding)
+    int* todo = work + grid_work_ints(buckets, n_map);
+    int* n_todo = todo + n_q;
+    hipMemsetAsync(n_todo, 0, sizeof(int), st);
+    const PointGrid g = grid_build(map_xyz, 3, nullptr, n_map, origin, cell, buckets, work, st);
+    hipLaunchKernelGGL(k_nn_query, dim3((n_q + 255) / 256), dim3(256), 0, st, g, h2, map_xyz, q_xyz, n_q, radius * radius, nn_idx, nn_sq,
+                       within, todo, n_todo, bounded);
+    if (bounded) return;
+    hipLaunchKernelGGL(k_nn_brute_list, dim3(kPersistCUs * 2), dim3(kNnThreads), 0, st, map_xyz, n_map, q_xyz, todo, n_todo,
+                       radius * radius, nn_idx, nn_sq, within);
+}
+
+// ---- the shared CSR hash grid (scvod_grid.h) ----
+// keep: nullptr, or one byte per point: a point whose byte is 0 is not entered
+__global__ __launch_bounds__(256) void k_grid_count(PointGrid g, const float* __restrict__ xyz, int stride, const uint8_t* __restrict__ keep, int n,
+                                                    int* count) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || (keep && !keep[i])) return;
+    const float* p = xyz + (size_t)stride * (size_t)i;
+    int cx, cy, cz;
+    grid_cell(g, p[0], p[1], p[2], cx, cy, cz);
+    atomicAdd(&count[grid_bucket(g, cx, cy, cz)], 1);
+}
+
+__global__ __launch_bounds__(256) void k_grid_fill(PointGrid g, const float* __restrict__ xyz, int stride, const uint8_t* __restrict__ keep, int n,
+                                                   int* cursor, int* entries) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || (keep && !keep[i])) return;
+    const float* p = xyz + (size_t)stride * (size_t)i;
+    int cx, cy, cz;
+    grid_cell(g, p[0], p[1], p[2], cx, cy, cz);
+    const uint32_t b = grid_bucket(g, cx, cy, cz);
+    entries[g.start[b] + atomicAdd(&cursor[b], 1)] = (int)i;
+}
+
+int32_t grid_buckets(int32_t n) {  // about two buckets per point
+    int32_t buckets = 1024;
+    while (buckets < 2 * (long long)n && buckets < (1 << 26)) buckets <<= 1;
+    return buckets;
+}
+size_t grid_work_ints(int32_t buckets, int32_t n) {
+    return 3 * (size_t)buckets + (size_t)(n > 0 ? n : 1) + 2 + (size_t)buckets / 1024 + 1;
+}
+
+PointGrid grid_build(const float* xyz, int stride, const uint8_t* keep, int32_t n, const float origin[3], float cell, int32_t buckets, int* work,
+                     hipStream_t st) {
     int* count = work;
     int* start = count + buckets;
     int* cursor = start + buckets;
     int* entries = cursor + buckets;
-    int* todo = entries + n_map;
-    int* n_todo = todo + n_q;
-    int* grand = n_todo + 1;
+    int* grand = entries + (n > 0 ? n : 1);
     int* block_tot = grand + 1;
-    const int nb = (buckets + 1023) / 1024;
+    const PointGrid g = {origin[0], origin[1], origin[2], 1.0f / cell, (uint32_t)buckets - 1u, start, count, entries};
+    if (n <= 0) return g;
+    const unsigned blocks = (unsigned)(((long long)n + 255) / 256);
     hipMemsetAsync(count, 0, sizeof(int) * (size_t)buckets, st);
     hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)buckets, st);
-    hipMemsetAsync(n_todo, 0, sizeof(int), st);
-    hipLaunchKernelGGL(k_nn_count, dim3((n_map + 255) / 256), dim3(256), 0, st, g, map_xyz, n_map, count);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(nb), dim3(1024), 0, st, count, start, block_tot, buckets);
-    hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, st, block_tot, nb, grand);
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, st, start, block_tot, buckets);
-    hipLaunchKernelGGL(k_nn_fill, dim3((n_map + 255) / 256), dim3(256), 0, st, g, map_xyz, n_map, start, cursor, entries);
-    hipLaunchKernelGGL(k_nn_query, dim3((n_q + 255) / 256), dim3(256), 0, st, g, map_xyz, q_xyz, n_q, radius * radius, start,
-                       count, entries, nn_idx, nn_sq, within, todo, n_todo, bounded);
-    if (bounded) return;
-    hipLaunchKernelGGL(k_nn_brute_list, dim3(kPersistCUs * 2), dim3(kNnThreads), 0, st, map_xyz, n_map, q_xyz, todo, n_todo,
-                       radius * radius, nn_idx, nn_sq, within);
+    hipLaunchKernelGGL(k_grid_count, dim3(blocks), dim3(256), 0, st, g, xyz, stride, keep, n, count);
+    launch_scan_ints(count, start, block_tot, grand, buckets, st);
+    hipLaunchKernelGGL(k_grid_fill, dim3(blocks), dim3(256), 0, st, g, xyz, stride, keep, n, cursor, entries);
+    return g;
 }
 
 void launch_scan_ints(const int* in, int* out, int* block_tot, int* grand_total, int n, hipStream_t st) {

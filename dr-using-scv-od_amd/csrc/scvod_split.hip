@@ -5,8 +5,7 @@
 // (ssc.cpp:1511-1540: the same look-up into the labelled original cloud, a hit on a rejected label dropped, the hit ids sorted and made
 // unique, the original points at those ids written as the estimate).  Both mark the base points that are the nearest neighbour of some
 // query point and hand out the marked and the unmarked points in base order.  Here:
-//     grid     the CSR hash grid of scvod_eval.hip / scvod_classes.hip (ev_buckets' rule, the same hash, cell and scan kernels) over the
-//              base cloud, with the caller's cell edge and record stride
+//     grid     the shared CSR hash grid of scvod_grid.h over the base cloud, with the caller's cell edge and record stride
 //     pass 1   k_sp_probe: one thread per query, the 27 cells around it.  A query whose candidate lies closer than 0.99 cell edges is
 //              FINISHED (nothing nearer can lie outside the cells it looked at; the evaluation's margin); so is every query of an empty
 //              base.  The others go to a list with their candidate, one atomic per wave (ballot / popcount rank)
@@ -27,66 +26,10 @@
 //              units of 32-bit words: NaN payloads survive.  Integer sums only: the same bytes on every run
 #include <hip/hip_runtime.h>
 
-#include "scvod_dev.h"
+#include "scvod_grid.h"
 
 namespace scvod {
 namespace {
-
-struct SpGrid {
-    float inv_h;
-    uint32_t mask;  // buckets - 1 (power of two)
-    const int* start;
-    const int* count;
-    const int* entries;
-};
-// the hash and the cell of scvod_k_nn_grid.inc with the origin at 0
-__device__ __forceinline__ uint32_t sp_bucket(uint32_t mask, int cx, int cy, int cz) {
-    return ((uint32_t)cx * 73856093u ^ (uint32_t)cy * 19349663u ^ (uint32_t)cz * 83492791u) & mask;
-}
-__device__ __forceinline__ void sp_cell(float inv_h, float x, float y, float z, int& cx, int& cy, int& cz) {
-    cx = (int)floorf(x * inv_h);
-    cy = (int)floorf(y * inv_h);
-    cz = (int)floorf(z * inv_h);
-}
-
-__global__ __launch_bounds__(256) void k_sp_grid_count(float inv_h, uint32_t mask, const float* __restrict__ base, int stride, int n_base, int* count) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_base) return;
-    const float* p = base + (size_t)stride * (size_t)i;
-    int cx, cy, cz;
-    sp_cell(inv_h, p[0], p[1], p[2], cx, cy, cz);
-    atomicAdd(&count[sp_bucket(mask, cx, cy, cz)], 1);
-}
-
-__global__ __launch_bounds__(256) void k_sp_grid_fill(float inv_h, uint32_t mask, const float* __restrict__ base, int stride, int n_base,
-                                                      const int* start, int* cursor, int* entries) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_base) return;
-    const float* p = base + (size_t)stride * (size_t)i;
-    int cx, cy, cz;
-    sp_cell(inv_h, p[0], p[1], p[2], cx, cy, cz);
-    const uint32_t b = sp_bucket(mask, cx, cy, cz);
-    entries[start[b] + atomicAdd(&cursor[b], 1)] = (int)i;  // (the order inside a bucket varies; the tie rule does not depend on it)
-}
-
-// (d, m) against (best, bi): the evaluation's tie rule
-__device__ __forceinline__ void sp_take(float d, int m, float& best, int& bi) {
-    if (m >= 0 && (bi < 0 || d < best || (d == best && m < bi))) {
-        best = d;
-        bi = m;
-    }
-}
-// the candidates of one bucket: the evaluation's expression
-__device__ __forceinline__ void sp_visit(const SpGrid& g, const float* __restrict__ base, int stride, uint32_t b, float qx, float qy, float qz,
-                                         float& best, int& bi) {
-    const int s0 = g.start[b], c = g.count[b];
-    for (int k = 0; k < c; ++k) {
-        const int m = g.entries[s0 + k];
-        const float* p = base + (size_t)stride * (size_t)m;
-        const float ex = p[0] - qx, ey = p[1] - qy, ez = p[2] - qz;
-        sp_take((ex * ex + ey * ey) + ez * ez, m, best, bi);
-    }
-}
 
 // a finished query: its outputs and its neighbour's mark
 __device__ __forceinline__ void sp_finish(const SpJob& J, int q, int bi, float best) {
@@ -101,19 +44,7 @@ __device__ __forceinline__ void sp_finish(const SpJob& J, int q, int bi, float b
     J.mark[bi] = gated ? (uint8_t)SCVOD_SPLIT_GATED : (uint8_t)SCVOD_SPLIT_HIT;
 }
 
-// the unfinished queries of the wave take consecutive slots of a list: one atomic per wave.  Every lane of the wave calls it.
-__device__ __forceinline__ int sp_slot(bool later, int* n) {
-    const unsigned long long bal = __ballot(later);
-    if (!bal) return -1;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)bal) - 1;  // (a grid-stride loop may leave a wave with lane 0 idle)
-    int slot0 = 0;
-    if (lane == leader) slot0 = atomicAdd(n, __popcll(bal));
-    slot0 = __shfl(slot0, leader, 64);
-    return later ? slot0 + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
-}
-
-__global__ __launch_bounds__(256) void k_sp_probe(SpGrid g, SpJob J, float thr1) {
+__global__ __launch_bounds__(256) void k_sp_probe(PointGrid g, SpJob J, float thr1) {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool valid = q < J.n_query;
     bool later = false;
@@ -123,16 +54,12 @@ __global__ __launch_bounds__(256) void k_sp_probe(SpGrid g, SpJob J, float thr1)
         if (J.n_base > 0) {
             const float* p = J.query + (size_t)J.query_stride * (size_t)q;
             const float qx = p[0], qy = p[1], qz = p[2];
-            int cx, cy, cz;
-            sp_cell(g.inv_h, qx, qy, qz, cx, cy, cz);
-            for (int dz = -1; dz <= 1; ++dz)
-                for (int dy = -1; dy <= 1; ++dy)
-                    for (int dx = -1; dx <= 1; ++dx) sp_visit(g, J.base, J.base_stride, sp_bucket(g.mask, cx + dx, cy + dy, cz + dz), qx, qy, qz, best, bi);
+            grid_probe27(g, J.base, J.base_stride, qx, qy, qz, best, bi);
             later = !(bi >= 0 && best < thr1);
         }
         if (!later) sp_finish(J, (int)q, bi, best);
     }
-    const int slot = sp_slot(later, J.n_list1);
+    const int slot = wave_list_slot(later, J.n_list1);
     if (later) {
         J.list1_q[slot] = (int)q;
         J.list1_bi[slot] = bi;
@@ -140,9 +67,9 @@ __global__ __launch_bounds__(256) void k_sp_probe(SpGrid g, SpJob J, float thr1)
     }
 }
 
-__global__ __launch_bounds__(256) void k_sp_rings(SpGrid g, SpJob J, float g1) {
+__global__ __launch_bounds__(256) void k_sp_rings(PointGrid g, SpJob J, float g1) {
     const int nt = *J.n_list1;
-    // whole waves enter the loop body together (the bound is rounded up to the wave), so sp_slot sees every lane
+    // whole waves enter the loop body together (the bound is rounded up to the wave), so wave_list_slot sees every lane
     const long long nt64 = ((long long)nt + 63) & ~63ll;
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < nt64; t += (long long)gridDim.x * 256) {
         bool later = false;
@@ -154,16 +81,10 @@ __global__ __launch_bounds__(256) void k_sp_rings(SpGrid g, SpJob J, float g1) {
             const float* p = J.query + (size_t)J.query_stride * (size_t)q;
             const float qx = p[0], qy = p[1], qz = p[2];
             int cx, cy, cz;
-            sp_cell(g.inv_h, qx, qy, qz, cx, cy, cz);
+            grid_cell(g, qx, qy, qz, cx, cy, cz);
             later = true;
             for (int r = 2; r <= J.max_rings; ++r) {
-                for (int dz = -r; dz <= r; ++dz)
-                    for (int dy = -r; dy <= r; ++dy) {
-                        const bool face = dz == -r || dz == r || dy == -r || dy == r;
-                        // a row of the ring's faces is walked whole, any other row only touches the ring at its two ends
-                        for (int dx = -r; dx <= r; dx += face ? 1 : 2 * r)
-                            sp_visit(g, J.base, J.base_stride, sp_bucket(g.mask, cx + dx, cy + dy, cz + dz), qx, qy, qz, best, bi);
-                    }
+                grid_shell(g, J.base, J.base_stride, cx, cy, cz, r, qx, qy, qz, best, bi);
                 const float reach = g1 * (float)r;
                 if (bi >= 0 && best < reach * reach) {
                     later = false;
@@ -172,7 +93,7 @@ __global__ __launch_bounds__(256) void k_sp_rings(SpGrid g, SpJob J, float g1) {
             }
             if (!later) sp_finish(J, q, bi, best);
         }
-        const int slot = sp_slot(later, J.n_list2);
+        const int slot = wave_list_slot(later, J.n_list2);
         if (later) J.list2_q[slot] = q;  // (the exhaustive scan sees the candidate again: it is not carried)
     }
 }
@@ -195,20 +116,20 @@ __global__ __launch_bounds__(256) void k_sp_exhaustive(SpJob J) {
             for (long long m = threadIdx.x; m < J.n_base; m += 256) {
                 const f4v v = rec[m];
                 const float ex = v.x - qx, ey = v.y - qy, ez = v.z - qz;
-                sp_take((ex * ex + ey * ey) + ez * ez, (int)m, best, bi);
+                grid_take((ex * ex + ey * ey) + ez * ez, (int)m, best, bi);
             }
         } else {
             for (long long m = threadIdx.x; m < J.n_base; m += 256) {
                 const float* b = J.base + 3 * (size_t)m;
                 const float ex = b[0] - qx, ey = b[1] - qy, ez = b[2] - qz;
-                sp_take((ex * ex + ey * ey) + ez * ez, (int)m, best, bi);
+                grid_take((ex * ex + ey * ey) + ez * ez, (int)m, best, bi);
             }
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
             const float ob = __shfl_xor(best, off, 64);
             const int oi = __shfl_xor(bi, off, 64);
-            sp_take(ob, oi, best, bi);
+            grid_take(ob, oi, best, bi);
         }
         if (lane == 0) {
             wbest[w] = best;
@@ -216,7 +137,7 @@ __global__ __launch_bounds__(256) void k_sp_exhaustive(SpJob J) {
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            for (int k = 1; k < 4; ++k) sp_take(wbest[k], wbi[k], best, bi);
+            for (int k = 1; k < 4; ++k) grid_take(wbest[k], wbi[k], best, bi);
             sp_finish(J, q, bi, best);
         }
         __syncthreads();  // (wbest / wbi are written again by the next query)
@@ -336,7 +257,7 @@ SpLayout sp_layout(int32_t buckets, int32_t n_base, int32_t n_query) {
     const size_t nt3 = 3 * (size_t)(L.n_tiles > 0 ? L.n_tiles : 1);
     size_t o = 0;
     L.grid = o;
-    o = sp_up(o + sizeof(int) * ev_grid_ints(buckets, n_base));
+    o = sp_up(o + sizeof(int) * grid_work_ints(buckets, n_base));
     L.list1 = o;  // length | query, candidate, distance
     o = sp_up(o + sizeof(int) * (1 + 3 * nq));
     L.list2 = o;  // length | query
@@ -360,12 +281,6 @@ size_t sp_work_bytes(int32_t buckets, int32_t n_base, int32_t n_query) { return 
 void launch_map_split(SpJob J, float cell, int32_t buckets, void* work, unsigned long long* stats, hipStream_t st) {
     const SpLayout L = sp_layout(buckets, J.n_base, J.n_query);
     unsigned char* w = (unsigned char*)work;
-    int* count = (int*)(w + L.grid);
-    int* start = count + buckets;
-    int* cursor = start + buckets;
-    int* entries = cursor + buckets;
-    int* grand = entries + (J.n_base > 0 ? J.n_base : 1);
-    int* block_tot = grand + 1;
     const size_t nq = (size_t)(J.n_query > 0 ? J.n_query : 1);
     J.n_list1 = (int*)(w + L.list1);
     J.list1_q = J.n_list1 + 1;
@@ -374,26 +289,11 @@ void launch_map_split(SpJob J, float cell, int32_t buckets, void* work, unsigned
     J.n_list2 = (int*)(w + L.list2);
     J.list2_q = J.n_list2 + 1;
     if (!J.mark) J.mark = w + L.mark;
-    SpGrid g;
-    g.inv_h = 1.0f / cell;
-    g.mask = (uint32_t)buckets - 1u;
-    g.start = start;
-    g.count = count;
-    g.entries = entries;
     hipMemsetAsync(J.n_list1, 0, sizeof(int), st);
     hipMemsetAsync(J.n_list2, 0, sizeof(int), st);
-    if (J.n_base > 0) {
-        hipMemsetAsync(J.mark, SCVOD_SPLIT_MISS, (size_t)J.n_base, st);
-        if (J.n_query > 0) {
-            hipMemsetAsync(count, 0, sizeof(int) * (size_t)buckets, st);
-            hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)buckets, st);
-            hipLaunchKernelGGL(k_sp_grid_count, dim3(sp_blocks(J.n_base)), dim3(256), 0, st, g.inv_h, g.mask, J.base, J.base_stride, J.n_base, count);
-            launch_scan_ints(count, start, block_tot, grand, buckets, st);
-            hipLaunchKernelGGL(k_sp_grid_fill, dim3(sp_blocks(J.n_base)), dim3(256), 0, st, g.inv_h, g.mask, J.base, J.base_stride, J.n_base, start,
-                               cursor, entries);
-        }
-    }
+    if (J.n_base > 0) hipMemsetAsync(J.mark, SCVOD_SPLIT_MISS, (size_t)J.n_base, st);
     if (J.n_query > 0) {
+        const PointGrid g = grid_build(J.base, J.base_stride, nullptr, J.n_base, kGridOrigin0, cell, buckets, (int*)(w + L.grid), st);
         const float g1 = 0.99f * cell;
         hipLaunchKernelGGL(k_sp_probe, dim3(sp_blocks(J.n_query)), dim3(256), 0, st, g, J, g1 * g1);
         if (J.n_base > 0) {

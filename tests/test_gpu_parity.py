@@ -830,6 +830,30 @@ def test_nn_search_parity(scvod, oracle):
     ctx.close()
 
 
+def test_nn_radius_search_parity(scvod, oracle):
+    """The bounded path of the grid search (scvod_nn_radius_search): the nearest map point inside the radius or -1 / +inf, against the
+    brute-force oracle.  Radii >= 0.2: the cell edge is the radius."""
+    rng = np.random.default_rng(11)
+    m = rng.uniform(-20, 20, (5000, 3)).astype(np.float32)
+    q = np.concatenate([m[:500] + rng.normal(0, 0.05, (500, 3)).astype(np.float32),
+                        rng.uniform(-20, 20, (700, 3)).astype(np.float32)])
+    P = _params(scvod, "semantickitti")
+    ctx = scvod.Ctx(P, max_points_total=1024, max_scans=1)
+    for radius in (0.25, 0.5):
+        i, d, found = ctx.nn_radius_search(m, q, radius)
+        oi, od, ow = oracle.nn_search(m, q, radius)
+        inside = ow != 0
+        print(f"radius {radius}: {int(inside.sum())} of {len(q)} queries have a neighbour inside")
+        assert 0 < inside.sum() < len(q)
+        assert np.array_equal(i, np.where(inside, oi, -1))
+        assert np.array_equal(d.view(np.uint32), np.where(inside, od, np.float32(np.inf)).view(np.uint32))
+        assert np.array_equal(found != 0, inside)
+    i, d, found = ctx.nn_radius_search(np.zeros((0, 3), np.float32), q, 0.25)
+    print(f"empty map: idx {np.unique(i)}, sqdist {np.unique(d)}")
+    assert (i == -1).all() and np.isposinf(d).all() and not found.any()
+    ctx.close()
+
+
 def test_error_conventions(scvod):
     """Status codes instead of exceptions / aborts (SURVEY 8b error conventions)."""
     import ctypes as C
