@@ -564,8 +564,21 @@ int ensure_merge(scvod_ctx* c) {
     return SCVOD_OK;
 }
 
+// the chunks of a batch of B scans for the chunked opt-in stages: f(s0, s1) for consecutive runs [s0, s1) of at most max_scans scans
+// and at most max_pts points (more points only when a single scan is larger)
+template <typename F>
+void scan_chunks(const std::vector<int32_t>& off, int B, int max_scans, int64_t max_pts, F f) {
+    for (int s0 = 0; s0 < B;) {
+        int s1 = s0 + 1;
+        while (s1 < B && s1 - s0 < max_scans && (int64_t)off[s1 + 1] - off[s0] <= max_pts) ++s1;
+        f(s0, s1);
+        s0 = s1;
+    }
+}
+
 // scratch of the region growing for chunks of up to `chunk` points, and its outputs over the ctx's capacity: allocated on first use
-constexpr int64_t kRgChunkPts = 1 << 23;  // points of the scans of one chunk (more only when a single scan is larger)
+constexpr int64_t kRgChunkPts = 1 << 23;  // points of the scans of one chunk
+constexpr int kRgChunkScans = 65535;      // (the scans of a chunk are a launch grid's y)
 int ensure_rgrow(scvod_ctx* c, int64_t chunk) {
     const size_t N = (size_t)c->cap_pts;
     RgJob& J = c->rg;
@@ -634,12 +647,7 @@ int run_rgrow(scvod_ctx* c, hipStream_t st) {
     const int B = c->A.n_scans;
     const std::vector<int32_t>& off = c->h_scan_off;
     int64_t need = 1;
-    for (int s0 = 0; s0 < B;) {
-        int s1 = s0 + 1;
-        while (s1 < B && s1 - s0 < 65535 && (int64_t)off[s1 + 1] - off[s0] <= kRgChunkPts) ++s1;
-        need = std::max(need, (int64_t)off[s1] - off[s0]);
-        s0 = s1;
-    }
+    scan_chunks(off, B, kRgChunkScans, kRgChunkPts, [&](int s0, int s1) { need = std::max(need, (int64_t)off[s1] - off[s0]); });
     int rc = ensure_rgrow(c, need);
     if (rc) return rc;
     RgJob& J = c->rg;
@@ -651,21 +659,18 @@ int run_rgrow(scvod_ctx* c, hipStream_t st) {
     J.frac = c->rg_frac;
     J.from_apri = c->batch_mode == 2 ? 1 : 0;
     HIPCHK(c, hipMemsetAsync(J.stats, 0, 8 * sizeof(int32_t), st));
-    for (int s0 = 0; s0 < B;) {
-        int s1 = s0 + 1;
-        while (s1 < B && s1 - s0 < 65535 && (int64_t)off[s1 + 1] - off[s0] <= kRgChunkPts) ++s1;
+    scan_chunks(off, B, kRgChunkScans, kRgChunkPts, [&](int s0, int s1) {
         J.s0 = s0;
         J.ns = s1 - s0;
         J.off0 = off[s0];
         launch_rgrow(c->dev, c->A, J, (int)(off[s1] - off[s0]), c->rg_sort_tmp, c->rg_sort_bytes, st, timer_hook, c);
-        s0 = s1;
-    }
+    });
     HIPCHK(c, hipGetLastError());
     return SCVOD_OK;
 }
 
 // scratch of the intensity calibration for chunks of up to `chunk` points: allocated on first use
-constexpr int64_t kCalChunkPts = 1 << 22;  // points of the scans of one chunk (more only when a single scan is larger)
+constexpr int64_t kCalChunkPts = 1 << 22;  // points of the scans of one chunk
 int ensure_calib(scvod_ctx* c, int64_t chunk) {
     if (c->cal_cap >= chunk) return SCVOD_OK;
     CalJob& J = c->cal;
@@ -695,22 +700,12 @@ int ensure_calib(scvod_ctx* c, int64_t chunk) {
     return SCVOD_OK;
 }
 
-template <typename F>
-void calib_chunks(const std::vector<int32_t>& off, int B, F f) {
-    for (int s0 = 0; s0 < B;) {
-        int s1 = s0 + 1;
-        while (s1 < B && s1 - s0 < kCalChunkScans && (int64_t)off[s1 + 1] - off[s0] <= kCalChunkPts) ++s1;
-        f(s0, s1);
-        s0 = s1;
-    }
-}
-
 // the intensity calibration over the batch, chunk by chunk of scans, on stream st (between k_emit and the voxel stage)
 int run_calib(scvod_ctx* c, hipStream_t st) {
     const int B = c->A.n_scans;
     const std::vector<int32_t>& off = c->h_scan_off;
     int64_t need = 1;
-    calib_chunks(off, B, [&](int s0, int s1) { need = std::max(need, (int64_t)off[s1] - off[s0]); });
+    scan_chunks(off, B, kCalChunkScans, kCalChunkPts, [&](int s0, int s1) { need = std::max(need, (int64_t)off[s1] - off[s0]); });
     int rc = ensure_calib(c, need);
     if (rc) return rc;
     CalJob J = c->cal;
@@ -723,7 +718,7 @@ int run_calib(scvod_ctx* c, hipStream_t st) {
     J.force_fallback = force ? 1 : 0;
     HIPCHK(c, hipMemsetAsync(J.stats, 0, 8 * sizeof(int32_t), st));
     HIPCHK(c, hipMemsetAsync(J.cand, 0, sizeof(unsigned long long), st));
-    calib_chunks(off, B, [&](int s0, int s1) {
+    scan_chunks(off, B, kCalChunkScans, kCalChunkPts, [&](int s0, int s1) {
         J.s0 = s0;
         J.ns = s1 - s0;
         J.off0 = off[s0];

@@ -8,8 +8,8 @@
 //                orders them by (scan, cluster, apri index): the positions of the stage
 //   k_rg_group   cluster records at the first position of every cluster
 //   k_rg_grid    per cluster (one workgroup): a uniform grid over its box in CSR form (at most 2 n cells)
-//   k_rg_knn     per point: the exact k nearest points of its cluster, (d^2, index) order, rings of cells widened until the k-th
-//                distance lies strictly below the bound of the unprobed region
+//   k_rg_knn     per point: the exact k nearest points of its cluster in (d^2, index) order
+//                (both on scvod_boxgrid.h: shape, cell rule, CSR build, top-k, ring walk and stop rule are stated there)
 //   k_rg_normal  per point: normal and curvature (scvod_math.h::point_normal_f32)
 //   k_rg_edges   per point: the edges p -> q of the propagation (p capable, |n_p . n_q| not below cos theta), as a bit mask
 //   k_rg_grow    per cluster (one workgroup): min-key propagation to a fixpoint (labels in LDS, or in HBM for large clusters), the
@@ -91,24 +91,10 @@ __global__ __launch_bounds__(kRgThreads) void k_rg_group(Arena A, RgJob J) {
     }
 }
 
-struct RgGrid {
-    float ox, oy, oz, h;
-    int dx, dy, dz;
-};
-__device__ __forceinline__ RgGrid rg_grid_of(const RgJob& J, int c) {
-    const float4 a = J.grid[2 * (size_t)c], b = J.grid[2 * (size_t)c + 1];
-    return RgGrid{a.x, a.y, a.z, a.w, __float_as_int(b.x), __float_as_int(b.y), __float_as_int(b.z)};
-}
-__device__ __forceinline__ int rg_cell1(float v, float o, float h, int d) {
-    const float t = (v - o) / h;
-    int c = t > 0.f ? (int)t : 0;
-    return c < d ? c : d - 1;
-}
-
 // one workgroup per cluster (grid-stride): the grid's shape, the cluster id of its positions, the CSR cells at cell[3 p ..]
 __global__ __launch_bounds__(kRgThreads) void k_rg_grid(RgJob J) {
     __shared__ int wsum[kRgThreads / 64 + 1];
-    __shared__ RgGrid G;
+    __shared__ BoxGrid G;
     const int ncl = J.cnt[1];
     for (int c = blockIdx.x; c < ncl; c += gridDim.x) {
         const int2 cr = J.cl[c];
@@ -117,57 +103,20 @@ __global__ __launch_bounds__(kRgThreads) void k_rg_grid(RgJob J) {
             const uint32_t* mn = J.bmin + 3 * (size_t)nm;
             const uint32_t* mx = J.bmax + 3 * (size_t)nm;
             const float ox = ord2f(mn[0]), oy = ord2f(mn[1]), oz = ord2f(mn[2]);
-            const float ex = ord2f(mx[0]) - ox, ey = ord2f(mx[1]) - oy, ez = ord2f(mx[2]) - oz;
-            float a = fmaxf(ex, fmaxf(ey, ez)), cmin = fminf(ex, fminf(ey, ez));
-            const float b = ex + ey + ez - a - cmin;
-            // about two points per cell on a surface, one in a volume; the kNN below is exact for any cell size
-            float h = fmaxf(fmaxf(sqrtf(a * b / (float)n) * 1.5f, cbrtf(a * b * cmin / (float)n)), 2.f * a / (float)n);
-            if (!(h > 0.f)) h = 1.f;
-            int dx, dy, dz;
-            for (;;) {
-                dx = (int)fminf(ex / h, 1.0e6f) + 1;
-                dy = (int)fminf(ey / h, 1.0e6f) + 1;
-                dz = (int)fminf(ez / h, 1.0e6f) + 1;
-                if ((double)dx * dy * dz <= 2.0 * n) break;
-                h *= 1.25f;
-            }
-            G = RgGrid{ox, oy, oz, h, dx, dy, dz};
-            J.grid[2 * (size_t)c] = make_float4(ox, oy, oz, h);
-            J.grid[2 * (size_t)c + 1] = make_float4(__int_as_float(dx), __int_as_float(dy), __int_as_float(dz), 0.f);
+            G = bg_shape(ox, oy, oz, ord2f(mx[0]) - ox, ord2f(mx[1]) - oy, ord2f(mx[2]) - oz, n, kRgShape);
+            bg_store(J.grid + 2 * (size_t)c, G, 0);
         }
+        for (int k = threadIdx.x; k < n; k += kRgThreads) J.pos_cl[p0 + k] = c;
         __syncthreads();
-        const int nc = G.dx * G.dy * G.dz;
-        int* cell = J.cell + 3 * (size_t)p0;  // nc + 1 <= 2 n + 1 <= 3 n words of this cluster
-        for (int k = threadIdx.x; k <= nc; k += kRgThreads) cell[k] = 0;
-        __syncthreads();
-        for (int k = threadIdx.x; k < n; k += kRgThreads) {
-            const float4 q = J.cxyz[p0 + k];
-            J.pos_cl[p0 + k] = c;
-            const int id = (rg_cell1(q.z, G.oz, G.h, G.dz) * G.dy + rg_cell1(q.y, G.oy, G.h, G.dy)) * G.dx + rg_cell1(q.x, G.ox, G.h, G.dx);
-            J.pcell[p0 + k] = id;
-            atomicAdd(&cell[id], 1);
-        }
-        __syncthreads();
-        int carry = 0;  // exclusive scan of the counts, in place
-        for (int k0 = 0; k0 <= nc; k0 += kRgThreads) {
-            const int k = k0 + threadIdx.x;
-            const int v = k <= nc ? cell[k] : 0;
-            int total;
-            const int ex = block_excl_scan<kRgThreads>(v, total, wsum);
-            if (k <= nc) cell[k] = carry + ex;
-            carry += total;
-            __syncthreads();
-        }
-        // scatter: cell[id] runs as the cursor of cell id; afterwards cell[id] is the END of id = the start of id + 1
-        for (int k = threadIdx.x; k < n; k += kRgThreads) {
-            const int slot = atomicAdd(&cell[J.pcell[p0 + k]], 1);
-            J.cell_pts[p0 + slot] = p0 + k;
-        }
+        // nc + 1 <= 2 n + 1 <= 3 n words of this cluster; the cell order is an indirection: cell_pts[rank] = position
+        bg_csr_build<kRgThreads>(G, n, J.cell + 3 * (size_t)p0, J.pcell + p0, wsum, [&](int k) { return J.cxyz[p0 + k]; },
+                                 [&](int k, int slot, float4) { J.cell_pts[p0 + slot] = p0 + k; });
         __syncthreads();
     }
 }
 
-// the k_eff nearest positions of p's cluster, ascending (d^2, position); d^2 = (dx*dx + dy*dy) + dz*dz in fp32
+// the k_eff nearest positions of p's cluster, ascending (d^2, position): scvod_boxgrid.h's search, the candidates of a run read
+// through cell_pts
 __global__ __launch_bounds__(kRgThreads) void k_rg_knn(RgJob J) {
     const int p = blockIdx.x * kRgThreads + threadIdx.x;
     if (p >= J.cnt[0]) return;
@@ -175,72 +124,29 @@ __global__ __launch_bounds__(kRgThreads) void k_rg_knn(RgJob J) {
     const int2 cr = J.cl[c];
     const int p0 = cr.x, n = cr.y;
     const int keff = n < J.k ? n : J.k;
-    const RgGrid G = rg_grid_of(J, c);
-    const int* cell = J.cell + 3 * (size_t)p0;  // after k_rg_grid: cell[id] = end of id, start of id = id ? cell[id - 1] : 0
+    const BoxGrid G = bg_load(J.grid + 2 * (size_t)c);
+    const int* cell = J.cell + 3 * (size_t)p0;
     const float4 x = J.cxyz[p];
-    const int cx = rg_cell1(x.x, G.ox, G.h, G.dx), cy = rg_cell1(x.y, G.oy, G.h, G.dy), cz = rg_cell1(x.z, G.oz, G.h, G.dz);
-    float bd[16];
-    int bq[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        bd[j] = __uint_as_float(0x7f800000u);
-        bq[j] = 0x7fffffff;
-    }
-    // margin of the bound: rounding of the cell assignment and of the distances
-    const float mg = 1.0e-6f * (fmaxf(fabsf(G.ox), fmaxf(fabsf(G.oy), fabsf(G.oz))) + G.h * (float)max(G.dx, max(G.dy, G.dz))) + 1.0e-6f * G.h;
+    const int cx = bg_cell1(x.x, G.ox, G.h, G.dx), cy = bg_cell1(x.y, G.oy, G.h, G.dy), cz = bg_cell1(x.z, G.oz, G.h, G.dz);
+    float bd[kBoxGridK], kth;
+    int bq[kBoxGridK], kq;
+    bg_topk_clear(bd, bq, kth, kq);
+    const float mg = bg_margin(G);
     for (int r = 0;; ++r) {
-        const int zl = max(cz - r, 0), zh = min(cz + r, G.dz - 1), yl = max(cy - r, 0), yh = min(cy + r, G.dy - 1);
-        for (int z = zl; z <= zh; ++z) {
-            for (int y = yl; y <= yh; ++y) {
-                const bool shell = r == 0 || z == cz - r || z == cz + r || y == cy - r || y == cy + r;
-                const int x0 = max(cx - r, 0), x1 = min(cx + r, G.dx - 1);
-                for (int xx = x0; xx <= x1; ++xx) {
-                    if (!shell && xx != cx - r) {  // inside the ring's box only its two x faces are new
-                        if (cx + r > x1) break;
-                        xx = cx + r;
-                    }
-                    const int id = (z * G.dy + y) * G.dx + xx;
-                    const int e = cell[id], b = id ? cell[id - 1] : 0;
-                    for (int t = b; t < e; ++t) {
-                        const int q = J.cell_pts[p0 + t];
-                        const float4 y4 = J.cxyz[q];
-                        const float ddx = y4.x - x.x, ddy = y4.y - x.y, ddz = y4.z - x.z;
-                        float cd = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                        int cq = q;
-#pragma unroll
-                        for (int j = 0; j < 16; ++j) {
-                            if (j < keff && (cd < bd[j] || (cd == bd[j] && cq < bq[j]))) {
-                                const float td = bd[j];
-                                const int tq = bq[j];
-                                bd[j] = cd;
-                                bq[j] = cq;
-                                cd = td;
-                                cq = tq;
-                            }
-                        }
-                    }
-                }
+        bg_ring_runs(G, cx, cy, cz, r, [&](int ia, int ib, int, int) {
+            int b, e;
+            bg_run(cell, ia, ib, b, e);
+            for (int t = b; t < e; ++t) {
+                const int q = J.cell_pts[p0 + t];
+                const float4 y4 = J.cxyz[q];
+                bg_topk_insert(bg_dist2(y4.x, y4.y, y4.z, x.x, x.y, x.z), q, keff, bd, bq, kth, kq);
             }
-        }
-        // bound of the unprobed region: the nearest face of the probed box that is not a face of the grid
-        float bnd = __uint_as_float(0x7f800000u);
-        if (cx - r > 0) bnd = fminf(bnd, x.x - (G.ox + (float)(cx - r) * G.h));
-        if (cx + r < G.dx - 1) bnd = fminf(bnd, (G.ox + (float)(cx + r + 1) * G.h) - x.x);
-        if (cy - r > 0) bnd = fminf(bnd, x.y - (G.oy + (float)(cy - r) * G.h));
-        if (cy + r < G.dy - 1) bnd = fminf(bnd, (G.oy + (float)(cy + r + 1) * G.h) - x.y);
-        if (cz - r > 0) bnd = fminf(bnd, x.z - (G.oz + (float)(cz - r) * G.h));
-        if (cz + r < G.dz - 1) bnd = fminf(bnd, (G.oz + (float)(cz + r + 1) * G.h) - x.z);
-        if (bnd == __uint_as_float(0x7f800000u)) break;  // the whole grid is probed
-        float kth = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (j == keff - 1) kth = bd[j];
-        const float b = bnd - mg;
-        if (b > 0.f && kth < (b * b) * 0.99999f) break;  // (kth is +inf while fewer than k_eff are found; ties at the bound widen)
+        });
+        if (bg_stop(bg_unprobed(G, cx, cy, cz, r, x.x, x.y, x.z), mg, kth)) break;
     }
     int* out = J.nbr + (size_t)p * J.k;
 #pragma unroll
-    for (int j = 0; j < 16; ++j)
+    for (int j = 0; j < kBoxGridK; ++j)
         if (j < keff) out[j] = bq[j];
 }
 

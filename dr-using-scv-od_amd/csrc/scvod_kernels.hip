@@ -24,6 +24,7 @@
 // tree reductions of those sums.
 #include <type_traits>
 
+#include "scvod_boxgrid.h"
 #include "scvod_grid.h"
 #include "scvod_sortnet.h"
 #include <rocprim/device/device_radix_sort.hpp>

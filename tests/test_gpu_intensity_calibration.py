@@ -117,6 +117,8 @@ def test_batches_equal_the_helper(scvod, oracle, ic, kind):
     got = ctx.batch_intensity_calibration_stats()
     assert {k: got[k] for k in want} == want, (got, want)
     assert got["points"] > 0 and got["cos_floored"] > 0 and ctx.batch_intensity_calibration_candidates() >= got["points"]
+    if kind == "K64":  # both readers of a run (the staged tile, the sorted copy) and a ring beyond the tile were exercised
+        assert 0 < got["fallback_queries"] < got["points"] and got["max_ring"] >= 2, got
     ctx.close()
 
 
