@@ -209,6 +209,11 @@ struct scvod_ctx {
     // and 24 counter words of their own, allocated by the first call
     Scratch cs;  // stream / ran: the last scoring call (scvod_score_classes_stats waits for it)
     unsigned long long* cs_counters = nullptr;
+    // object scores (scvod_score_instances_device, scvod_instances.hip): a grow-only block (the global table, the sort's buffers) and 8
+    // counter words of their own, allocated by the first call; not part of the arena, not the evaluation's and not the class scores'
+    Scratch in;  // stream / ran: the last call (scvod_score_instances_stats waits for it)
+    unsigned long long* in_counters = nullptr;
+    int in_variant = 0;
     // scan stacking (scvod_batch_stack_scans, scvod_stack.hip): the segment and tile tables, one grow-only block of their own allocated
     // by the first call; not part of the arena
     Scratch stk;
@@ -1475,6 +1480,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->ev_counters) hipFree(c->ev_counters);
     if (c->cs.buf) hipFree(c->cs.buf);
     if (c->cs_counters) hipFree(c->cs_counters);
+    if (c->in.buf) hipFree(c->in.buf);
+    if (c->in_counters) hipFree(c->in_counters);
     if (c->stk.buf) hipFree(c->stk.buf);
     if (c->sp.buf) hipFree(c->sp.buf);
     if (c->sp_stats) hipFree(c->sp_stats);
@@ -3322,6 +3329,130 @@ int64_t scvod_score_classes_pass2_queries(scvod_ctx* c) {
 
 int64_t scvod_score_classes_scratch_bytes(scvod_ctx* c) {
     return c ? (int64_t)c->cs.cap + (c->cs_counters ? (int64_t)sizeof(unsigned long long) * 24 : 0) : 0;
+}
+
+// ---- object scores: removal per labelled object (scvod_instances.hip) ----
+void scvod_instance_params_default(scvod_instance_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    const uint16_t st[8] = {10, 31, 30, 32, 16, 13, 18, 20};  // the static counterparts of 252..259, in that order
+    p->n_dynamic_classes = 8;
+    p->n_static_classes = 8;
+    for (int k = 0; k < 8; ++k) {
+        p->dynamic_classes[k] = (uint16_t)(252 + k);
+        p->static_classes[k] = st[k];
+    }
+    p->removed_below = 0.5;
+    p->retained_from = 0.5;
+    p->min_points = 1;
+}
+
+int scvod_instance_finish(const scvod_instance* table, int64_t n, const scvod_instance_params* params, scvod_instance_result* out) {
+    if (n < 0 || (n > 0 && !table) || !out) return SCVOD_ERR_INVALID;
+    scvod_instance_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_instance_params_default(&p);
+    if (p.n_dynamic_classes < 0 || p.n_dynamic_classes > 16 || p.n_static_classes < 0 || p.n_static_classes > 16 ||
+        !std::isfinite(p.removed_below) || !std::isfinite(p.retained_from))
+        return SCVOD_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    for (int64_t i = 0; i < n; ++i) {
+        const scvod_instance& r = table[i];
+        const uint16_t sem = (uint16_t)(r.label & 0xFFFFu);
+        bool dyn = false, stat = false;
+        for (int k = 0; k < p.n_dynamic_classes; ++k) dyn |= sem == p.dynamic_classes[k];
+        for (int k = 0; k < p.n_static_classes; ++k) stat |= sem == p.static_classes[k];
+        if ((r.label >> 16) == 0 || r.n_points < p.min_points || !(dyn || stat)) {
+            ++out->skipped;
+        } else if (dyn) {
+            ++out->hd_gt;
+            out->hd_points += r.n_points;
+            out->hd_points_preserved += r.n_preserved;
+            if ((double)r.n_preserved < p.removed_below * (double)r.n_points) ++out->hd_removed;
+        } else {
+            ++out->ld_gt;
+            out->ld_points += r.n_points;
+            out->ld_points_preserved += r.n_preserved;
+            if ((double)r.n_preserved >= p.retained_from * (double)r.n_points) ++out->ld_retained;
+        }
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();  // scvod_eval_finish's rule for a zero denominator
+    out->hd_removed_rate = out->hd_gt ? 100.0 * (double)out->hd_removed / (double)out->hd_gt : nan;
+    out->ld_retained_rate = out->ld_gt ? 100.0 * (double)out->ld_retained / (double)out->ld_gt : nan;
+    return SCVOD_OK;
+}
+
+int scvod_instance_merge(const scvod_instance* a, int64_t na, const scvod_instance* b, int64_t nb, scvod_instance* out, int64_t cap,
+                         int64_t* n_out) {
+    if (na < 0 || nb < 0 || cap < 0 || (na > 0 && !a) || (nb > 0 && !b) || (cap > 0 && !out) || !n_out) return SCVOD_ERR_INVALID;
+    for (int64_t i = 1; i < na; ++i)
+        if (!(a[i - 1].label < a[i].label)) return SCVOD_ERR_INVALID;
+    for (int64_t i = 1; i < nb; ++i)
+        if (!(b[i - 1].label < b[i].label)) return SCVOD_ERR_INVALID;
+    int64_t i = 0, j = 0, m = 0;
+    while (i < na || j < nb) {
+        scvod_instance r;
+        if (j >= nb || (i < na && a[i].label < b[j].label)) {
+            r = a[i++];
+        } else if (i >= na || b[j].label < a[i].label) {
+            r = b[j++];
+        } else {
+            r = a[i++];
+            const scvod_instance& o = b[j++];
+            r.first_point = o.first_point < r.first_point ? o.first_point : r.first_point;
+            r.n_points += o.n_points;
+            r.n_inlier += o.n_inlier;
+            r.n_preserved += o.n_preserved;
+        }
+        if (m < cap) out[m] = r;
+        ++m;
+    }
+    *n_out = m;
+    return m > cap ? SCVOD_ERR_CAPACITY : SCVOD_OK;
+}
+
+int scvod_score_instances_device(scvod_ctx* c, const uint32_t* d_key, const uint8_t* d_point_result, int64_t n, scvod_instance* d_instances,
+                                 int32_t cap_instances, int64_t* d_n, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n < 0 || n > (int64_t)INT32_MAX || (n > 0 && (!d_key || !d_point_result)) || !d_n)
+        return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (cap_instances < 1 || cap_instances > (1 << 22))
+        return fail(c, SCVOD_ERR_INVALID, "cap_instances %d outside 1 .. %d", cap_instances, 1 << 22);
+    if (((uintptr_t)d_key & 3) || ((uintptr_t)d_instances & 7) || ((uintptr_t)d_n & 7))
+        return fail(c, SCVOD_ERR_INVALID, "d_key must be 4-byte aligned, d_instances and d_n 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->ev.ran ? c->ev.stream : c->stream);
+    if (int rc = counter_block(c, &c->in_counters, 8)) return rc;
+    if (int rc = scratch_reserve(c, c->in, in_work_bytes(cap_instances))) return rc;
+    if (int e = launch_instance_score(d_key, d_point_result, (int32_t)n, d_instances, cap_instances, d_n, c->in.buf, c->in_counters, c->in_variant, st))
+        return fail(c, SCVOD_ERR_HIP, "rocprim radix sort: %s", hipGetErrorString((hipError_t)e));
+    HIPCHK(c, hipGetLastError());
+    c->in.stream = st;
+    c->in.ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_score_instances_stats(scvod_ctx* c, int64_t* h_out4) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out4) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->in.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_score_instances_device on this ctx yet");
+    if (int rc = read_counters(c, c->in_counters, 4, c->in.stream, h_out4)) return rc;
+    if (h_out4[2])
+        return fail(c, SCVOD_ERR_CAPACITY, "more distinct keys than cap_instances (at least %lld found)", (long long)h_out4[1]);
+    return SCVOD_OK;
+}
+
+int64_t scvod_score_instances_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->in.cap + (c->in_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+}
+
+int scvod_set_score_instances_variant(scvod_ctx* c, int32_t variant) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (variant != 0 && variant != 1) return fail(c, SCVOD_ERR_INVALID, "variant %d (0 or 1)", variant);
+    c->in_variant = variant;
+    return SCVOD_OK;
 }
 
 // ---- scan stacking (scvod_stack.hip) ----

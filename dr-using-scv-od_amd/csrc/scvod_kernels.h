@@ -448,6 +448,16 @@ void launch_class_score(const float* gt_xyz, const uint32_t* gt_label, int32_t n
                         const uint8_t* est_keep, int32_t n_est, const CsLists& L, float cell, float max_dist, int32_t rings, int32_t buckets,
                         int* work, unsigned long long* counters, uint8_t* point_result, hipStream_t st);
 
+// the points of a labelled cloud grouped by their 32-bit key (scvod_score_instances_device; scvod_instances.hip).  work: in_work_bytes(cap)
+// bytes (the global table of in_table_slots(cap) slots, the sort's buffers); counters: 8 words, cleared by every launch: records written,
+// distinct keys found, overflow, spilled tiles, then the kernels' own.  out: nullptr counts only.  variant 0: equal keys of a wave are
+// combined before the LDS table (the shipped path); 1: every point adds into the LDS table on its own (tools/instance_score_cost.py's
+// comparison).  Returns 0 or the hipError_t of the sort
+uint32_t in_table_slots(int32_t cap);
+size_t in_work_bytes(int32_t cap);
+int launch_instance_score(const uint32_t* key, const uint8_t* point_result, int32_t n, scvod_instance* out, int32_t cap, int64_t* d_n, void* work,
+                          unsigned long long* counters, int variant, hipStream_t st);
+
 // a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the shared one (grid_buckets, grid_work_ints)
 // over the base cloud with the caller's cell edge; work: sp_work_bytes bytes; stats: the 8 words of scvod_map_split_stats, written by
 // every launch.  The optional outputs of SpJob are nullptr when not asked for; mark == nullptr: a byte array inside `work`

@@ -105,6 +105,26 @@ CLASS_ESTIMATE = ("other", "ground", "building", "tree", "none")
 CLASS_P = 32
 
 
+class InstanceParams(C.Structure):
+    """struct scvod_instance_params (include/scvod.h)"""
+    _fields_ = [("n_dynamic_classes", C.c_int32), ("dynamic_classes", C.c_uint16 * 16), ("n_static_classes", C.c_int32),
+                ("static_classes", C.c_uint16 * 16), ("removed_below", C.c_double), ("retained_from", C.c_double), ("min_points", C.c_int64)]
+
+
+INSTANCE_COUNTS = ("hd_gt", "hd_removed", "ld_gt", "ld_retained", "hd_points", "hd_points_preserved", "ld_points", "ld_points_preserved",
+                   "skipped")
+
+
+class InstanceResult(C.Structure):
+    """struct scvod_instance_result (include/scvod.h)"""
+    _fields_ = [(n, C.c_int64) for n in INSTANCE_COUNTS] + [(n, C.c_double) for n in ("hd_removed_rate", "ld_retained_rate")]
+
+
+# struct scvod_instance: one record of scvod_score_instances_device's table
+INSTANCE_DTYPE = np.dtype([("label", "<u4"), ("first_point", "<i4"), ("n_points", "<i8"), ("n_inlier", "<i8"), ("n_preserved", "<i8")])
+INSTANCE_STATS = ("written", "distinct", "overflow", "spilled_tiles")
+
+
 class SplitParams(C.Structure):
     """struct scvod_split_params (include/scvod.h)"""
     _fields_ = [("cell", C.c_float), ("max_rings", C.c_int32), ("base_stride", C.c_int32), ("query_stride", C.c_int32),
@@ -287,6 +307,13 @@ def load_lib():
         "scvod_score_classes_stats": (C.c_int, [vp, C.POINTER(ClassResult)]),
         "scvod_score_classes_pass2_queries": (i64, [vp]),
         "scvod_score_classes_scratch_bytes": (i64, [vp]),
+        "scvod_score_instances_device": (C.c_int, [vp, vp, vp, i64, vp, i32, vp, vp]),
+        "scvod_score_instances_stats": (C.c_int, [vp, vp]),
+        "scvod_score_instances_scratch_bytes": (i64, [vp]),
+        "scvod_set_score_instances_variant": (C.c_int, [vp, i32]),
+        "scvod_instance_params_default": (None, [C.POINTER(InstanceParams)]),
+        "scvod_instance_finish": (C.c_int, [vp, i64, C.POINTER(InstanceParams), C.POINTER(InstanceResult)]),
+        "scvod_instance_merge": (C.c_int, [vp, i64, vp, i64, vp, i64, C.POINTER(i64)]),
         "scvod_split_params_default": (None, [C.POINTER(SplitParams)]),
         "scvod_map_split_device": (C.c_int, [vp, vp, vp, i32, vp, i32, C.POINTER(SplitParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "scvod_map_split_stats": (C.c_int, [vp, vp]),
@@ -328,6 +355,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_batch_point_classes", "scvod_class_params_default", "scvod_class_finish", "scvod_score_classes_device",
                     "scvod_batch_score_classes", "scvod_score_classes_stats", "scvod_score_classes_pass2_queries",
                     "scvod_score_classes_scratch_bytes",
+                    "scvod_score_instances_device", "scvod_score_instances_stats", "scvod_score_instances_scratch_bytes",
+                    "scvod_set_score_instances_variant", "scvod_instance_params_default", "scvod_instance_finish", "scvod_instance_merge",
                     "scvod_stack_offsets", "scvod_pose_from_matrix", "scvod_batch_stack_scans", "scvod_stack_scans",
                     "scvod_stack_scratch_bytes",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
@@ -391,6 +420,53 @@ def class_finish(conf_and_far):
     r = ClassResult()
     load_lib().scvod_class_finish(cnt.ctypes.data_as(C.c_void_p), C.byref(r))
     return _class_dict(r)
+
+
+def instance_params_default(dynamic_classes=None, static_classes=None, removed_below=None, retained_from=None, min_points=None):
+    """scvod_instance_params with the defaults (dynamic 252..259, their static counterparts, both thresholds 0.5, min_points 1),
+    overridden by keyword"""
+    p = InstanceParams()
+    load_lib().scvod_instance_params_default(C.byref(p))
+    for name, lst in (("dynamic_classes", dynamic_classes), ("static_classes", static_classes)):
+        if lst is not None:
+            cl = [int(v) for v in lst]
+            setattr(p, "n_" + name, len(cl))  # (more than 16: scvod_instance_finish refuses them)
+            arr = getattr(p, name)
+            for k in range(16):
+                arr[k] = cl[k] if k < len(cl) else 0
+    if removed_below is not None:
+        p.removed_below = float(removed_below)
+    if retained_from is not None:
+        p.retained_from = float(retained_from)
+    if min_points is not None:
+        p.min_points = int(min_points)
+    return p
+
+
+def _status(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed with status {rc}")
+
+
+def instance_finish(table, params=None):
+    """a table of INSTANCE_DTYPE records -> the dict of scvod_instance_result (object counts, point sums, the two rates).  Host only"""
+    t = np.ascontiguousarray(table, INSTANCE_DTYPE).reshape(-1)
+    r = InstanceResult()
+    _status(load_lib().scvod_instance_finish(t.ctypes.data_as(C.c_void_p) if t.size else None, t.size,
+                                             C.byref(params) if params is not None else None, C.byref(r)), "scvod_instance_finish")
+    return {k: getattr(r, k) for k, _ in InstanceResult._fields_}
+
+
+def instance_merge(a, b):
+    """two tables ascending by key -> one: counts added, first_point the smaller of the two.  Host only"""
+    a = np.ascontiguousarray(a, INSTANCE_DTYPE).reshape(-1)
+    b = np.ascontiguousarray(b, INSTANCE_DTYPE).reshape(-1)
+    out = np.zeros(a.size + b.size, INSTANCE_DTYPE)
+    n = C.c_int64(0)
+    _status(load_lib().scvod_instance_merge(a.ctypes.data_as(C.c_void_p) if a.size else None, a.size,
+                                            b.ctypes.data_as(C.c_void_p) if b.size else None, b.size,
+                                            out.ctypes.data_as(C.c_void_p) if out.size else None, out.size, C.byref(n)), "scvod_instance_merge")
+    return out[:n.value].copy()
 
 
 def split_params_default(cell=None, max_rings=None, base_stride=None, query_stride=None, reject_classes=None):
@@ -1061,6 +1137,55 @@ class Ctx:
     def score_classes_scratch_bytes(self):
         """device scratch of the class scores on this ctx (not part of arena_bytes or evaluate_scratch_bytes)"""
         return int(self.lib.scvod_score_classes_scratch_bytes(self.h))
+
+    # ---- object scores from a device instance table (include/scvod.h: scvod_score_instances_device ...) ----
+    def score_instances_device(self, d_key, d_point_result, cap_instances=65536, d_instances=None, stream=None, count_only=False):
+        """the points grouped by their 4-byte key and counted per group: d_key 4-byte words and d_point_result uint8 (the bytes of
+        evaluate_device / batch_evaluate), contiguous CUDA tensors of one length.  d_instances: a CUDA tensor of at least
+        cap_instances * 32 bytes, allocated when None; count_only=True passes none at all.  Returns (d_instances, d_n): the records as
+        bytes (view them with INSTANCE_DTYPE after the download) and the int64 [1] record count, both on the device.  Asynchronous on
+        `stream`: score_instances_stats()"""
+        import torch
+        n = int(d_key.numel())
+        assert d_key.is_contiguous() and d_key.element_size() == 4
+        assert d_point_result.is_contiguous() and d_point_result.element_size() == 1 and d_point_result.numel() >= n
+        cap = int(cap_instances)
+        if count_only:
+            d_instances = None
+        elif d_instances is None:
+            d_instances = torch.empty(max(cap, 1) * INSTANCE_DTYPE.itemsize, dtype=torch.uint8, device=d_key.device)
+        else:
+            assert d_instances.is_contiguous() and d_instances.numel() * d_instances.element_size() >= cap * INSTANCE_DTYPE.itemsize
+        d_n = torch.empty(1, dtype=torch.int64, device=d_key.device)
+        self._chk(self.lib.scvod_score_instances_device(self.h, C.c_void_p(d_key.data_ptr()) if n else None,
+                                                        C.c_void_p(d_point_result.data_ptr()) if n else None, n,
+                                                        C.c_void_p(d_instances.data_ptr()) if d_instances is not None else None, cap,
+                                                        C.c_void_p(d_n.data_ptr()), C.c_void_p(stream or 0)))
+        return d_instances, d_n
+
+    def score_instances_stats(self):
+        """{written, distinct, overflow, spilled_tiles} of the last score_instances_device; synchronises its stream; raises after an
+        overflow"""
+        out = np.zeros(4, np.int64)
+        self._chk(self.lib.scvod_score_instances_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(zip(INSTANCE_STATS, (int(v) for v in out)))
+
+    def score_instances_scratch_bytes(self):
+        """device scratch of the object scores on this ctx (not part of arena_bytes or the other stages' scratch)"""
+        return int(self.lib.scvod_score_instances_scratch_bytes(self.h))
+
+    def batch_score_instances(self, d_gt_label, poses, flags=0, eval_params=None, cap_instances=65536, stream=None):
+        """batch_evaluate with a result byte per input point, then score_instances_device keyed by d_gt_label on the same stream, no
+        host synchronisation in between.  One read at the end returns the table as a numpy array of INSTANCE_DTYPE; evaluate_stats()
+        holds the batch's counters"""
+        import torch
+        n = self._n_pts
+        res = torch.empty(max(n, 1), dtype=torch.uint8, device=d_gt_label.device)
+        self.batch_evaluate(d_gt_label, poses, flags=flags, params=eval_params, d_point_result=res, stream=stream)
+        # (stream None: the library runs the scoring on the evaluation's stream)
+        d_inst, _ = self.score_instances_device(d_gt_label.reshape(-1)[:n], res[:n], cap_instances=cap_instances, stream=stream)
+        written = self.score_instances_stats()["written"]
+        return d_inst[:written * INSTANCE_DTYPE.itemsize].cpu().numpy().view(INSTANCE_DTYPE).copy()
 
     # ---- a map split by nearest-neighbour hits on the device (include/scvod.h: scvod_map_split_device ...) ----
     def map_split_device(self, d_base, d_query, params=None, d_base_label=None, d_mark=None, d_order=None, d_seg4=None, d_base_out=None,

@@ -1031,6 +1031,74 @@ int64_t scvod_score_classes_pass2_queries(scvod_ctx* ctx);
 /* bytes of device scratch the class scores hold on this ctx (0 before the first call) */
 int64_t scvod_score_classes_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- object scores: removal per labelled object, from a device instance table (opt-in: nothing runs or is allocated unless it is
+ * called) ----------------------------------------------------------------------------------------------------------------------------
+ * Reference analogue: tool/plotIoU.py:70-84 plots, per sequence, the high-dynamic objects of the truth (HD_gt) and how many of them were
+ * removed (HD_removed), the low-dynamic objects (LD_gt) and how many were retained (LD_retained).  The numbers are hard-coded there and no
+ * program of the reference computes them: the object rule below is THIS PROJECT'S CONVENTION.  SemanticKITTI
+ * labels carry what it needs -- label & 0xFFFF the class, label >> 16 the instance -- and scvod_evaluate_device / scvod_batch_evaluate
+ * write one byte per truth point that says whether the point survived.  The device part groups the points by their 32-bit label and
+ * counts per group: integer sums and a minimum, the same bytes on every run and for every order of the points. */
+typedef struct scvod_instance { /* 32 bytes */
+    uint32_t label;
+    int32_t first_point;  /* lowest point index carrying this key */
+    int64_t n_points;
+    int64_t n_inlier;     /* bit 0 of the result byte */
+    int64_t n_preserved;  /* bit 0 set and (bit 1 set) == (bit 2 set): analysis.py's rule (num_static_preserved + num_dynamic_preserved) */
+} scvod_instance;
+/* d_key [n] one uint32 per point (the truth labels; opaque to the device: every value is a legal key, 0 and 0xFFFFFFFF included);
+ * d_point_result [n] the bytes of scvod_evaluate_device / scvod_batch_evaluate (only bits 0-2 are read).  d_instances [cap_instances]
+ * receives one record per distinct key, ascending by key; NULL counts only.  d_n [1] receives the record count ON THE DEVICE -- a
+ * consumer on the same stream needs no host read.  cap_instances (1 .. 1 << 22) sizes the output and the global hash table (a power of
+ * two of slots, at least 2 * cap_instances).  More distinct keys than cap_instances is an overflow: nothing is written at or behind
+ * cap_instances, d_n[0] = -1, and the records inside the buffer are unspecified.  Stream-ordered, never synchronises with the host;
+ * stream NULL = the stream of the ctx's last scvod_evaluate_device / scvod_batch_evaluate (the call whose bytes it reads), or the ctx's
+ * stream when there was none.  Each call overwrites the stats of the one before, and the calls of one ctx must be ordered among
+ * themselves (they share their scratch).  Argument errors (NULL ctx, n < 0 or n > INT32_MAX, a NULL array with n > 0, cap_instances
+ * outside 1 .. 1 << 22, d_n NULL, d_instances or d_n not 8-byte aligned) are SCVOD_ERR_INVALID before any device is looked for.
+ * Scratch (40 bytes per table slot, 24 bytes per record for the sort and its temporary storage, 8 counter words) is an allocation of
+ * its own, grow-only, freed by scvod_destroy and NOT part of scvod_arena_bytes, scvod_evaluate_scratch_bytes or
+ * scvod_score_classes_scratch_bytes; a call that needs more than any before waits for the one in flight before it grows. */
+int scvod_score_instances_device(scvod_ctx* ctx, const uint32_t* d_key, const uint8_t* d_point_result, int64_t n, scvod_instance* d_instances,
+                                 int32_t cap_instances, int64_t* d_n, void* stream);
+/* h_out4 = {records written (counting only: that would have been), distinct keys found, overflow, tiles whose on-chip table spilled} of
+ * the last scvod_score_instances_device.  Synchronises that call's stream.  After an overflow h_out4 is filled ("distinct keys found" is
+ * then a lower bound, records written 0) and the call returns SCVOD_ERR_CAPACITY.  SCVOD_ERR_STATE before the first call. */
+int scvod_score_instances_stats(scvod_ctx* ctx, int64_t* h_out4);
+/* bytes of device scratch the object scores hold on this ctx (0 before the first call) */
+int64_t scvod_score_instances_scratch_bytes(scvod_ctx* ctx);
+/* Development switch behind profiles/instance_score_cost.txt, never needed for a result: 0 (the default) combines the equal keys of a
+ * wave before they reach the on-chip table; 1 lets every point add into the on-chip table on its own.  The tables are identical. */
+int scvod_set_score_instances_variant(scvod_ctx* ctx, int32_t variant);
+typedef struct scvod_instance_params {
+    int32_t n_dynamic_classes;    /* 0..16 */
+    uint16_t dynamic_classes[16]; /* classes (label & 0xFFFF) of high-dynamic objects; default 252..259 */
+    int32_t n_static_classes;     /* 0..16 */
+    uint16_t static_classes[16];  /* classes of low-dynamic objects; default 10, 31, 30, 32, 16, 13, 18, 20 */
+    double removed_below;         /* an HD object is removed iff n_preserved < removed_below * n_points; default 0.5 */
+    double retained_from;         /* an LD object is retained iff n_preserved >= retained_from * n_points; default 0.5 */
+    int64_t min_points;           /* smaller records are skipped; default 1 */
+} scvod_instance_params;
+/* dynamic classes 252..259; static classes 10, 31, 30, 32, 16, 13, 18, 20 (the SemanticKITTI static counterparts of 252..259 in that
+ * order: car, bicyclist, person, motorcyclist, on-rails, bus, truck, other-vehicle); both thresholds 0.5; min_points 1 */
+void scvod_instance_params_default(scvod_instance_params* p);
+typedef struct scvod_instance_result {
+    int64_t hd_gt, hd_removed, ld_gt, ld_retained;
+    int64_t hd_points, hd_points_preserved, ld_points, ld_points_preserved;
+    int64_t skipped;
+    double hd_removed_rate, ld_retained_rate; /* 100.0 * hd_removed / hd_gt and 100.0 * ld_retained / ld_gt; NaN for a zero denominator */
+} scvod_instance_result;
+/* Host only, no device.  A record is an object iff label >> 16 != 0, n_points >= min_points and its class is in one of the two lists
+ * (dynamic wins when it is in both); every other record counts in `skipped`.  The products are taken in double:
+ * (double)n_preserved < removed_below * (double)n_points, (double)n_preserved >= retained_from * (double)n_points.  params NULL = the
+ * defaults.  SCVOD_ERR_INVALID: a NULL table with n > 0, n < 0, out NULL, a list length outside 0..16, a threshold that is not finite. */
+int scvod_instance_finish(const scvod_instance* table, int64_t n, const scvod_instance_params* params, scvod_instance_result* out);
+/* Host only.  Two tables ascending by key -> one (the batches or shards of one sequence scored together): counts are added, first_point
+ * is the smaller of the two.  *n_out is the true size; SCVOD_ERR_CAPACITY when it exceeds cap (nothing is written behind cap; out may
+ * be NULL with cap 0: count only).  SCVOD_ERR_INVALID for an input that is not strictly ascending (nothing is written then). */
+int scvod_instance_merge(const scvod_instance* a, int64_t na, const scvod_instance* b, int64_t nb, scvod_instance* out, int64_t cap,
+                         int64_t* n_out);
+
 /* ---- scan stacking: neighbouring scans moved into the middle scan's frame, on the device (opt-in: nothing runs or is allocated
  * unless it is called) -------------------------------------------------------------------------------------------------------------
  * Reference analogue: src/makeScan.cpp:153-244, the stacker in front of the path for sparse, non-repetitive sensors.  Output scan
