@@ -246,6 +246,8 @@ struct scvod_ctx {
     int batch_mode = 0;          // do_patchwork of the last batch: 1 Patchwork+binning, 0 binning only, 2 caller's apri_vec
     bool apri_compact = false;   // PointAPRI records not materialised yet (k_apri_expand on request)
     bool voxels_valid = false;   // the last batch ran the voxel stage in descriptor mode (not VoxelGrid)
+    int desc_mode = 0;           // scvod_set_voxel_descriptors: 0 vox_av / vox_cov of a batch on demand (lean voxel stage), 1 eager
+    bool desc_valid = false;     // vox_av / vox_cov hold the last batch's values (ensure_descriptors fills them otherwise)
     bool clusters_valid = false;
     bool clustered_this_batch = false;       // the batch's pt_mapcls bytes carry car / dynamic marks of an earlier clustering (cleared before the next one)
     bool types_valid = false;
@@ -756,8 +758,10 @@ int merge_check(scvod_ctx* c) {
     return SCVOD_OK;
 }
 
+// lean_ok: a batch entry, whose descriptors may wait for their first reader (ensure_descriptors); the per-scan API hands them to the
+// host at once and keeps the fused form
 int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_scans, hipStream_t st,
-              int do_patchwork, int apply_filter, int do_voxels, int sync, bool off_pinned = false) {
+              int do_patchwork, int apply_filter, int do_voxels, int sync, bool off_pinned = false, bool lean_ok = false) {
     if (!c) return SCVOD_ERR_INVALID;
     if (n_scans <= 0 || !h_off || (!d_xyzi && do_patchwork != 2)) return fail(c, SCVOD_ERR_INVALID, "empty batch");
     unmerge_view(c);
@@ -799,10 +803,15 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
     c->batch_valid = false;
     c->counts_valid = false;
     c->voxels_valid = false;
+    c->desc_valid = false;
     c->clusters_valid = false;
     c->types_valid = false;
     c->track_valid = false;
     c->tables_valid = false;
+    // a ctx with the intensity merge on reads every descriptor in its clustering: it keeps the fused form (lean + on demand measured
+    // 0.7 ms slower for it, profiles/lazy_voxel_descriptors_cost.md; SCVOD_VOX_LEAN_MERGE: development, that measurement)
+    static const bool lean_merge = getenv("SCVOD_VOX_LEAN_MERGE") != nullptr;
+    const int lean = (lean_ok && do_voxels && do_patchwork != 3 && c->desc_mode == 0 && (c->im_iterations == 0 || lean_merge)) ? 1 : 0;
     // marks per input point for the static map (car-cluster member / dynamic / list marks): clean for every new batch
     if (mx > 0 && do_patchwork != 2 && do_patchwork != 3) HIPCHK(c, hipMemsetAsync(c->A.pt_mapcls, 0, (size_t)total, st));
     c->clustered_this_batch = false;
@@ -811,9 +820,9 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
         launch_process(c->dev, c->A, st, 1, apply_filter, 0, timer_hook, c);
         const int rc_cal = run_calib(c, st);
         if (rc_cal) return rc_cal;
-        if (do_voxels) launch_process(c->dev, c->A, st, 4, apply_filter, 1, timer_hook, c);
+        if (do_voxels) launch_process(c->dev, c->A, st, 4, apply_filter, 1, timer_hook, c, lean);
     } else if (mx > 0) {
-        launch_process(c->dev, c->A, st, do_patchwork, apply_filter, do_voxels, timer_hook, c);
+        launch_process(c->dev, c->A, st, do_patchwork, apply_filter, do_voxels, timer_hook, c, lean);
     }
     c->cal_done = c->cal_on && do_patchwork == 1;  // (a batch of empty scans is a calibrated batch of no points)
     HIPCHK(c, hipGetLastError());
@@ -823,6 +832,7 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
     }
     c->batch_valid = true;
     c->voxels_valid = (do_voxels != 0);
+    c->desc_valid = (do_voxels != 0) && !lean;  // (every process call decides it again: a lean batch's descriptors are not there yet)
     c->have_patchwork = (do_patchwork == 1);
     c->batch_mode = do_patchwork;
     c->apri_compact = (do_patchwork == 1);
@@ -838,6 +848,17 @@ int ensure_counts(scvod_ctx* c) {
     c->h_counts.resize((size_t)c->A.n_scans * 8);
     HIPCHK(c, hipMemcpy(c->h_counts.data(), c->A.counts, sizeof(int32_t) * c->h_counts.size(), hipMemcpyDeviceToHost));
     c->counts_valid = true;
+    return SCVOD_OK;
+}
+
+// Every reader of vox_av / vox_cov comes through here first: a lean voxel stage left them unwritten, k_vx_descriptors fills them for the
+// whole batch on stream st -- ordered behind the batch's own kernels there -- at the first request.  Its inputs (vox_pt_begin, vox_pts,
+// apri_int) are written by the voxel stage and its predecessors only; no later stage uses them as scratch.
+int ensure_descriptors(scvod_ctx* c, hipStream_t st) {
+    if (!c->voxels_valid || c->desc_valid) return SCVOD_OK;
+    launch_vox_descriptors(c->A, 0, c->A.n_scans, st, timer_hook, c);
+    HIPCHK(c, hipGetLastError());
+    c->desc_valid = true;
     return SCVOD_OK;
 }
 
@@ -862,6 +883,7 @@ int fetch_scan(scvod_ctx* c, int32_t s, scvod_scan_result* out) {
     }
     const Arena& A = c->A;
     hipStream_t st = c->last_stream;
+    if (int rc_desc = ensure_descriptors(c, st)) return rc_desc;
     if (c->have_patchwork) launch_cls(A, s, base, k[0], st);
     if (c->apri_compact && k[4] > 0) launch_apri_expand(c->dev, A, s, 1, k[4], st);  // PointAPRI records of this scan only
     if (c->apri_compact && c->cal_done) launch_calib_apri(A, s, k[4], st);             // ... with the calibrated intensity (a second small
@@ -1627,7 +1649,7 @@ int scvod_track_probe(scvod_ctx* c, const float* h_xyzi, const int32_t* h_offset
 
 int scvod_batch_process(scvod_ctx* c, const void* d_xyzi, const int32_t* h_scan_offsets, int32_t n_scans, void* stream,
                         int32_t sync) {
-    return run_batch(c, d_xyzi, h_scan_offsets, n_scans, (hipStream_t)stream, 1, 1, 1, sync);
+    return run_batch(c, d_xyzi, h_scan_offsets, n_scans, (hipStream_t)stream, 1, 1, 1, sync, false, true);
 }
 
 int scvod_batch_counts(scvod_ctx* c, int32_t* h_out) {
@@ -1671,6 +1693,7 @@ int scvod_batch_cluster(scvod_ctx* c, void* stream, int32_t sync) {
     }
     launch_cluster(c->dev, c->A, c->batch_mode == 2 ? 1 : 0, st, timer_hook, c);
     if (c->im_iterations > 0) {  // (before the max_name passes: they read pt_cluster, left as it was, and the post-merge pt_type)
+        if (int rc_desc = ensure_descriptors(c, st)) return rc_desc;  // (the merge compares vox_av / vox_cov)
         c->im.iterations = c->im_iterations;
         c->im.search_c = c->im_search_c;
         c->im.diff = c->im_diff;
@@ -2249,6 +2272,13 @@ int scvod_set_intensity_merge(scvod_ctx* c, int32_t iterations, int32_t search_c
     c->im_diff = intensity_diff;
     c->im_cov = intensity_cov;
     c->clusters_valid = c->types_valid = c->tables_valid = c->track_valid = false;
+    return SCVOD_OK;
+}
+
+int scvod_set_voxel_descriptors(scvod_ctx* c, int32_t mode) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (mode != 0 && mode != 1) return fail(c, SCVOD_ERR_INVALID, "voxel descriptors: mode %d is neither 0 (on demand) nor 1 (eager)", mode);
+    c->desc_mode = mode;  // (takes effect with the next batch; the current one keeps what it has)
     return SCVOD_OK;
 }
 
@@ -2841,7 +2871,7 @@ int scvod_sequence_ingest(scvod_ctx* c, const float* h_xyzi, const int32_t* h_sc
         if (rc == SCVOD_OK && (hipEventRecord(c->ingest_copied[b], c->copy_stream) != hipSuccess ||
                                hipStreamWaitEvent(st, c->ingest_copied[b], 0) != hipSuccess))
             rc = fail(c, SCVOD_ERR_HIP, "ingest event");
-        if (rc == SCVOD_OK) rc = run_batch(c, c->ingest_buf[b], po, ns, st, 1, 1, 1, 0, true);
+        if (rc == SCVOD_OK) rc = run_batch(c, c->ingest_buf[b], po, ns, st, 1, 1, 1, 0, true, true);
         if (rc == SCVOD_OK && fn) {
             const int frc = fn(user, c, s0, ns, (void*)st);
             if (frc != SCVOD_OK) rc = fail(c, frc, "chunk callback returned %d", frc);

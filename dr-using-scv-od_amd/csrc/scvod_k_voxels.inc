@@ -191,16 +191,63 @@ __global__ __launch_bounds__(1024) void k_vx_partition(DevParams P, Arena A) {
 #define SCVOD_VOX_K32_LDS 1
 #endif
 constexpr size_t vox_key_bytes(int cap, size_t ksize) { return (((size_t)(cap + cap / 8) * (SCVOD_VOX_K32_LDS ? ksize : 8)) + 15) & ~(size_t)15; }
-constexpr size_t vox_lds_bytes(int cap, size_t ksize = 8) { return vox_key_bytes(cap, ksize) + (size_t)cap * 8 + 128; }
+// DESC = false (the lean form): no staged intensities; what is left of that area holds the <= 128 (chunk, wave) head counts
+constexpr size_t vox_aux_bytes(int cap, bool desc) { return desc ? (size_t)cap * 4 : ((size_t)(cap / 64) * 4 + 15) & ~(size_t)15; }
+constexpr size_t vox_lds_bytes(int cap, size_t ksize = 8, bool desc = true) {
+    return vox_key_bytes(cap, ksize) + (size_t)cap * 4 + vox_aux_bytes(cap, desc) + 128;
+}
+// workgroups per CU of the lean 4096 tier with 32-bit keys (x2 for the 2048 tier): 35.2 KB of LDS each, four fit where the full form's
+// 51.3 KB allows three (profiles/lazy_voxel_descriptors_cost.md has both measured)
+#ifndef SCVOD_VOX_LEAN_MORE
+#define SCVOD_VOX_LEAN_MORE 4
+#endif
+#ifndef SCVOD_VOX_LEAN_S
+#define SCVOD_VOX_LEAN_S 12  // workgroups per CU of the lean 1024 tier (8.9 KB of LDS each; the fused form runs eight)
+#endif
+// The intensity descriptor of one voxel (SSC::makeHashCloud's intensity_av / intensity_cov): fp32 running sum in list order, divided by
+// float(count); population variance accumulated as float += double.  ONE routine for the fused form (k_vx_bucket<..., DESC = true>)
+// and the on-demand kernel (k_vx_descriptors), so their bits cannot drift apart.  at(j): intensity of the voxel's j-th point;
+// U values are fetched together before they are added in order (U > 1 where at() is a chain of global loads).
+template <int U, typename F>
+__device__ __forceinline__ void vx_descriptor(int n, F&& at, float& av_out, float& cov_out) {
+    float av = 0.f;
+    for (int j0 = 0; j0 < n; j0 += U) {
+        float x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) x[u] = (j0 + u < n) ? at(j0 + u) : 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (j0 + u < n) av += x[u];
+    }
+    const float fn = (float)n;
+    av = av / fn;
+    float cov = 0.f;
+    for (int j0 = 0; j0 < n; j0 += U) {
+        float x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) x[u] = (j0 + u < n) ? at(j0 + u) : 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (j0 + u < n) {
+                const double d = (double)(x[u] - av);
+                cov = (float)((double)cov + d * d);
+            }
+    }
+    av_out = av;
+    cov_out = cov / fn;
+}
 // which tiers run the pad-free network (scvod_sortnet.h): those measured faster with it (profiles/padfree_sort_cost.md);
 // the 256 and 1024 tiers are slower, they keep the padded network.  SCVOD_VOX_PADFREE=0: none, 2: all
 constexpr bool vx_bucket_padfree(int cap) { return SCVOD_VOX_PADFREE == 2 || (SCVOD_VOX_PADFREE == 1 && cap >= 2048); }
-template <int CAP, int THREADS, int C_LO, int C_HI, int LGE, int MODE = 0, typename KT = unsigned long long>
+// DESC = false (MODE 0 only): the lean form of a batch whose descriptors are computed on demand (k_vx_descriptors) -- no intensity
+// staging, no per-voxel sums, no tmp_vox_av / tmp_vox_cov
+template <int CAP, int THREADS, int C_LO, int C_HI, int LGE, int MODE = 0, typename KT = unsigned long long, bool DESC = true>
 __global__ __launch_bounds__(THREADS)
 #if SCVOD_VOX_K32_LDS
-__attribute__((amdgpu_waves_per_eu((sizeof(KT) == 4 && CAP <= 4096 && CAP >= 2048) ? 6 : 1, 8)))
+__attribute__((amdgpu_waves_per_eu((sizeof(KT) == 4 && CAP <= 4096 && CAP >= 2048) ? (DESC ? 6 : 2 * SCVOD_VOX_LEAN_MORE) : 1, 8)))
 #endif
 void k_vx_bucket(DevParams P, Arena A) {
+    static_assert(DESC || MODE == 0, "the lean form is makeHashCloud's");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool K32 = sizeof(KT) == 4;
     constexpr bool PADFREE = vx_bucket_padfree(CAP);
@@ -211,8 +258,8 @@ void k_vx_bucket(DevParams P, Arena A) {
     constexpr size_t KB = vox_key_bytes(CAP, sizeof(KT));
     static_assert(KB >= (size_t)SLOTS * sizeof(KT), "key area");
     int* l_vbeg = (int*)(smem + KB);                         // [CAP]
-    float* l_int = (float*)(smem + KB + (size_t)CAP * 4);    // [CAP] intensity in sorted order
-    int* wsum = (int*)(smem + KB + (size_t)CAP * 8);
+    float* l_int = (float*)(smem + KB + (size_t)CAP * 4);    // [CAP] intensity in sorted order (DESC), else the [CAP / 64] head counts only
+    int* wsum = (int*)(smem + KB + (size_t)CAP * 4 + vox_aux_bytes(CAP, DESC));
     int lo, hi;
     order_range(A.vorder_off, C_LO, C_HI, lo, hi);
     constexpr bool PV = (CAP == 4096 && MODE == 0);  // (profiling build: the dominant tier is clocked)
@@ -286,7 +333,7 @@ void k_vx_bucket(DevParams P, Arena A) {
     } else {
         keys = gkeys;
         vbeg = A.tmp_vox_begin + (size_t)base + off;  // rewritten below with final values
-        ints = A.tmp_vox_av + (size_t)base + off;     // m >= nv entries: used as staging, rewritten below
+        ints = nullptr;                               // (the per-voxel loops gather from apri_int themselves)
         block_bitonic_sort<THREADS, false>(keys, m);
     }
 #define KX(j) (in_lds ? sort_slot<PADK>(j) : (j))
@@ -295,7 +342,7 @@ void k_vx_bucket(DevParams P, Arena A) {
     if (in_lds) {
         // two barriers for the whole bucket instead of three per THREADS keys: heads counted per (chunk, wave) by ballot, ONE prefix
         // over those <= CAP / 64 counts (two per lane of the first wave), then every head knows its place.  The counts borrow the
-        // intensity area, which is idle until the staging below.
+        // intensity area, which is idle until the staging below (the lean form keeps just these counts of it).
         constexpr int NW = THREADS / 64;
         static_assert(CAP / 64 <= 128, "two (chunk, wave) counts per lane");
         int* wcnt = (int*)l_int;
@@ -377,39 +424,42 @@ void k_vx_bucket(DevParams P, Arena A) {
         __syncthreads();  // LDS is reused by the next item
         continue;
     }
-    if (in_lds) {
-        for (int j = threadIdx.x; j < m; j += THREADS) ints[j] = A.apri_int[(size_t)base + k_idx(keys[KX(j)])];
-        __syncthreads();
-    }
-    if (PV) PROF_MARK(3, 3);
-    // per voxel: sequential fp32 mean, then population variance accumulated as float += double
-    for (int v = threadIdx.x; v < nv; v += THREADS) {
-        const int j0 = vbeg[v];
-        const int j1 = (v + 1 < nv) ? vbeg[v + 1] : m;
-        float av = 0.f;
+    auto vox_key_of = [&](int j0) -> int32_t {
+        return K32 ? (int32_t)(((int64_t)b << P.vb_shift) + (int64_t)k_major(keys[KX(j0)]) - P.key_off) : vx_unbias(k_major(keys[KX(j0)]));
+    };
+    if constexpr (DESC) {
         if (in_lds) {
-            for (int j = j0; j < j1; ++j) av += ints[j];
-        } else {
-            for (int j = j0; j < j1; ++j) av += A.apri_int[(size_t)base + k_idx(keys[j])];
+            for (int j = threadIdx.x; j < m; j += THREADS) ints[j] = A.apri_int[(size_t)base + k_idx(keys[KX(j)])];
+            __syncthreads();
         }
-        const float fn = (float)(j1 - j0);
-        av = av / fn;
-        float cov = 0.f;
-        for (int j = j0; j < j1; ++j) {
-            const float in = in_lds ? ints[j] : A.apri_int[(size_t)base + k_idx(keys[j])];
-            const double d = (double)(in - av);
-            cov = (float)((double)cov + d * d);
+        if (PV) PROF_MARK(3, 3);
+        // per voxel: sequential fp32 mean, then population variance accumulated as float += double
+        for (int v = threadIdx.x; v < nv; v += THREADS) {
+            const int j0 = vbeg[v];
+            const int j1 = (v + 1 < nv) ? vbeg[v + 1] : m;
+            float av, cov;
+            if (in_lds)
+                vx_descriptor<1>(j1 - j0, [&](int j) { return ints[j0 + j]; }, av, cov);
+            else
+                vx_descriptor<1>(j1 - j0, [&](int j) { return A.apri_int[(size_t)base + k_idx(keys[j0 + j])]; }, av, cov);
+            A.tmp_vox_key[(size_t)base + off + v] = vox_key_of(j0);
+            A.tmp_vox_cov[(size_t)base + off + v] = cov;
+            A.tmp_vox_av[(size_t)base + off + v] = av;
         }
-        cov = cov / fn;
-        A.tmp_vox_key[(size_t)base + off + v] = K32 ? (int32_t)(((int64_t)b << P.vb_shift) + (int64_t)k_major(keys[KX(j0)]) - P.key_off)
-                                                      : vx_unbias(k_major(keys[KX(j0)]));
-        A.tmp_vox_cov[(size_t)base + off + v] = cov;
-        A.tmp_vox_av[(size_t)base + off + v] = av;
+        __syncthreads();
+        if (PV) PROF_MARK(3, 4);
+        // vbeg aliases tmp_vox_begin in the oversize path: every thread rewrites only its own entries
+        for (int v = threadIdx.x; v < nv; v += THREADS) A.tmp_vox_begin[(size_t)base + off + v] = off + vbeg[v];
+    } else {
+        if (PV) PROF_MARK(3, 3);
+        if (PV) PROF_MARK(3, 4);
+        // key and list start of every voxel; vbeg aliases tmp_vox_begin in the oversize path: a thread reads and rewrites only its own entries
+        for (int v = threadIdx.x; v < nv; v += THREADS) {
+            const int j0 = vbeg[v];
+            A.tmp_vox_key[(size_t)base + off + v] = vox_key_of(j0);
+            A.tmp_vox_begin[(size_t)base + off + v] = off + j0;
+        }
     }
-    __syncthreads();
-    if (PV) PROF_MARK(3, 4);
-    // vbeg aliases tmp_vox_begin in the oversize path: every thread rewrites only its own entries
-    for (int v = threadIdx.x; v < nv; v += THREADS) A.tmp_vox_begin[(size_t)base + off + v] = off + vbeg[v];
     if (threadIdx.x == 0) A.vb_nvox[s * kMaxBuckets + b] = nv;
     __syncthreads();  // LDS is reused by the next item
     if (PV) PROF_MARK(3, 5);
@@ -431,6 +481,8 @@ __global__ __launch_bounds__(1024) void k_vx_final_offsets(DevParams P, Arena A)
 }
 
 // one WAVE per (scan, bucket) -- a bucket holds a few dozen voxels -- four buckets per workgroup: a quarter of the workgroups to dispatch
+// DESC = false: keys and point-list starts only (the lean form wrote no tmp_vox_av / tmp_vox_cov)
+template <bool DESC>
 __global__ __launch_bounds__(256) void k_vx_final(DevParams P, Arena A) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), s = blockIdx.y;
     if (b >= P.n_buckets) return;
@@ -442,7 +494,29 @@ __global__ __launch_bounds__(256) void k_vx_final(DevParams P, Arena A) {
     for (int v = threadIdx.x & 63; v < nv; v += 64) {
         A.vox_key[(size_t)base + dst + v] = A.tmp_vox_key[(size_t)base + src + v];
         A.vox_pt_begin[(size_t)base + s + dst + v] = A.tmp_vox_begin[(size_t)base + src + v];
-        A.vox_av[(size_t)base + dst + v] = A.tmp_vox_av[(size_t)base + src + v];
-        A.vox_cov[(size_t)base + dst + v] = A.tmp_vox_cov[(size_t)base + src + v];
+        if constexpr (DESC) {
+            A.vox_av[(size_t)base + dst + v] = A.tmp_vox_av[(size_t)base + src + v];
+            A.vox_cov[(size_t)base + dst + v] = A.tmp_vox_cov[(size_t)base + src + v];
+        }
+    }
+}
+
+// vox_av / vox_cov of scans [s0, s0 + gridDim.y) from the finished lists of a lean voxel stage, on demand (the batch's first fetch, the
+// intensity merge).  A voxel's points stand in vox_pts in (key, apri index) order, the order the fused form sums in.  A thread per
+// voxel: a 64-beam scan has 15 k voxels of three points on average, and the few voxels of several hundred points (next to the
+// sensor) cost their thread two passes of eight gathers in flight -- short beside the scan's other voxels spread over the chip.
+__global__ __launch_bounds__(256) void k_vx_descriptors(Arena A, int s0) {
+    const int s = s0 + blockIdx.y;
+    const int base = A.scan_off[s];
+    const int nv = A.counts[s * 8 + 6];
+    const int32_t* vbeg = A.vox_pt_begin + (size_t)base + s;
+    const int32_t* vpts = A.vox_pts + (size_t)base;
+    const float* in = A.apri_int + (size_t)base;
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < nv; v += gridDim.x * 256) {
+        const int j0 = vbeg[v];
+        float av, cov;
+        vx_descriptor<8>(vbeg[v + 1] - j0, [&](int j) { return in[vpts[j0 + j]]; }, av, cov);
+        A.vox_av[(size_t)base + v] = av;
+        A.vox_cov[(size_t)base + v] = cov;
     }
 }

@@ -370,7 +370,10 @@ typedef void (*TimerHook)(void* user, const char* name, int begin);
 // 2 = neither (apri / counts already in the arena: voxel stage only), 4 = the voxel stage alone on the compact arrays a
 // do_patchwork = 1 call without voxels left (the intensity calibration runs between the two).
 void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_patchwork, int apply_filter,
-                    int do_voxels, TimerHook th, void* tu);
+                    int do_voxels, TimerHook th, void* tu, int lean_voxels = 0);
+// lean_voxels = 1: the voxel stage leaves vox_av / vox_cov unwritten; launch_vox_descriptors fills them for scans [s0, s0 + n_scans)
+// from vox_pt_begin / vox_pts / apri_int when somebody asks
+void launch_vox_descriptors(const Arena& A, int s0, int n_scans, hipStream_t st, TimerHook th, void* tu);
 void launch_apri_expand(const DevParams& P, const Arena& A, int s0, int n_scans, int max_pts, hipStream_t st);
 struct VgJob {                // SSC::getCloud label filter + pcl::VoxelGrid (ssc.cpp:1063-1076, 1103-1106)
     const uint32_t* labels;   // per input point, or nullptr (no filter, no intensity scaling)

@@ -453,7 +453,7 @@ constexpr int kVoxCapS = 1024, kVoxThreadsS = 64;
 constexpr int kVoxCapL = 8192, kVoxThreadsL = 512;
 
 void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_patchwork, int apply_filter,
-                    int do_voxels, TimerHook th, void* tu) {
+                    int do_voxels, TimerHook th, void* tu, int lean_voxels) {
     const int B = A.n_scans;
     if (B <= 0) return;
     if (do_patchwork == 1) {
@@ -575,45 +575,64 @@ void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_p
             hipLaunchKernelGGL(k_vx_final_offsets, dim3(B), dim3(1024), 0, st, P, A);
             return;
         }
-        auto bucket_tiers = [&](auto kt) {
+        auto bucket_tiers = [&](auto kt, auto desc) {
             using KT = decltype(kt);
             constexpr size_t KS = sizeof(KT);
-            constexpr int kMore = (KS == 4 && SCVOD_VOX_K32_LDS) ? 3 : 2;  // workgroups per CU of the 4096 tier (x2, x4 for the next two)
-            hipFuncSetAttribute((const void*)k_vx_bucket<kVoxCapL, kVoxThreadsL * kTSv, kClassL, 63, kLGEv, 0, KT>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vox_lds_bytes(kVoxCapL, KS));
-            hipFuncSetAttribute((const void*)k_vx_bucket<4096, 256 * kTSv, kClassM2, kClassL - 1, kLGEv, 0, KT>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vox_lds_bytes(4096, KS));
+            constexpr bool DESC = decltype(desc)::value;
+            // workgroups per CU of the 4096 tier (x2 for the 2048 tier): what the LDS of each form allows, both measured
+            constexpr int kMore = (KS == 4 && SCVOD_VOX_K32_LDS) ? (DESC ? 3 : SCVOD_VOX_LEAN_MORE) : 2;
+            hipFuncSetAttribute((const void*)k_vx_bucket<kVoxCapL, kVoxThreadsL * kTSv, kClassL, 63, kLGEv, 0, KT, DESC>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vox_lds_bytes(kVoxCapL, KS, DESC));
+            hipFuncSetAttribute((const void*)k_vx_bucket<4096, 256 * kTSv, kClassM2, kClassL - 1, kLGEv, 0, KT, DESC>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vox_lds_bytes(4096, KS, DESC));
             TH_BEGIN("vx_bucket_8192");
-            hipLaunchKernelGGL((k_vx_bucket<kVoxCapL, kVoxThreadsL * kTSv, kClassL, 63, kLGEv, 0, KT>), dim3(kPersistCUs), dim3(kVoxThreadsL * kTSv),
-                               vox_lds_bytes(kVoxCapL, KS), st, P, A);
+            hipLaunchKernelGGL((k_vx_bucket<kVoxCapL, kVoxThreadsL * kTSv, kClassL, 63, kLGEv, 0, KT, DESC>), dim3(kPersistCUs), dim3(kVoxThreadsL * kTSv),
+                               vox_lds_bytes(kVoxCapL, KS, DESC), st, P, A);
             TH_END("vx_bucket_8192");
             TH_BEGIN("vx_bucket_4096");
-            hipLaunchKernelGGL((k_vx_bucket<4096, 256 * kTSv, kClassM2, kClassL - 1, kLGEv, 0, KT>), dim3(kPersistCUs * kMore), dim3(256 * kTSv),
-                               vox_lds_bytes(4096, KS), st, P, A);
+            hipLaunchKernelGGL((k_vx_bucket<4096, 256 * kTSv, kClassM2, kClassL - 1, kLGEv, 0, KT, DESC>), dim3(kPersistCUs * kMore), dim3(256 * kTSv),
+                               vox_lds_bytes(4096, KS, DESC), st, P, A);
             TH_END("vx_bucket_4096");
             TH_BEGIN("vx_bucket_2048");
-            hipLaunchKernelGGL((k_vx_bucket<2048, 128 * kTSv, kClassM, kClassM2 - 1, kLGEv, 0, KT>), dim3(kPersistCUs * kMore * 2), dim3(128 * kTSv),
-                               vox_lds_bytes(2048, KS), st, P, A);
+            hipLaunchKernelGGL((k_vx_bucket<2048, 128 * kTSv, kClassM, kClassM2 - 1, kLGEv, 0, KT, DESC>), dim3(kPersistCUs * kMore * 2), dim3(128 * kTSv),
+                               vox_lds_bytes(2048, KS, DESC), st, P, A);
             TH_END("vx_bucket_2048");
             TH_BEGIN("vx_bucket_1024");
-            hipLaunchKernelGGL((k_vx_bucket<kVoxCapS, kVoxThreadsS * kTSv, kClassXS, kClassM - 1, kLGEv, 0, KT>), dim3(kPersistCUs * 8),
-                               dim3(kVoxThreadsS * kTSv), vox_lds_bytes(kVoxCapS, KS), st, P, A);  // (twelve per CU measured slower than eight)
+            hipLaunchKernelGGL((k_vx_bucket<kVoxCapS, kVoxThreadsS * kTSv, kClassXS, kClassM - 1, kLGEv, 0, KT, DESC>), dim3(kPersistCUs * (DESC ? 8 : SCVOD_VOX_LEAN_S)),
+                               dim3(kVoxThreadsS * kTSv), vox_lds_bytes(kVoxCapS, KS, DESC), st, P, A);  // (fused form: twelve per CU measured slower than eight; lean form: twelve faster, sixteen no better)
             TH_END("vx_bucket_1024");
             TH_BEGIN("vx_bucket_256");
-            hipLaunchKernelGGL((k_vx_bucket<256, 64, 0, kClassXS - 1, 3, 0, KT>), dim3(kPersistCUs * 32), dim3(64), vox_lds_bytes(256, KS), st, P, A);
+            hipLaunchKernelGGL((k_vx_bucket<256, 64, 0, kClassXS - 1, 3, 0, KT, DESC>), dim3(kPersistCUs * 32), dim3(64), vox_lds_bytes(256, KS, DESC), st, P, A);
             TH_END("vx_bucket_256");
         };
-        if (A.vx_k32)
-            bucket_tiers((uint32_t)0);
-        else
-            bucket_tiers((unsigned long long)0);
+        if (A.vx_k32) {
+            if (lean_voxels)
+                bucket_tiers((uint32_t)0, std::false_type{});
+            else
+                bucket_tiers((uint32_t)0, std::true_type{});
+        } else {
+            if (lean_voxels)
+                bucket_tiers((unsigned long long)0, std::false_type{});
+            else
+                bucket_tiers((unsigned long long)0, std::true_type{});
+        }
         TH_BEGIN("vx_final_offsets");
         hipLaunchKernelGGL(k_vx_final_offsets, dim3(B), dim3(1024), 0, st, P, A);
         TH_END("vx_final_offsets");
         TH_BEGIN("vx_final");
-        hipLaunchKernelGGL(k_vx_final, dim3((P.n_buckets + 3) / 4, B), dim3(256), 0, st, P, A);
+        if (lean_voxels)
+            hipLaunchKernelGGL(k_vx_final<false>, dim3((P.n_buckets + 3) / 4, B), dim3(256), 0, st, P, A);
+        else
+            hipLaunchKernelGGL(k_vx_final<true>, dim3((P.n_buckets + 3) / 4, B), dim3(256), 0, st, P, A);
         TH_END("vx_final");
     }
+}
+
+void launch_vox_descriptors(const Arena& A, int s0, int n_scans, hipStream_t st, TimerHook th, void* tu) {
+    if (n_scans <= 0 || A.max_scan_pts <= 0) return;
+    TH_BEGIN("vx_descriptors");
+    hipLaunchKernelGGL(k_vx_descriptors, dim3((A.max_scan_pts + 4095) / 4096, n_scans), dim3(256), 0, st, A, s0);  // (voxels <= points; grid-stride)
+    TH_END("vx_descriptors");
 }
 
 void launch_apri_expand(const DevParams& P, const Arena& A, int s0, int n_scans, int max_pts, hipStream_t st) {

@@ -233,6 +233,7 @@ def load_lib():
         "scvod_set_max_name_literal": (C.c_int, [vp, i32]),
         "scvod_set_intensity_merge": (C.c_int, [vp, i32, i32, f32, f32]),
         "scvod_batch_cluster_merge_stats": (C.c_int, [vp, vp]),
+        "scvod_set_voxel_descriptors": (C.c_int, [vp, i32]),
         "scvod_set_region_growing": (C.c_int, [vp, i32, i32, i32, C.c_double, f32, C.c_double]),
         "scvod_batch_fetch_cluster_classes": (C.c_int, [vp, i32, i32, i32, i32, vp, i32]),
         "scvod_batch_fetch_region_growing": (C.c_int, [vp, i32, vp, vp, i32]),
@@ -340,7 +341,7 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_bin_scan", "scvod_voxelize", "scvod_pose_delta", "scvod_track_probe", "scvod_batch_process",
                     "scvod_batch_counts", "scvod_batch_fetch", "scvod_batch_cluster", "scvod_batch_fetch_clusters", "scvod_cluster",
                     "scvod_batch_cluster_types", "scvod_batch_fetch_cluster_types",
-                    "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_set_region_growing", "scvod_batch_fetch_cluster_classes", "scvod_batch_fetch_region_growing", "scvod_batch_region_growing_stats", "scvod_set_intensity_calibration", "scvod_batch_fetch_intensity_calibration", "scvod_batch_intensity_calibration_stats", "scvod_batch_intensity_calibration_candidates", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
+                    "scvod_batch_track", "scvod_batch_fetch_track", "scvod_set_track_mode", "scvod_set_cluster_exact", "scvod_batch_cluster_stats", "scvod_batch_cluster_rule_stats", "scvod_batch_cluster_help_stats", "scvod_set_max_name_literal", "scvod_set_intensity_merge", "scvod_batch_cluster_merge_stats", "scvod_set_voxel_descriptors", "scvod_set_region_growing", "scvod_batch_fetch_cluster_classes", "scvod_batch_fetch_region_growing", "scvod_batch_region_growing_stats", "scvod_set_intensity_calibration", "scvod_batch_fetch_intensity_calibration", "scvod_batch_intensity_calibration_stats", "scvod_batch_intensity_calibration_candidates", "scvod_batch_cluster_last_name", "scvod_set_chain_capacity", "scvod_chain_workspace_bytes", "scvod_get_params", "scvod_set_track_owned", "scvod_set_track_halo", "scvod_batch_track_chains", "scvod_chain_state_bytes", "scvod_chain_export_state", "scvod_batch_track_resume", "scvod_batch_track_compare", "scvod_batch_track_compare_device", "scvod_batch_map_accumulate_range", "scvod_batch_track_stats", "scvod_batch_export_table", "scvod_batch_track_tables", "scvod_sequence_ingest",
                     "scvod_map_create", "scvod_map_destroy", "scvod_map_last_error", "scvod_map_capacity", "scvod_map_clear",
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
                     "scvod_map_create_kind", "scvod_map_kind", "scvod_map_scratch_bytes", "scvod_map_accumulate_labelled",
@@ -829,6 +830,12 @@ class Ctx:
         """SSC::refineClusterByIntensity (ssc.cpp:571-635) after the clustering; iterations = 0 turns it off (the default).  The
         defaults are the values of both shipped YAML files"""
         self._chk(self.lib.scvod_set_intensity_merge(self.h, int(iterations), int(search_c), float(diff), float(cov)))
+
+    def set_voxel_descriptors(self, mode=0):
+        """When a batch's vox_av / vox_cov are computed: 0 (the default) at their first request -- a batch_fetch, or the clustering of
+        a ctx with the intensity merge on -- by a kernel of their own, 1 inside the voxel stage of every batch.  Same bits either way;
+        takes effect with the next batch.  The per-scan calls (process_scan, bin_scan, voxelize) always compute them at once"""
+        self._chk(self.lib.scvod_set_voxel_descriptors(self.h, int(mode)))
 
     def batch_cluster_merge_stats(self):
         out = np.zeros(4, np.int32)

@@ -252,8 +252,19 @@ int scvod_batch_process(scvod_ctx* ctx, const void* d_xyzi, const int32_t* h_sca
  * scvod_batch_fetch_track refuse a scan index >= that n_scans with SCVOD_ERR_INVALID -- the rows a larger, earlier batch left in the arena are never readable as live data. */
 int scvod_batch_counts(scvod_ctx* ctx, int32_t* h_out);
 
-/* Download the full result of scan `s` of the last batch. */
+/* Download the full result of scan `s` of the last batch.  vox_av / vox_cov: a batch's voxel stage leaves them out (nothing on the
+ * device chain reads them unless the intensity merge is on); the first fetch of a batch computes them for all its scans with one
+ * kernel on the batch's stream, later fetches find them there.  Same bits as the per-scan calls return
+ * (scvod_set_voxel_descriptors chooses when they are computed, never what). */
 int scvod_batch_fetch(scvod_ctx* ctx, int32_t s, scvod_scan_result* out);
+
+/* When the per-voxel intensity descriptors (vox_av / vox_cov) of a batch are computed.  mode 0 (the default): on demand -- at the
+ * first scvod_batch_fetch of the batch, or before the intensity merge of a scvod_batch_cluster when scvod_set_intensity_merge was
+ * turned on after the batch was processed; a ctx whose intensity merge is already on when the batch is processed computes them in
+ * the voxel stage, since its clustering reads every one of them.  mode 1: eager, in the voxel stage of every batch.  The values are
+ * bit-identical in both modes.  Takes effect with the next batch.  scvod_process_scan, scvod_bin_scan and scvod_voxelize return the
+ * descriptors to the host at once and always compute them in the voxel stage.  SCVOD_ERR_INVALID for any other mode. */
+int scvod_set_voxel_descriptors(scvod_ctx* ctx, int32_t mode);
 
 /* Scan-vs-next-scan differencing of the whole batch on the device: SSC::tracking (src/ssc.cpp:1250-1426) for every scan
  * against its successor, the way SSC::segDF drives it (src/ssc.cpp:1449-1451).  Needs scvod_batch_cluster and
