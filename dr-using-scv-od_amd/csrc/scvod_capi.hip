@@ -214,6 +214,10 @@ struct scvod_ctx {
     Scratch in;  // stream / ran: the last call (scvod_score_instances_stats waits for it)
     unsigned long long* in_counters = nullptr;
     int in_variant = 0;
+    // the truth label of the table's objects (scvod_batch_object_truth, scvod_objtruth.hip): a grow-only block (the spill list, the
+    // fallback's regions) and 8 counter words of their own, allocated by the first call; not part of the arena or the table's scratch
+    Scratch ot;  // stream / ran: the last call (scvod_batch_object_truth_stats waits for it)
+    unsigned long long* ot_counters = nullptr;
     // scan stacking (scvod_batch_stack_scans, scvod_stack.hip): the segment and tile tables, one grow-only block of their own allocated
     // by the first call; not part of the arena
     Scratch stk;
@@ -1504,6 +1508,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->cs_counters) hipFree(c->cs_counters);
     if (c->in.buf) hipFree(c->in.buf);
     if (c->in_counters) hipFree(c->in_counters);
+    if (c->ot.buf) hipFree(c->ot.buf);
+    if (c->ot_counters) hipFree(c->ot_counters);
     if (c->stk.buf) hipFree(c->stk.buf);
     if (c->sp.buf) hipFree(c->sp.buf);
     if (c->sp_stats) hipFree(c->sp_stats);
@@ -3482,6 +3488,104 @@ int scvod_set_score_instances_variant(scvod_ctx* c, int32_t variant) {
     if (!c) return SCVOD_ERR_INVALID;
     if (variant != 0 && variant != 1) return fail(c, SCVOD_ERR_INVALID, "variant %d (0 or 1)", variant);
     c->in_variant = variant;
+    return SCVOD_OK;
+}
+
+// ---- the truth label every object of the table covers (scvod_objtruth.hip) ----
+int scvod_batch_object_truth(scvod_ctx* c, const uint32_t* d_gt_label, const scvod_eval_params* params, void* d_truth, int64_t cap_truth,
+                             void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!d_gt_label || !d_truth || cap_truth < 0) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (((uintptr_t)d_gt_label & 3) || ((uintptr_t)d_truth & 3)) return fail(c, SCVOD_ERR_INVALID, "d_gt_label and d_truth must be 4-byte aligned");
+    scvod_eval_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_eval_params_default(&p);
+    if (p.n_dynamic_classes < 0 || p.n_dynamic_classes > 16) return fail(c, SCVOD_ERR_INVALID, "%d dynamic classes (0..16)", p.n_dynamic_classes);
+    if (!c->obj_lists_serial) return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_truth needs a scvod_batch_objects that asked for records or members");
+    if (int rc = export_check(c, c->obj_lists_track, "scvod_batch_object_truth")) return rc;
+    if (c->obj_lists_serial != c->cluster_serial)
+        return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_truth: the last object table belongs to an earlier clustering: call scvod_batch_objects again");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    if (int rc = counter_block(c, &c->ot_counters, 8)) return rc;
+    if (int rc = scratch_reserve(c, c->ot, truth_work_bytes(c->A.total_pts, c->A.max_scan_pts))) return rc;
+    const size_t N = (size_t)(c->cap_pts > 0 ? c->cap_pts : 1);
+    TruthJob J{};
+    J.tab_stats = c->obj_stats;  // what the table left in the scratch; none of its caller's buffers
+    J.key_out = c->obj_keys + N;
+    J.begin = c->obj_words + 2 * N;
+    J.gt = d_gt_label;
+    J.K.n = p.n_dynamic_classes;
+    for (int k = 0; k < J.K.n; ++k) J.K.c[k] = p.dynamic_classes[k];
+    J.out = (scvod_object_truth*)d_truth;
+    J.cap = (long long)cap_truth;
+    J.counters = c->ot_counters;
+    launch_object_truth(c->A, J, c->ot.buf, st);
+    HIPCHK(c, hipGetLastError());
+    c->ot.stream = st;
+    c->ot.ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_object_truth_stats(scvod_ctx* c, int64_t* h_out8) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->ot.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_batch_object_truth on this ctx yet");
+    if (int rc = read_counters(c, c->ot_counters, 8, c->ot.stream, h_out8)) return rc;
+    if (h_out8[2]) return fail(c, SCVOD_ERR_CAPACITY, "the table holds %lld objects, the truth buffer %lld", (long long)h_out8[1], (long long)h_out8[0]);
+    return SCVOD_OK;
+}
+
+int64_t scvod_batch_object_truth_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->ot.cap + (c->ot_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+}
+
+void scvod_object_truth_params_default(scvod_object_truth_params* p) {
+    if (!p) return;
+    p->moving_from = 0.5;
+    p->pure_from = 0.5;
+    p->min_points = 1;
+}
+
+int scvod_object_truth_finish(const scvod_object* objects, const scvod_object_truth* truth, int64_t n, const scvod_object_truth_params* params,
+                              scvod_object_truth_result* out) {
+    if (n < 0 || (n > 0 && (!objects || !truth)) || !out) return SCVOD_ERR_INVALID;
+    scvod_object_truth_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_object_truth_params_default(&p);
+    if (!std::isfinite(p.moving_from) || !std::isfinite(p.pure_from)) return SCVOD_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    for (int64_t i = 0; i < n; ++i) {
+        const scvod_object& o = objects[i];
+        const scvod_object_truth& t = truth[i];
+        if ((int64_t)t.n_points < p.min_points) {
+            ++out->skipped;
+            continue;
+        }
+        if ((double)t.n_label < p.pure_from * (double)t.n_points) ++out->mixed_objects;
+        if ((double)t.n_moving >= p.moving_from * (double)t.n_points) {
+            ++out->moving_objects;
+            if (o.dynamic == 1)
+                ++out->moving_dynamic;
+            else if (o.cls != 2)
+                ++out->moving_not_car;
+            else if (o.state == 0)
+                ++out->moving_car_static;
+            else
+                ++out->moving_car_untracked;
+        } else {
+            ++out->static_objects;
+            if (o.dynamic == 1) ++out->static_dynamic;
+        }
+    }
+    const double nan = std::numeric_limits<double>::quiet_NaN();  // scvod_eval_finish's rule for a zero denominator
+    const int64_t alarms = out->moving_dynamic + out->static_dynamic;
+    out->precision = alarms ? 100.0 * (double)out->moving_dynamic / (double)alarms : nan;
+    out->recall = out->moving_objects ? 100.0 * (double)out->moving_dynamic / (double)out->moving_objects : nan;
     return SCVOD_OK;
 }
 

@@ -461,6 +461,29 @@ size_t in_work_bytes(int32_t cap);
 int launch_instance_score(const uint32_t* key, const uint8_t* point_result, int32_t n, scvod_instance* out, int32_t cap, int64_t* d_n, void* work,
                           unsigned long long* counters, int variant, hipStream_t st);
 
+// the truth label every object of the table covers (scvod_batch_object_truth; scvod_objtruth.hip): reads key_out, begin and stats[1] of
+// the ObjectJob that built the table, as ShapeJob does.  work: truth_work_bytes bytes (the spill list, then kOtGroups regions of
+// 2 * max_scan_pts slots); counters: the 8 words of scvod_batch_object_truth_stats, cleared by every launch
+constexpr int kOtGroups = 32;  // workgroups of the fallback launch, each with a region of its own
+enum { kOtWritten = 0, kOtObjects, kOtOverflow, kOtFallback, kOtMovingPoints, kOtMovingMembers };
+struct TruthJob {
+    const uint64_t* key_out;     // the table's sorted member list
+    const int32_t* begin;        // the table's run starts
+    const long long* tab_stats;  // the table's stats ([1]: its objects)
+    const uint32_t* gt;          // [total points] caller's labels, one per input point
+    EvClasses K;                 // the moving classes
+    scvod_object_truth* out;     // [cap] caller's
+    long long cap;
+    unsigned long long* counters;
+    // filled by launch_object_truth
+    int32_t* list;               // objects for the fallback, in arbitrary order
+    long long list_cap;
+    unsigned long long* regions;
+    long long region_slots;
+};
+size_t truth_work_bytes(long long total_pts, int max_scan_pts);
+void launch_object_truth(const Arena& A, TruthJob J, void* work, hipStream_t st);
+
 // a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the shared one (grid_buckets, grid_work_ints)
 // over the base cloud with the caller's cell edge; work: sp_work_bytes bytes; stats: the 8 words of scvod_map_split_stats, written by
 // every launch.  The optional outputs of SpJob are nullptr when not asked for; mark == nullptr: a byte array inside `work`

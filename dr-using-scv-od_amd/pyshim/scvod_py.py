@@ -124,6 +124,26 @@ class InstanceResult(C.Structure):
 INSTANCE_DTYPE = np.dtype([("label", "<u4"), ("first_point", "<i4"), ("n_points", "<i8"), ("n_inlier", "<i8"), ("n_preserved", "<i8")])
 INSTANCE_STATS = ("written", "distinct", "overflow", "spilled_tiles")
 
+# struct scvod_object_truth: the truth label one object of the table covers (scvod_batch_object_truth), 32 bytes
+OBJECT_TRUTH_DTYPE = np.dtype([("label", "<u4"), ("n_label", "<i4"), ("n_class", "<i4"), ("n_moving", "<i4"), ("n_distinct", "<i4"),
+                               ("n_points", "<i4"), ("reserved", "<i4", 2)])
+OBJ_TRUTH_ONCHIP_LABELS = 128  # SCVOD_OBJ_TRUTH_ONCHIP_LABELS
+OBJECT_TRUTH_STATS = ("written", "objects", "overflow", "fallback_objects", "moving_points", "moving_members")
+
+
+class ObjectTruthParams(C.Structure):
+    """struct scvod_object_truth_params (include/scvod.h)"""
+    _fields_ = [("moving_from", C.c_double), ("pure_from", C.c_double), ("min_points", C.c_int64)]
+
+
+OBJECT_TRUTH_COUNTS = ("moving_objects", "moving_dynamic", "moving_car_static", "moving_car_untracked", "moving_not_car", "static_objects",
+                       "static_dynamic", "mixed_objects", "skipped")
+
+
+class ObjectTruthResult(C.Structure):
+    """struct scvod_object_truth_result (include/scvod.h)"""
+    _fields_ = [(n, C.c_int64) for n in OBJECT_TRUTH_COUNTS] + [(n, C.c_double) for n in ("precision", "recall")]
+
 
 class SplitParams(C.Structure):
     """struct scvod_split_params (include/scvod.h)"""
@@ -315,6 +335,11 @@ def load_lib():
         "scvod_instance_params_default": (None, [C.POINTER(InstanceParams)]),
         "scvod_instance_finish": (C.c_int, [vp, i64, C.POINTER(InstanceParams), C.POINTER(InstanceResult)]),
         "scvod_instance_merge": (C.c_int, [vp, i64, vp, i64, vp, i64, C.POINTER(i64)]),
+        "scvod_batch_object_truth": (C.c_int, [vp, vp, C.POINTER(EvalParams), vp, i64, vp]),
+        "scvod_batch_object_truth_stats": (C.c_int, [vp, vp]),
+        "scvod_batch_object_truth_scratch_bytes": (i64, [vp]),
+        "scvod_object_truth_params_default": (None, [C.POINTER(ObjectTruthParams)]),
+        "scvod_object_truth_finish": (C.c_int, [vp, vp, i64, C.POINTER(ObjectTruthParams), C.POINTER(ObjectTruthResult)]),
         "scvod_split_params_default": (None, [C.POINTER(SplitParams)]),
         "scvod_map_split_device": (C.c_int, [vp, vp, vp, i32, vp, i32, C.POINTER(SplitParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "scvod_map_split_stats": (C.c_int, [vp, vp]),
@@ -358,6 +383,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_score_classes_scratch_bytes",
                     "scvod_score_instances_device", "scvod_score_instances_stats", "scvod_score_instances_scratch_bytes",
                     "scvod_set_score_instances_variant", "scvod_instance_params_default", "scvod_instance_finish", "scvod_instance_merge",
+                    "scvod_batch_object_truth", "scvod_batch_object_truth_stats", "scvod_batch_object_truth_scratch_bytes",
+                    "scvod_object_truth_params_default", "scvod_object_truth_finish",
                     "scvod_stack_offsets", "scvod_pose_from_matrix", "scvod_batch_stack_scans", "scvod_stack_scans",
                     "scvod_stack_scratch_bytes",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
@@ -456,6 +483,31 @@ def instance_finish(table, params=None):
     _status(load_lib().scvod_instance_finish(t.ctypes.data_as(C.c_void_p) if t.size else None, t.size,
                                              C.byref(params) if params is not None else None, C.byref(r)), "scvod_instance_finish")
     return {k: getattr(r, k) for k, _ in InstanceResult._fields_}
+
+
+def object_truth_params_default(moving_from=None, pure_from=None, min_points=None):
+    """scvod_object_truth_params with the defaults (both thresholds 0.5, min_points 1), overridden by keyword"""
+    p = ObjectTruthParams()
+    load_lib().scvod_object_truth_params_default(C.byref(p))
+    if moving_from is not None:
+        p.moving_from = float(moving_from)
+    if pure_from is not None:
+        p.pure_from = float(pure_from)
+    if min_points is not None:
+        p.min_points = int(min_points)
+    return p
+
+
+def object_truth_finish(objects, truth, params=None):
+    """the OBJECT_DTYPE records of a table and the OBJECT_TRUTH_DTYPE records of batch_object_truth on it -> the dict of
+    scvod_object_truth_result (object counts, precision and recall of the dynamic flag).  Host only"""
+    o = np.ascontiguousarray(objects, OBJECT_DTYPE).reshape(-1)
+    t = np.ascontiguousarray(truth, OBJECT_TRUTH_DTYPE).reshape(-1)
+    assert o.size == t.size
+    r = ObjectTruthResult()
+    _status(load_lib().scvod_object_truth_finish(o.ctypes.data_as(C.c_void_p) if o.size else None, t.ctypes.data_as(C.c_void_p) if t.size else None,
+                                                 o.size, C.byref(params) if params is not None else None, C.byref(r)), "scvod_object_truth_finish")
+    return {k: getattr(r, k) for k, _ in ObjectTruthResult._fields_}
 
 
 def instance_merge(a, b):
@@ -1029,6 +1081,33 @@ class Ctx:
         out = np.zeros(4, np.int64)
         self._chk(self.lib.scvod_batch_object_shapes_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return dict(written=int(out[0]), objects=int(out[1]), not_finite=int(out[2]), overflow=bool(out[3]))
+
+    # ---- the truth label of the table's objects (include/scvod.h: scvod_batch_object_truth) ----
+    def batch_object_truth(self, d_gt_label, params=None, cap=None, stream=None):
+        """one OBJECT_TRUTH_DTYPE record per object of the last batch_objects that asked for more than the counts, in table order:
+        d_gt_label holds one 4-byte label per input point of the batch (torch device tensor), params an EvalParams (only its class
+        list is read; None: the defaults).  Returns a torch uint8 device tensor [cap, 32] (cap None: the batch's points, which holds
+        every table); the rows behind the records written are not initialised.  Asynchronous on `stream`:
+        batch_object_truth_stats() tells how many records were written"""
+        import torch
+        assert d_gt_label.is_contiguous() and d_gt_label.element_size() == 4 and d_gt_label.numel() >= self._n_pts
+        cap = int(self._n_pts if cap is None else cap)
+        out = torch.empty((max(cap, 1), OBJECT_TRUTH_DTYPE.itemsize), dtype=torch.uint8, device=d_gt_label.device)
+        self._chk(self.lib.scvod_batch_object_truth(self.h, C.c_void_p(d_gt_label.data_ptr()), C.byref(params) if params is not None else None,
+                                                    C.c_void_p(out.data_ptr()), cap, C.c_void_p(stream or 0)))
+        return out[:cap]
+
+    def batch_object_truth_stats(self):
+        """{written, objects, overflow, fallback_objects, moving_points, moving_members} of the last batch_object_truth; synchronises
+        its stream; raises after an overflow"""
+        out = np.zeros(8, np.int64)
+        self._chk(self.lib.scvod_batch_object_truth_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(written=int(out[0]), objects=int(out[1]), overflow=bool(out[2]), fallback_objects=int(out[3]), moving_points=int(out[4]),
+                    moving_members=int(out[5]))
+
+    def batch_object_truth_scratch_bytes(self):
+        """device scratch of the stage on this ctx (not part of arena_bytes or batch_objects_scratch_bytes)"""
+        return int(self.lib.scvod_batch_object_truth_scratch_bytes(self.h))
 
     def set_timing(self, on):
         self._chk(self.lib.scvod_set_timing(self.h, int(bool(on))))

@@ -1110,6 +1110,75 @@ int scvod_instance_finish(const scvod_instance* table, int64_t n, const scvod_in
 int scvod_instance_merge(const scvod_instance* a, int64_t na, const scvod_instance* b, int64_t nb, scvod_instance* out, int64_t cap,
                          int64_t* n_out);
 
+/* ---- the truth label every object of the table covers, on the device (opt-in: nothing runs or is allocated unless it is called) ----
+ * Reference analogue: none.  tool/feature.py (per-class feature boxplots) and tool/plotIoU.py (object counts) hold hard-coded numbers;
+ * no program of the reference joins Frame::cluster_set with labelled truth.  The device part is a group-by with integer counts and is
+ * exact; the object rule on the host (scvod_object_truth_finish) is THIS PROJECT'S CONVENTION.  A member point's
+ * label is d_gt_label[scan_offsets[s] + apri_src[slot]] -- the join d_member_src documents; label & 0xFFFF is its class, label >> 16
+ * its instance, and every 32-bit value is a legal label, 0 and 0xFFFFFFFF included.  One record per object, in table order; `label` is
+ * the key of scvod_instance, so a record joins with the instance table on the host.  The records are the same bytes on every run and
+ * depend on the multiset of an object's labels alone. */
+#define SCVOD_OBJ_TRUTH_ONCHIP_LABELS 128 /* an object with at most this many distinct labels never takes the fallback path */
+typedef struct scvod_object_truth { /* 32 bytes */
+    uint32_t label;      /* the 32-bit truth label most members carry; equal counts: the SMALLEST label value                */
+    int32_t n_label;     /* members carrying it                                                                              */
+    int32_t n_class;     /* members whose (l & 0xFFFF) == (label & 0xFFFF)                                                   */
+    int32_t n_moving;    /* members whose (l & 0xFFFF) is in params->dynamic_classes                                         */
+    int32_t n_distinct;  /* distinct 32-bit labels among the members                                                         */
+    int32_t n_points;    /* members (== scvod_object::n_points)                                                              */
+    int32_t reserved[2]; /* 0                                                                                                */
+} scvod_object_truth;
+/* One scvod_object_truth per object of the LAST scvod_batch_objects call of this batch that asked for records, members or the
+ * per-point objects, into d_truth [cap_truth]: the call reads the sorted member list that call left in the table's scratch, exactly as
+ * scvod_batch_object_shapes does, under the same state rules (SCVOD_ERR_STATE without such a call -- a count-only call is none -- or
+ * after another clustering; SCVOD_ERR_STATE without clustering and types of the batch; SCVOD_ERR_INVALID when the table read a tracking
+ * result that is stale now; a SCVOD_OBJ_NO_TRACK table is fine).  d_gt_label: the array scvod_batch_evaluate takes, one uint32 per
+ * INPUT point of the last batch.  params: only n_dynamic_classes / dynamic_classes are read (NULL: scvod_eval_params_default).
+ * Stream-ordered (stream NULL = the stream of the ctx's last batch call; the table call must be ordered before it), never synchronises
+ * with the host; each call overwrites the stats of the one before, and the calls of one ctx must be ordered among themselves (they
+ * share their scratch).  Argument errors (NULL ctx, d_gt_label or d_truth NULL or not 4-byte aligned, cap_truth < 0, a class count
+ * outside 0..16) are SCVOD_ERR_INVALID before any device is looked for.  Nothing is written at or behind cap_truth; the overflow is
+ * latched until the next call.  An object with more than SCVOD_OBJ_TRUTH_ONCHIP_LABELS distinct labels is counted again in global
+ * memory by a second launch on the same stream (32 workgroups, none of which waits for another); its record is the same.  Scratch
+ * (4 bytes per 129 batch points for the list of such objects, 32 regions of 16 bytes per point of the batch's largest scan, 8 counter
+ * words) is an allocation of its own, grow-only, freed by scvod_destroy and NOT part of scvod_arena_bytes or
+ * scvod_batch_objects_scratch_bytes; a call that needs more than any before waits for the one in flight before it grows. */
+int scvod_batch_object_truth(scvod_ctx* ctx, const uint32_t* d_gt_label, const scvod_eval_params* params, void* d_truth, int64_t cap_truth,
+                             void* stream);
+/* h_out8 = {records written, objects of the table, 1 when the table outgrew cap_truth, objects that took the fallback path, input
+ * points of the batch whose class is in the list, the sum of n_moving over ALL objects of the table (those at or behind cap_truth
+ * too), 0, 0} of the last scvod_batch_object_truth: word 4 minus word 5 is the number of moving points that sit in no object at all.
+ * Synchronises that call's stream.  SCVOD_ERR_CAPACITY after an overflow (h_out8 is filled), SCVOD_ERR_STATE before the first call. */
+int scvod_batch_object_truth_stats(scvod_ctx* ctx, int64_t* h_out8);
+/* bytes of device scratch the stage holds on this ctx (0 before the first call) */
+int64_t scvod_batch_object_truth_scratch_bytes(scvod_ctx* ctx);
+typedef struct scvod_object_truth_params {
+    double moving_from; /* an object is truth-moving iff n_moving >= moving_from * n_points; default 0.5 */
+    double pure_from;   /* an object is mixed iff n_label < pure_from * n_points; default 0.5            */
+    int64_t min_points; /* smaller objects are skipped; default 1                                        */
+} scvod_object_truth_params;
+/* 0.5, 0.5, 1 */
+void scvod_object_truth_params_default(scvod_object_truth_params* p);
+typedef struct scvod_object_truth_result {
+    int64_t moving_objects;       /* truth-moving objects: the sum of the next four                                           */
+    int64_t moving_dynamic;       /* ... with dynamic == 1: found                                                             */
+    int64_t moving_car_static;    /* ... not dynamic, cls == 2, state == 0: walked by the tracking and judged static          */
+    int64_t moving_car_untracked; /* ... not dynamic, cls == 2, any other state (-1 in a table): typed car, never judged      */
+    int64_t moving_not_car;       /* ... not dynamic, cls != 2: typed tree or building, so the tracking never walked it       */
+    int64_t static_objects;       /* the other objects                                                                        */
+    int64_t static_dynamic;       /* ... with dynamic == 1: false alarms                                                      */
+    int64_t mixed_objects;        /* objects of either kind whose winning label covers less than pure_from of their members   */
+    int64_t skipped;              /* objects below min_points (counted nowhere else)                                          */
+    double precision;             /* 100.0 * moving_dynamic / (moving_dynamic + static_dynamic); NaN for a zero denominator   */
+    double recall;                /* 100.0 * moving_dynamic / moving_objects; NaN for a zero denominator                      */
+} scvod_object_truth_result;
+/* Host only, no device.  objects [n] and truth [n]: the records of one table and of the truth call on it, index by index.  The
+ * products are taken in double: (double)n_moving >= moving_from * (double)n_points, (double)n_label < pure_from * (double)n_points,
+ * with n_points of the truth record.  params NULL = the defaults.  SCVOD_ERR_INVALID: a NULL array with n > 0, n < 0, out NULL, a
+ * threshold that is not finite. */
+int scvod_object_truth_finish(const scvod_object* objects, const scvod_object_truth* truth, int64_t n, const scvod_object_truth_params* params,
+                              scvod_object_truth_result* out);
+
 /* ---- scan stacking: neighbouring scans moved into the middle scan's frame, on the device (opt-in: nothing runs or is allocated
  * unless it is called) -------------------------------------------------------------------------------------------------------------
  * Reference analogue: src/makeScan.cpp:153-244, the stacker in front of the path for sparse, non-repetitive sensors.  Output scan
