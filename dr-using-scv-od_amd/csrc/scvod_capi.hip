@@ -758,7 +758,7 @@ int merge_check(scvod_ctx* c) {
         c->im_overflow = st[4];
     }
     if (c->im_overflow > 0)
-        return fail(c, SCVOD_ERR_CAPACITY, "intensity merge: the neighbour pairs of %d scans outgrew their scratch (%d per point)", c->im_overflow, kImPairsPerPt);
+        return fail(c, SCVOD_ERR_CAPACITY, "intensity merge: the neighbour pairs of %d scans outgrew their scratch (%d per point + %d per scan)", c->im_overflow, kImPairsPerPt, kImPairsPerScan);
     return SCVOD_OK;
 }
 

@@ -189,7 +189,8 @@ __global__ __launch_bounds__(kImThreads) void k_im_merge(DevParams P, Arena A, M
     int fusions = 0, absorbed = 0;  // (wave 0)
     for (int it = 0; it < M.iterations && np > 0; ++it) {
         for (int w = tid; w < nw; w += kImThreads) inv[w] = 0u;
-        // the clusters that have a pair, in descending order of their key (ties: none -- voxel sets are disjoint)
+        // the clusters that have a pair, in descending order of their key (equal keys -- clusters that share an aliased voxel next to
+        // the -1 bins -- in ascending name: the low word is the index of the cluster's first pair, and pairs are sorted by name)
         int nc = 0;
         for (int j0 = 0; j0 < np; j0 += kImThreads) {
             const int j = j0 + tid;

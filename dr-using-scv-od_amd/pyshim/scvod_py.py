@@ -685,6 +685,7 @@ class Ctx:
         a = np.ascontiguousarray(apri)
         r = ScanResult()
         self._chk(self.lib.scvod_voxelize(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], C.byref(r)))
+        self._n_scans, self._n_pts = 1, int(a.shape[0])  # (a batch of one scan: the batch_* calls may follow)
         return _unpack(r)
 
     def pose_delta(self, pose_pre, pose_next):

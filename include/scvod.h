@@ -466,8 +466,9 @@ int scvod_cluster(scvod_ctx* ctx, const scvod_apri* h_apri, int32_t n, int32_t* 
  * search_c must lie in 1..3: the neighbour walk looks up (2 search_c + 1)^2 grid rows per voxel, and the packed index triples
  * (clamped at -2 below the grid) reproduce findVoxelNeighbors up to that radius for every triple the range / FOV filter keeps.
  * The grid's range x azimuth row table and a bit per point of the largest scan share the LDS of one workgroup (160 KB): larger
- * grids are refused by scvod_batch_cluster.  A scan whose neighbour pairs outgrow their scratch (4 per point) keeps its partition and
- * every reader of the clustering (fetches, scvod_cluster, tracking, merge stats) then fails with SCVOD_ERR_CAPACITY.
+ * grids are refused by scvod_batch_cluster.  A scan of n points whose neighbour pairs outgrow their scratch (4 n + 256 pairs before
+ * de-duplication: 4 per point, and a slack per scan that lets small sparse scans through) keeps its partition and every reader
+ * of the clustering (fetches, scvod_cluster, tracking, merge stats) then fails with SCVOD_ERR_CAPACITY.
  * SCVOD_ERR_INVALID for negative values or search_c outside 1..3.  Scratch of about 100 bytes per point of the ctx's capacity is allocated on the first merged
  * clustering (counted by scvod_arena_bytes). */
 int scvod_set_intensity_merge(scvod_ctx* ctx, int32_t iterations, int32_t search_c, float intensity_diff, float intensity_cov);

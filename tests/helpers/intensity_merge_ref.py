@@ -100,8 +100,14 @@ def literal(vox, running, grid, iterations, search_c, diff, cov_max):
     return np.array([owner[int(c)] for c in running], np.int64)
 
 
-def convention(vox, names, grid, iterations, search_c, diff, cov_max, stats=None):
-    """names: canonical cluster name (smallest apri index) per apri point.  Returns the fused canonical name per point."""
+def convention(vox, names, grid, iterations, search_c, diff, cov_max, stats=None, ties=None):
+    """names: canonical cluster name (smallest apri index) per apri point.  Returns the fused canonical name per point.
+    ties: how clusters with EQUAL smallest voxel keys are visited (they occur: a voxel next to the -1 bins holds points of several
+    clusters) -- None: as the stable sort finds them (first voxel, then point order), "asc" / "desc": by name.  The device takes
+    them in ascending name.  stats also receives fusions_per_iteration and key_ties: the number of clusters whose smallest key equals
+    another's, counted over ALL clusters.  The order can matter only between tied clusters that both have a neighbour of another
+    label and are visited, so key_ties > 0 says that a scan holds ties, not that one decided anything: the comparison of the three
+    orders (tests/test_intensity_merge_cases.py) is the check that carries the weight."""
     key, av, cov, idx3, slot, vlab, members, grid = _tables(vox, names, grid)
     key0 = {c: min(int(key[v]) for v in vs) for c, vs in members.items()}
     vox_of = {c: set(vs) for c, vs in members.items()}
@@ -110,10 +116,12 @@ def convention(vox, names, grid, iterations, search_c, diff, cov_max, stats=None
     nb = {}
     n_before = len(vox_of)
     n_fusions = 0
+    per_iteration = []
+    order = {None: lambda c: -key0[c], "asc": lambda c: (-key0[c], c), "desc": lambda c: (-key0[c], -c)}[ties]
     for it in range(iterations):
         invalid = set()
         fusions = []
-        for c in sorted(vox_of, key=lambda c: -key0[c]):
+        for c in sorted(vox_of, key=order):
             if c in invalid:
                 continue
             S_ = set()
@@ -136,8 +144,11 @@ def convention(vox, names, grid, iterations, search_c, diff, cov_max, stats=None
                     owner[o] = t
         label = np.array([owner[int(c)] for c in vlab], np.int64)   # a voxel's label: the cluster of its first point
         n_fusions += len(fusions)
+        per_iteration.append(len(fusions))
     if stats is not None:
-        stats.update(clusters_before=n_before, fusions=n_fusions, clusters_after=len(vox_of))
+        k0 = sorted(key0.values())
+        stats.update(clusters_before=n_before, fusions=n_fusions, clusters_after=len(vox_of), fusions_per_iteration=per_iteration,
+                     key_ties=sum(1 for i, k in enumerate(k0) if (i and k0[i - 1] == k) or (i + 1 < len(k0) and k0[i + 1] == k)))
     return np.array([owner[int(c)] for c in names], np.int64)
 
 
