@@ -16,117 +16,15 @@
 // {label, intensity}, 8 bits each, instead of the 16-bit intensity -- `instance_map` in the colour of the recognised class
 // (ssc.cpp:501-554).  The label is the representative point's OWN byte: the smallest (offset, label, intensity) wins, so the
 // leading 48 bits, hence the point's xyz, are the plain map's for the same kept set.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "scvod_dev.h"
+#include "scvod_maptable.h"
 
 using namespace scvod;
-
-struct MapRec {
-    unsigned long long key;  // ~0 = empty
-    unsigned long long val;  // packed {qx, qy, qz, qi}, 16 bits each, smallest wins (labelled kind: {qx, qy, qz} 16 bits each, label 8, qi 8)
-};
-static_assert(sizeof(MapRec) == 16, "map record");
-
-struct scvod_map {
-    int device = 0;
-    float leaf = 0.2f;
-    long long capacity = 0;  // power of two
-    MapRec* table = nullptr;
-    unsigned long long* counters = nullptr;  // [0] records exported, [1] insertions dropped (table full / out of range), [2..2+64) per-part counts / cursors
-    float* d_pose = nullptr;                 // [pose_cap][12]
-    long long pose_cap = 0;
-    std::vector<float> up_pose;
-    int kind = SCVOD_MAP_KIND_PLAIN;
-    // labelled kind only: scan offsets of the ctx-free accumulate (staged like the poses) and the class bytes of the batch form
-    int32_t* d_offs = nullptr;  // [offs_cap]
-    long long offs_cap = 0;
-    std::vector<int32_t> up_offs;
-    uint8_t* d_cls = nullptr;  // [cls_cap] one byte per input point of the largest batch seen (grow-only)
-    long long cls_cap = 0;
-    std::string err;
-};
 
 namespace scvod {
 namespace {
 
-constexpr unsigned long long kEmpty = ~0ull;
-constexpr int kMapMaxProbes = 512;  // linear probing: longer runs only appear beyond ~95 % load
-constexpr int kCellBits = 21, kCellBias = 1 << 20;
-// k_map_accumulate: points per thread and round / points per workgroup.  Measured on the 2761-scan K64 job (round 3): one point per
-// thread beats two / four / eight in flight (4.82 / 4.96 / 5.43 / 6.19 ms at 2048 points per workgroup: the extra registers cost
-// occupancy and the later atomics act on staler peeks), and 8192 points per workgroup beat 512 .. 32768 (5.03 .. 4.45 .. 4.58 ms)
-constexpr int kMapU = 1, kMapPts = 8192;
-
-int mfail(scvod_map* m, int code, const char* fmt, ...) {
-    if (m) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof(buf), fmt, ap);
-        va_end(ap);
-        m->err = buf;
-    }
-    return code;
-}
-#define MHIP(m, call)                                                                                    \
-    do {                                                                                                 \
-        hipError_t e__ = (call);                                                                         \
-        if (e__ != hipSuccess) return mfail(m, SCVOD_ERR_HIP, "%s: %s", #call, hipGetErrorString(e__)); \
-    } while (0)
-
-__device__ __forceinline__ unsigned long long map_mix(unsigned long long k) {  // murmur3 finaliser
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-
-// home slot of a cell: a hash of the whole cell.  (Blocks of neighbouring cells laid side by side in the table were measured in rounds 3
-// and 5, from 2 x 2 x 1 to 4 x 4 x 4 cells: every one slower -- profiles/r05_experiments.md.)
-__device__ __forceinline__ unsigned long long map_home(unsigned long long key, unsigned long long mask) { return map_mix(key) & mask; }
-
-// cell + packed in-cell offset of a world point.  floor(p * inv_leaf) like pcl::VoxelGrid's cell index; the offset is
-// quantised to 16 bits of the cell edge, the intensity to 1/256 (clamped to [0, 255.996]).
-__device__ __forceinline__ bool map_encode(float x, float y, float z, float intensity, float inv_leaf, unsigned long long& key,
-                                           unsigned long long& val) {
-    const float fx = x * inv_leaf, fy = y * inv_leaf, fz = z * inv_leaf;
-    const float cx = floor_f(fx), cy = floor_f(fy), cz = floor_f(fz);
-    if (!(cx >= -(float)kCellBias && cx < (float)kCellBias && cy >= -(float)kCellBias && cy < (float)kCellBias &&
-          cz >= -(float)kCellBias && cz < (float)kCellBias))
-        return false;  // also NaN
-    const unsigned long long ux = (unsigned long long)((int)cx + kCellBias), uy = (unsigned long long)((int)cy + kCellBias),
-                             uz = (unsigned long long)((int)cz + kCellBias);
-    key = (ux << (2 * kCellBits)) | (uy << kCellBits) | uz;
-    auto q16 = [](float f) -> unsigned long long {
-        int q = (int)(f * 65536.0f);
-        return (unsigned long long)(q < 0 ? 0 : (q > 65535 ? 65535 : q));
-    };
-    float in = intensity * 256.0f;
-    in = in < 0.f ? 0.f : (in > 65535.f ? 65535.f : in);
-    val = (q16(fx - cx) << 48) | (q16(fy - cy) << 32) | (q16(fz - cz) << 16) | (unsigned long long)(int)in;
-    return true;
-}
-
-// One 16-byte load per probe (key and value together).  The load is an ordinary cached one: a key, once set, never changes
-// and a value only decreases, so a stale record can only show (a) an empty slot that is taken by now -- the CAS then returns
-// the owner -- or (b) a value above the current one -- the atomicMin then runs although it was not needed.  Both are harmless.
-__device__ __forceinline__ MapRec map_peek(const MapRec* table, unsigned long long h) {
-    const ulonglong2 r = *reinterpret_cast<const ulonglong2*>(&table[h]);
-    MapRec m;
-    m.key = r.x;
-    m.val = r.y;
-    return m;
-}
 // `first` = map_peek(table, h0) with h0 = map_mix(key) & mask (the caller issued it early, several probes in flight)
 __device__ __forceinline__ bool map_insert_from(MapRec* table, unsigned long long mask, unsigned long long key, unsigned long long val,
                                                 unsigned long long h, MapRec rec) {
@@ -256,13 +154,6 @@ __global__ __launch_bounds__(256) void k_map_mark_lists(Arena A) {
     }
 }
 
-// is `label` set in the 256-bit table k0..k3?  The four words are kernel arguments: they live in scalar registers
-__device__ __forceinline__ bool map_bit256(unsigned long long k0, unsigned long long k1, unsigned long long k2, unsigned long long k3,
-                                           unsigned int label) {
-    const unsigned long long lo = (label & 64u) ? k1 : k0, hi = (label & 64u) ? k3 : k2;
-    return (((label & 128u) ? hi : lo) >> (label & 63u)) & 1ull;
-}
-
 // the labelled kind's value: map_encode's three offsets, then the caller's byte, then (int)clamp(intensity, 0, 255)
 __device__ __forceinline__ unsigned long long map_val_labelled(unsigned long long plain_val, unsigned int label, float intensity) {
     float in = intensity;
@@ -388,8 +279,7 @@ __global__ __launch_bounds__(256) void k_map_export(const MapRec* __restrict__ t
                 const int cx = (int)(q.key >> (2 * kCellBits)) - kCellBias, cy = (int)((q.key >> kCellBits) & ((1u << kCellBits) - 1u)) - kCellBias,
                           cz = (int)(q.key & ((1u << kCellBits) - 1u)) - kCellBias;
                 const float qx = (float)((q.val >> 48) & 0xffffu), qy = (float)((q.val >> 32) & 0xffffu), qz = (float)((q.val >> 16) & 0xffffu);
-                out_xyzi[o] = make_float4(((float)cx + (qx + 0.5f) / 65536.0f) * leaf, ((float)cy + (qy + 0.5f) / 65536.0f) * leaf,
-                                          ((float)cz + (qz + 0.5f) / 65536.0f) * leaf,
+                out_xyzi[o] = make_float4(map_decode(cx, qx, leaf), map_decode(cy, qy, leaf), map_decode(cz, qz, leaf),
                                           LABELLED ? (float)(q.val & 0xffu) : (float)(q.val & 0xffffu) / 256.0f);
             }
             if (LABELLED && out_label) out_label[o] = (uint8_t)((q.val >> 8) & 0xffu);
@@ -515,13 +405,6 @@ __global__ __launch_bounds__(256) void k_map_scatter_parts_padded(const MapRec* 
 }  // namespace
 }  // namespace scvod
 
-// the one place the map code needs the batch context: its arena, parameters and validity flags
-struct scvod_ctx;
-extern "C" int scvod__ctx_types_valid(scvod_ctx* c);
-extern "C" int scvod__ctx_view(scvod_ctx* ctx, Arena* arena, int* device, int* track_valid, int* batch_valid, int* n_scans,
-                               int* max_scan_pts, int* batch_mode, int* num_min_pts);
-extern "C" void* scvod__ctx_stream(scvod_ctx* ctx, void* stream);
-
 extern "C" {
 
 int scvod_map_create(int device, int64_t capacity_cells, float leaf, scvod_map** out) {
@@ -562,6 +445,7 @@ void scvod_map_destroy(scvod_map* m) {
     if (m->d_pose) hipFree(m->d_pose);
     if (m->d_offs) hipFree(m->d_offs);
     if (m->d_cls) hipFree(m->d_cls);
+    if (m->q_counters) hipFree(m->q_counters);
     delete m;
 }
 
@@ -647,39 +531,6 @@ int scvod_batch_map_accumulate_range(scvod_ctx* ctx, scvod_map* m, const float* 
     return SCVOD_OK;
 }
 
-// the 256 keep / select bytes as the four words the kernels take; NULL = every label
-static void map_table256(const uint8_t* h256, unsigned long long k[4]) {
-    for (int w = 0; w < 4; ++w) {
-        k[w] = h256 ? 0ull : ~0ull;
-        if (h256)
-            for (int b = 0; b < 64; ++b)
-                if (h256[64 * w + b]) k[w] |= 1ull << b;
-    }
-}
-
-// the poses of a call as matrices on the device (h_poses NULL: the zero pose, n times).  The staging vector may still feed an earlier
-// asynchronous copy: values that differ from the previous call's wait for `st` first.
-static int map_stage_poses(scvod_map* m, const float* h_poses, int n, hipStream_t st) {
-    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    std::vector<float> T((size_t)12 * n);
-    for (int s = 0; s < n; ++s) scvod_pose_matrix(h_poses ? h_poses + 6 * s : zero, T.data() + 12 * s);
-    if (m->pose_cap < n) {
-        MHIP(m, hipStreamSynchronize(st));
-        if (m->d_pose) hipFree(m->d_pose);
-        m->d_pose = nullptr;
-        m->pose_cap = 0;
-        m->up_pose.clear();
-        MHIP(m, hipMalloc(&m->d_pose, sizeof(float) * 12 * (size_t)n));
-        m->pose_cap = n;
-    }
-    if (m->up_pose != T) {
-        MHIP(m, hipStreamSynchronize(st));
-        m->up_pose = T;
-        MHIP(m, hipMemcpyAsync(m->d_pose, m->up_pose.data(), sizeof(float) * T.size(), hipMemcpyHostToDevice, st));
-    }
-    return SCVOD_OK;
-}
-
 // scans [first, first + count) of a cloud whose offsets and poses are on the device already
 static int map_launch_labelled(scvod_map* m, const void* d_xyzi, const uint8_t* d_labels, const int32_t* d_offs, int first, int count, int max_pts,
                                const unsigned long long k[4], hipStream_t st) {
@@ -699,33 +550,15 @@ int scvod_map_accumulate_labelled(scvod_map* m, const void* d_xyzi, const uint8_
     if (!m || n_scans < 0 || (n_scans > 0 && !h_scan_offsets)) return mfail(m, SCVOD_ERR_INVALID, "bad arguments");
     if (m->kind != SCVOD_MAP_KIND_LABELLED) return mfail(m, SCVOD_ERR_INVALID, "scvod_map_accumulate_labelled needs a map of kind SCVOD_MAP_KIND_LABELLED");
     if (n_scans == 0) return SCVOD_OK;
-    if (h_scan_offsets[0] < 0) return mfail(m, SCVOD_ERR_INVALID, "scan offsets start below 0");
     int max_pts = 0;
-    for (int s = 0; s < n_scans; ++s) {
-        if (h_scan_offsets[s + 1] < h_scan_offsets[s]) return mfail(m, SCVOD_ERR_INVALID, "scan offsets decrease at scan %d", s);
-        if (h_scan_offsets[s + 1] - h_scan_offsets[s] > max_pts) max_pts = h_scan_offsets[s + 1] - h_scan_offsets[s];
-    }
+    if (int rc = map_check_offsets(m, h_scan_offsets, n_scans, &max_pts)) return rc;
     if (max_pts > 0 && (!d_xyzi || !d_labels)) return mfail(m, SCVOD_ERR_INVALID, "NULL points or labels of a cloud that is not empty");
     if ((uintptr_t)d_xyzi & 15u) return mfail(m, SCVOD_ERR_INVALID, "d_xyzi is not 16-byte aligned");
     if (max_pts == 0) return SCVOD_OK;
     MHIP(m, hipSetDevice(m->device));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = map_stage_poses(m, h_poses, n_scans, st)) return rc;
-    const std::vector<int32_t> offs(h_scan_offsets, h_scan_offsets + n_scans + 1);
-    if (m->offs_cap < n_scans + 1) {
-        MHIP(m, hipStreamSynchronize(st));
-        if (m->d_offs) hipFree(m->d_offs);
-        m->d_offs = nullptr;
-        m->offs_cap = 0;
-        m->up_offs.clear();
-        MHIP(m, hipMalloc(&m->d_offs, sizeof(int32_t) * ((size_t)n_scans + 1)));
-        m->offs_cap = (long long)n_scans + 1;
-    }
-    if (m->up_offs != offs) {  // (the same hazard as the poses' staging vector)
-        MHIP(m, hipStreamSynchronize(st));
-        m->up_offs = offs;
-        MHIP(m, hipMemcpyAsync(m->d_offs, m->up_offs.data(), sizeof(int32_t) * offs.size(), hipMemcpyHostToDevice, st));
-    }
+    if (int rc = map_stage_offsets(m, h_scan_offsets, n_scans, st)) return rc;
     unsigned long long k[4];
     map_table256(h_keep256, k);
     return map_launch_labelled(m, d_xyzi, d_labels, m->d_offs, 0, n_scans, max_pts, k, st);

@@ -295,6 +295,10 @@ def load_lib():
         "scvod_map_accumulate_labelled": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
         "scvod_batch_map_accumulate_classes": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
         "scvod_map_points_labelled": (C.c_int, [vp, vp, vp, vp, i64, vp, C.POINTER(i64), vp]),
+        "scvod_map_query": (C.c_int, [vp, vp, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
+        "scvod_batch_map_query": (C.c_int, [vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
+        "scvod_map_query_stats": (C.c_int, [vp, vp]),
+        "scvod_map_query_scratch_bytes": (i64, [vp]),
         "scvod_batch_point_labels": (C.c_int, [vp, vp, i64, i32, vp]),
         "scvod_batch_export_points": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
         "scvod_batch_export_stats": (C.c_int, [vp, vp]),
@@ -371,6 +375,7 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_pose_matrix", "scvod_batch_map_accumulate", "scvod_map_export", "scvod_map_export_parts", "scvod_map_export_parts_padded", "scvod_map_merge", "scvod_map_points",
                     "scvod_map_create_kind", "scvod_map_kind", "scvod_map_scratch_bytes", "scvod_map_accumulate_labelled",
                     "scvod_batch_map_accumulate_classes", "scvod_map_points_labelled",
+                    "scvod_map_query", "scvod_batch_map_query", "scvod_map_query_stats", "scvod_map_query_scratch_bytes",
                     "scvod_batch_point_labels", "scvod_batch_export_points", "scvod_batch_export_stats",
                     "scvod_batch_objects", "scvod_batch_objects_stats", "scvod_batch_objects_scratch_bytes",
                     "scvod_feature_params_default", "scvod_set_object_features", "scvod_batch_object_shapes", "scvod_batch_object_shapes_stats",
@@ -1429,6 +1434,8 @@ MAP_KIND_PLAIN, MAP_KIND_LABELLED = 0, 1  # SCVOD_MAP_KIND_*
 # scvod_batch_point_labels: one byte per input point (include/scvod.h, SCVOD_PT_*)
 PT_DROPPED, PT_GROUND, PT_REJECTED, PT_UNCLUSTERED, PT_STATIC_OTHER, PT_STATIC_CAR, PT_DYNAMIC = range(7)
 PT_STATIC_BUILDING = 7  # scvod_batch_point_classes only
+MAPQ_MISS, MAPQ_CELL, MAPQ_NEAR, MAPQ_OUT = 0, 1, 2, 3  # SCVOD_MAPQ_*: the result byte of StaticMap.query
+MAPQ_OUTPUTS = ("result", "cell_val", "nn_key", "nn_sqdist", "scan_counts")
 
 
 class StaticMap:
@@ -1500,6 +1507,49 @@ class StaticMap:
 
     def scratch_bytes(self):
         return int(self.lib.scvod_map_scratch_bytes(self.h))
+
+    def _query_outputs(self, n, n_scans, radius, want):
+        """the device tensors a query writes, by name (MAPQ_OUTPUTS), and the five pointers in the C order"""
+        import torch
+        want = tuple(w for w in MAPQ_OUTPUTS if float(radius) > 0.0 or not w.startswith("nn_")) if want is None else tuple(want)
+        assert all(w in MAPQ_OUTPUTS for w in want), want
+        dev = torch.device("cuda", self.device)
+        shape = {"result": ((n,), torch.uint8), "cell_val": ((n,), torch.int64), "nn_key": ((n,), torch.int64),
+                 "nn_sqdist": ((n,), torch.float32), "scan_counts": ((n_scans, 4), torch.int64)}
+        out = {w: torch.empty(shape[w][0], dtype=shape[w][1], device=dev) for w in want}
+        return out, [C.c_void_p(out[w].data_ptr()) if w in out else None for w in MAPQ_OUTPUTS]
+
+    def query(self, d_xyzi, scan_offsets, poses=None, radius=0.0, select=None, want=("result",), stream=None):
+        """scvod_map_query of the caller's cloud (torch float32 [n, 4] on the map's device): a dict of device tensors, one per name in
+        `want` (MAPQ_OUTPUTS; None: every output the radius allows) -- result uint8 [n], cell_val and nn_key int64 [n] (the bits of the
+        uint64), nn_sqdist float32 [n], scan_counts int64 [n_scans, 4] = {CELL, NEAR, MISS, OUT}.  Rows are at the input index, so the
+        offsets should start at 0.  select: see _table256 (labelled maps only).  Stream-ordered, no synchronisation."""
+        off = np.ascontiguousarray(scan_offsets, np.int32)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == len(off) - 1
+        out, ptr = self._query_outputs(int(off[-1]) if len(off) else 0, len(off) - 1, radius, want)
+        k, pk = self._table256(select)
+        self._chk(self.lib.scvod_map_query(self.h, C.c_void_p(d_xyzi.data_ptr()), off.ctypes.data_as(C.c_void_p), len(off) - 1,
+                                           None if p is None else p.ctypes.data_as(C.c_void_p), float(radius), pk, *ptr, C.c_void_p(stream or 0)))
+        return out
+
+    def query_batch(self, ctx, poses, radius=0.0, select=None, want=("result",), stream=None):
+        """scvod_batch_map_query: the same for every input point of the ctx's last batch"""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p.shape[0] == ctx._n_scans
+        out, ptr = self._query_outputs(int(ctx._n_pts), ctx._n_scans, radius, want)
+        k, pk = self._table256(select)
+        self._chk(self.lib.scvod_batch_map_query(ctx.h, self.h, p.ctypes.data_as(C.c_void_p), float(radius), pk, *ptr, C.c_void_p(stream or 0)))
+        return out
+
+    def query_stats(self):
+        """{points, cell, near, miss, out} of the last query (synchronises its stream)"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_map_query_stats(self.h, o))
+        return dict(zip(("points", "cell", "near", "miss", "out"), (int(v) for v in o[:5])))
+
+    def query_scratch_bytes(self):
+        return int(self.lib.scvod_map_query_scratch_bytes(self.h))
 
     def points_labelled(self, select=None, stream=None):
         """labelled maps: (xyzi float32 [n, 4], labels uint8 [n], records int64 [n, 2]) of the cells whose label is selected (see

@@ -682,6 +682,53 @@ int64_t scvod_map_scratch_bytes(const scvod_map* map);
 int scvod_map_points_labelled(scvod_map* map, void* d_xyzi, uint8_t* d_labels, void* d_records, int64_t cap, const uint8_t* h_select256,
                               int64_t* n_out, void* stream);
 
+/* ---- asking the map: the cell of a point and the nearest representative around it (both kinds) ------------------------------------
+ * Reads the table only: no record, no counter of the map, no scratch of the accumulate calls moves.  The point at h_scan_offsets[s] + i
+ * of d_xyzi (packed float4, 16-byte aligned) is moved by the pose of scan s with the expression of the accumulate calls (products and
+ * sums rounded one by one; h_poses NULL: the zero pose) and its OWN CELL is the key an accumulate would give it.  A key is present iff
+ * it is met from its home slot before an empty slot and within 512 slots -- the bound insertion uses, so a key that any accumulate or
+ * merge placed is always found and one whose insertion was dropped is absent.  With h_select256 (labelled maps only) a cell whose
+ * label byte is not selected counts as empty for every output.
+ * radius == 0 looks at the own cell only (d_nn_key and d_nn_sqdist must be NULL).  0 < radius <= 0.99f * leaf also looks at the 27
+ * cells around the own cell (cells outside the +-2^20 range do not exist): a CANDIDATE is the representative of an occupied, selected
+ * cell among them, decoded in fp32 as scvod_map_points does, ((float)c + (q + 0.5f) / 65536.0f) * leaf per axis, at squared distance
+ * d = (dx*dx + dy*dy) + dz*dz in fp32 from the moved point, and it counts only when d < radius * radius.  The nearest wins, equal d
+ * goes to the smaller key.  While fp32 rounding of the coordinates stays far below 0.01 * leaf (a few km from the origin at leaf 0.2)
+ * this is the nearest representative of the whole map within the radius; the definition is the 27-cell one.
+ * Every output is optional and holds one entry per input point at the input index h_scan_offsets[s] + i:
+ *   d_result      one SCVOD_MAPQ_* byte.  It speaks about cells, the nn pair about distance: an occupied own cell whose representative
+ *                 is farther than the radius is CELL with an empty nn pair.
+ *   d_cell_val    the own cell's 64-bit value (what scvod_map_export hands out), ~0 when it is absent or the point has no cell
+ *   d_nn_key, d_nn_sqdist   key and d of the nearest candidate, ~0 and +inf when there is none
+ *   d_scan_counts [n_scans][4] is overwritten with the numbers of {CELL, NEAR, MISS, OUT} points per scan
+ * When only d_result, d_cell_val or d_scan_counts are asked for, a point whose own cell is occupied never looks at its neighbours.
+ * Stream-ordered against accumulate, merge and clear; offsets, poses and the select table are copied before the call returns, and the
+ * call never synchronises with the host -- except as the accumulate calls do: offsets or poses that differ from the previous call's
+ * wait for `stream` first (a query with the poses of the accumulate before it uploads nothing), and the first query allocates its
+ * counters.  Using one map from two streams at once is the caller's business: nothing here orders them, and the staging copies and
+ * the counters are one per map.
+ * Refused with SCVOD_ERR_INVALID before anything is launched or written: a NULL map, a radius that is negative, NaN or above
+ * 0.99f * leaf, an nn output with radius 0, a select table on a plain map, n_scans < 0, NULL offsets, offsets that decrease or start
+ * below 0, NULL points of a cloud that is not empty, a d_xyzi that is not 16-byte aligned. */
+#define SCVOD_MAPQ_MISS 0 /* own cell not occupied, and (radius > 0) no representative within the radius */
+#define SCVOD_MAPQ_CELL 1 /* own cell occupied                                                            */
+#define SCVOD_MAPQ_NEAR 2 /* own cell not occupied, a representative of the 27 cells is within the radius */
+#define SCVOD_MAPQ_OUT 3  /* the point has no cell: its coordinates are NaN or beyond +-2^20 cells         */
+int scvod_map_query(scvod_map* map, const void* d_xyzi, const int32_t* h_scan_offsets, int32_t n_scans, const float* h_poses, float radius,
+                    const uint8_t* h_select256, uint8_t* d_result, uint64_t* d_cell_val, uint64_t* d_nn_key, float* d_nn_sqdist,
+                    int64_t* d_scan_counts, void* stream);
+/* The same for the input cloud of the ctx's last batch, every input point included (those Patchwork dropped too); h_poses
+ * [n_scans][6].  SCVOD_ERR_STATE without a processed batch of input clouds, SCVOD_ERR_INVALID for a map on another device, both before
+ * anything is launched; stream NULL = the stream of the ctx's last batch call. */
+int scvod_batch_map_query(scvod_ctx* ctx, scvod_map* map, const float* h_poses, float radius, const uint8_t* h_select256, uint8_t* d_result,
+                          uint64_t* d_cell_val, uint64_t* d_nn_key, float* d_nn_sqdist, int64_t* d_scan_counts, void* stream);
+/* h_out8 = {points, CELL, NEAR, MISS, OUT, 0, 0, 0} of the last query.  Synchronises that query's stream.  SCVOD_ERR_STATE before the
+ * first query. */
+int scvod_map_query_stats(scvod_map* map, int64_t* h_out8);
+/* bytes of device memory the queries hold on this map: their counters (0 before the first query, and for NULL).
+ * scvod_map_scratch_bytes and scvod_arena_bytes do not move. */
+int64_t scvod_map_query_scratch_bytes(const scvod_map* map);
+
 /* ---- the result of a batch handed on: per-point labels and the cleaned scans, on the device -------------------------------
  * Reference analogue: the `static_pt` / `dynamic_pt` lists of SSC::saveSegCloud mode 3 (src/ssc.cpp:477-554) and the clouds of the
  * evaluation block (`cloud_eva_static`, `g_cloud_vec`, the _static / _dynamic / _original .pcd files, ssc.cpp:1454-1540).  The
