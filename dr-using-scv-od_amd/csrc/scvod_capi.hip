@@ -3538,6 +3538,26 @@ int scvod_batch_object_truth_stats(scvod_ctx* c, int64_t* h_out8) {
     return SCVOD_OK;
 }
 
+// internal bridge for scvod_mapfilter.hip (not part of the public header): the lists the last scvod_batch_objects left in the scratch,
+// under the state rules of scvod_batch_object_truth; on a refusal *err is the ctx's message
+int scvod__ctx_object_lists(scvod_ctx* c, const char* who, const long long** tab_stats, const uint64_t** key_out, const int32_t** begin,
+                            const char** err) {
+    int rc = SCVOD_OK;
+    if (!c->obj_lists_serial)
+        rc = fail(c, SCVOD_ERR_STATE, "%s needs a scvod_batch_objects that asked for records or members", who);
+    else if ((rc = export_check(c, c->obj_lists_track, who)) != SCVOD_OK)
+        ;
+    else if (c->obj_lists_serial != c->cluster_serial)
+        rc = fail(c, SCVOD_ERR_STATE, "%s: the last object table belongs to an earlier clustering: call scvod_batch_objects again", who);
+    *err = c->err.c_str();
+    if (rc) return rc;
+    const size_t N = (size_t)(c->cap_pts > 0 ? c->cap_pts : 1);
+    *tab_stats = c->obj_stats;
+    *key_out = c->obj_keys + N;
+    *begin = c->obj_words + 2 * N;
+    return SCVOD_OK;
+}
+
 int64_t scvod_batch_object_truth_scratch_bytes(scvod_ctx* c) {
     return c ? (int64_t)c->ot.cap + (c->ot_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
 }

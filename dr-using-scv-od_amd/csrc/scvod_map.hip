@@ -446,6 +446,7 @@ void scvod_map_destroy(scvod_map* m) {
     if (m->d_offs) hipFree(m->d_offs);
     if (m->d_cls) hipFree(m->d_cls);
     if (m->q_counters) hipFree(m->q_counters);
+    if (m->f_buf) hipFree(m->f_buf);
     delete m;
 }
 

@@ -1,6 +1,6 @@
-// scvod_maptable.h -- the static map's table as its two translation units see it: the record, the map object, the hash, the cell of a
+// scvod_maptable.h -- the static map's table as its translation units see it: the record, the map object, the hash, the cell of a
 // point, the probe load, the decode of a record and the host-side staging of poses and scan offsets.  scvod_map.hip fills, merges and
-// exports the table; scvod_mapquery.hip only reads it.
+// exports the table; scvod_mapquery.hip and scvod_mapfilter.hip only read it (through scvod_mapprobe.h).
 #ifndef SCVOD_MAPTABLE_H_
 #define SCVOD_MAPTABLE_H_
 #include <hip/hip_runtime.h>
@@ -40,6 +40,12 @@ struct scvod_map {
     long long q_points = 0;                    // points of the last query
     hipStream_t q_stream = nullptr;            // its stream
     bool q_ran = false;
+    // scvod_map_filter: one grow-only block of the filter's own (its counters, side and result bytes, tile counts; scvod_mapfilter.hip)
+    unsigned char* f_buf = nullptr;
+    size_t f_cap = 0;
+    long long f_points = 0;          // points of the last filter
+    hipStream_t f_stream = nullptr;  // its stream
+    bool f_ran = false;
     std::string err;
 };
 
@@ -200,5 +206,7 @@ extern "C" int scvod__ctx_types_valid(scvod_ctx* c);
 extern "C" int scvod__ctx_view(scvod_ctx* ctx, scvod::Arena* arena, int* device, int* track_valid, int* batch_valid, int* n_scans,
                                int* max_scan_pts, int* batch_mode, int* num_min_pts);
 extern "C" void* scvod__ctx_stream(scvod_ctx* ctx, void* stream);
+extern "C" int scvod__ctx_object_lists(scvod_ctx* ctx, const char* who, const long long** tab_stats, const uint64_t** key_out, const int32_t** begin,
+                                       const char** err);
 
 #endif

@@ -145,6 +145,22 @@ class ObjectTruthResult(C.Structure):
     _fields_ = [(n, C.c_int64) for n in OBJECT_TRUTH_COUNTS] + [(n, C.c_double) for n in ("precision", "recall")]
 
 
+class MapFilterParams(C.Structure):
+    """struct scvod_map_filter_params (include/scvod.h), 24 bytes"""
+    _fields_ = [("radius", C.c_float), ("flags", C.c_int32), ("vote_num", C.c_int32), ("vote_den", C.c_int32), ("min_points", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# struct scvod_map_filter_object: what the members of one object of the table said (scvod_batch_map_filter's d_votes), 32 bytes
+MAP_FILTER_OBJECT_DTYPE = np.dtype([("n_cell", "<i4"), ("n_near", "<i4"), ("n_miss", "<i4"), ("n_out", "<i4"), ("n_points", "<i4"),
+                                    ("verdict", "<i4"), ("reserved", "<i4", 2)])
+MAPF_KNOWN, MAPF_NOVEL, MAPF_OUT = 0, 1, 2  # SCVOD_MAPF_*: the side byte of StaticMap.filter
+MAPF_OBJECT_VOTE = 1                         # SCVOD_MAPF_OBJECT_VOTE
+MAP_FILTER_TILE = 2048                       # SCVOD_MAP_FILTER_TILE
+MAPF_OUTPUTS = ("result", "side", "order", "bounds", "xyzi", "payload", "votes")
+MAP_FILTER_STATS = ("points", "known", "novel", "out", "moved_to_known", "moved_to_novel", "objects_voted", "objects_known")
+
+
 class SplitParams(C.Structure):
     """struct scvod_split_params (include/scvod.h)"""
     _fields_ = [("cell", C.c_float), ("max_rings", C.c_int32), ("base_stride", C.c_int32), ("query_stride", C.c_int32),
@@ -299,6 +315,11 @@ def load_lib():
         "scvod_batch_map_query": (C.c_int, [vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
         "scvod_map_query_stats": (C.c_int, [vp, vp]),
         "scvod_map_query_scratch_bytes": (i64, [vp]),
+        "scvod_map_filter_params_default": (None, [C.POINTER(MapFilterParams)]),
+        "scvod_map_filter": (C.c_int, [vp, vp, vp, i32, vp, C.POINTER(MapFilterParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "scvod_batch_map_filter": (C.c_int, [vp, vp, vp, C.POINTER(MapFilterParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "scvod_map_filter_stats": (C.c_int, [vp, vp]),
+        "scvod_map_filter_scratch_bytes": (i64, [vp]),
         "scvod_batch_point_labels": (C.c_int, [vp, vp, i64, i32, vp]),
         "scvod_batch_export_points": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
         "scvod_batch_export_stats": (C.c_int, [vp, vp]),
@@ -376,6 +397,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_map_create_kind", "scvod_map_kind", "scvod_map_scratch_bytes", "scvod_map_accumulate_labelled",
                     "scvod_batch_map_accumulate_classes", "scvod_map_points_labelled",
                     "scvod_map_query", "scvod_batch_map_query", "scvod_map_query_stats", "scvod_map_query_scratch_bytes",
+                    "scvod_map_filter_params_default", "scvod_map_filter", "scvod_batch_map_filter", "scvod_map_filter_stats",
+                    "scvod_map_filter_scratch_bytes",
                     "scvod_batch_point_labels", "scvod_batch_export_points", "scvod_batch_export_stats",
                     "scvod_batch_objects", "scvod_batch_objects_stats", "scvod_batch_objects_scratch_bytes",
                     "scvod_feature_params_default", "scvod_set_object_features", "scvod_batch_object_shapes", "scvod_batch_object_shapes_stats",
@@ -488,6 +511,16 @@ def instance_finish(table, params=None):
     _status(load_lib().scvod_instance_finish(t.ctypes.data_as(C.c_void_p) if t.size else None, t.size,
                                              C.byref(params) if params is not None else None, C.byref(r)), "scvod_instance_finish")
     return {k: getattr(r, k) for k, _ in InstanceResult._fields_}
+
+
+def map_filter_params_default(**kw):
+    """scvod_map_filter_params with the defaults (radius 0, flags 0, vote 1 / 2, min_points 1), overridden by keyword"""
+    p = MapFilterParams()
+    load_lib().scvod_map_filter_params_default(C.byref(p))
+    for name, value in kw.items():
+        assert name in dict(MapFilterParams._fields_), name
+        setattr(p, name, value)
+    return p
 
 
 def object_truth_params_default(moving_from=None, pure_from=None, min_points=None):
@@ -1550,6 +1583,59 @@ class StaticMap:
 
     def query_scratch_bytes(self):
         return int(self.lib.scvod_map_query_scratch_bytes(self.h))
+
+    # ---- cleaning scans against the map (include/scvod.h: scvod_map_filter) ----
+    def _filter_outputs(self, n, n_scans, want, payload, votes_cap):
+        """the device tensors a filter writes, by name (MAPF_OUTPUTS), and the pointers result .. xyzi, payload out, votes"""
+        import torch
+        want = tuple(want)
+        assert all(w in MAPF_OUTPUTS for w in want), want
+        assert "payload" not in want or payload is not None, "a payload output needs a payload input"
+        dev = torch.device("cuda", self.device)
+        shape = {"result": ((n,), torch.uint8), "side": ((n,), torch.uint8), "order": ((n,), torch.int32), "bounds": ((n_scans, 2), torch.int32),
+                 "xyzi": ((n, 4), torch.float32), "payload": ((n,), torch.int32), "votes": ((int(votes_cap or 0), 8), torch.int32)}
+        out = {w: torch.empty(shape[w][0], dtype=shape[w][1], device=dev) for w in want}
+        return out, {w: (C.c_void_p(out[w].data_ptr()) if w in out else None) for w in MAPF_OUTPUTS}
+
+    def filter(self, d_xyzi, scan_offsets, poses=None, params=None, select=None, want=("side",), payload=None, stream=None):
+        """scvod_map_filter of the caller's cloud (torch float32 [n, 4] on the map's device): a dict of device tensors, one per name in
+        `want` -- result and side uint8 [n], order int32 [n] (in-scan indices: KNOWN, NOVEL, OUT per scan), bounds int32 [n_scans, 2],
+        xyzi float32 [n, 4], payload int32 [n] (the gather of `payload`, a torch tensor of one 32-bit word per point).  Rows are at the
+        input index, so the offsets should start at 0.  Stream-ordered, no synchronisation."""
+        off = np.ascontiguousarray(scan_offsets, np.int32)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == len(off) - 1
+        out, ptr = self._filter_outputs(int(off[-1]) if len(off) else 0, len(off) - 1, want, payload, None)
+        k, pk = self._table256(select)
+        self._chk(self.lib.scvod_map_filter(self.h, C.c_void_p(d_xyzi.data_ptr()), off.ctypes.data_as(C.c_void_p), len(off) - 1,
+                                            None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(params) if params is not None else None, pk,
+                                            ptr["result"], ptr["side"], ptr["order"], ptr["bounds"], ptr["xyzi"],
+                                            None if payload is None else C.c_void_p(payload.data_ptr()), ptr["payload"], C.c_void_p(stream or 0)))
+        return out
+
+    def filter_batch(self, ctx, poses, params=None, select=None, want=("side",), payload=None, votes_cap=None, stream=None):
+        """scvod_batch_map_filter: the same for every input point of the ctx's last batch.  With MAPF_OBJECT_VOTE in params.flags the
+        objects of the ctx's last object table vote; "votes" in want: int32 [votes_cap, 8] records (view as MAP_FILTER_OBJECT_DTYPE on
+        the host; votes_cap None: one per input point, which no table outgrows)"""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p.shape[0] == ctx._n_scans
+        cap = int(ctx._n_pts) if votes_cap is None else int(votes_cap)
+        out, ptr = self._filter_outputs(int(ctx._n_pts), ctx._n_scans, want, payload, cap)
+        k, pk = self._table256(select)
+        self._chk(self.lib.scvod_batch_map_filter(ctx.h, self.h, p.ctypes.data_as(C.c_void_p), C.byref(params) if params is not None else None, pk,
+                                                  ptr["result"], ptr["side"], ptr["order"], ptr["bounds"], ptr["xyzi"],
+                                                  None if payload is None else C.c_void_p(payload.data_ptr()), ptr["payload"],
+                                                  ptr["votes"], cap if "votes" in out else 0, C.c_void_p(stream or 0)))
+        return out
+
+    def filter_stats(self):
+        """the MAP_FILTER_STATS of the last filter as a dict (synchronises its stream); ScvodError with status -4 after a votes overflow"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_map_filter_stats(self.h, o))
+        return dict(zip(MAP_FILTER_STATS, (int(v) for v in o)))
+
+    def filter_scratch_bytes(self):
+        return int(self.lib.scvod_map_filter_scratch_bytes(self.h))
 
     def points_labelled(self, select=None, stream=None):
         """labelled maps: (xyzi float32 [n, 4], labels uint8 [n], records int64 [n, 2]) of the cells whose label is selected (see

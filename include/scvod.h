@@ -729,6 +729,78 @@ int scvod_map_query_stats(scvod_map* map, int64_t* h_out8);
  * scvod_map_scratch_bytes and scvod_arena_bytes do not move. */
 int64_t scvod_map_query_scratch_bytes(const scvod_map* map);
 
+/* ---- cleaning scans against a prior map: every scan split into its known, novel and cell-less points ------------------------------
+ * Reference analogue: none (the reference keeps its map as a PCL cloud and has no such program); sides and vote rule are this
+ * library's convention.
+ * Cloud, offsets, poses, radius, select table, the point's transform and its OWN CELL are exactly those of scvod_map_query, the staging
+ * and stream-order rules included: offsets, poses, parameters and the select table are copied before the call returns, a filter with
+ * the poses of the accumulate or query before it uploads nothing, and the call synchronises with the host only as scvod_map_query does
+ * (offsets or poses that changed; a scratch that has to grow).  params NULL = the defaults.
+ * OWN SIDE.  d_result (optional) is the byte scvod_map_query writes for the same arguments, before any vote.  A point's own side is
+ * SCVOD_MAPF_KNOWN for CELL or NEAR, SCVOD_MAPF_NOVEL for MISS, SCVOD_MAPF_OUT for OUT.  With a radius, a point whose own cell is
+ * occupied never looks at its neighbours; no nn pair is produced here.
+ * VOTE (SCVOD_MAPF_OBJECT_VOTE, scvod_batch_map_filter only).  For every object of the table that the last scvod_batch_objects left
+ * in the ctx's scratch (the state rules of scvod_batch_object_truth; a SCVOD_OBJ_NO_TRACK table is fine) the results of its member
+ * points are counted.  An object with n_points >= min_points VOTES: it is KNOWN iff
+ *     (int64)(n_cell + n_near) * vote_den >= (int64)vote_num * n_points
+ * and NOVEL otherwise -- integers only, so host and device agree by construction.  A member whose own result is not OUT takes its
+ * object's verdict as its side.  OUT members and every point that is no member of a voting object (ground, rejected, dropped and
+ * unclustered points, members of objects below min_points) keep their own side.  d_votes (optional) receives one
+ * scvod_map_filter_object per object in table order; nothing is written at or behind cap_votes, an overflow is latched for
+ * scvod_map_filter_stats and changes no side and no other output.
+ * OUTPUTS, each optional, each exactly as many entries as the input (no capacity, no overflow):
+ *   d_side         one SCVOD_MAPF_* byte per input point at the input index
+ *   d_order        the stable three-way partition PER SCAN: with b = h_scan_offsets[s], d_order[b + j] lists the in-scan indices of the
+ *                  KNOWN points ascending, then the NOVEL ones ascending, then the OUT ones ascending
+ *   d_bounds       int32 [n_scans][2] on the device: {n_known, n_known + n_novel} of scan s
+ *   d_xyzi_out     d_xyzi_out[b + j] = the input record d_xyzi[b + d_order[b + j]] bit for bit (sensor frame; the intensity word and NaN
+ *                  payloads travel); 16-byte aligned
+ *   d_payload_out  the same gather of d_payload_in (one uint32 per input point); refused without d_payload_in
+ * The partition works on tiles of SCVOD_MAP_FILTER_TILE consecutive points of one scan; no workgroup waits for another.
+ * The call reads the table only: no record and no counter of the map moves, scvod_map_query_stats keeps describing the last QUERY, and
+ * scvod_map_query_scratch_bytes, scvod_map_scratch_bytes, scvod_arena_bytes, the object table's and the truth stage's scratch do not
+ * move.  The filter's scratch is one grow-only allocation of its own, owned by the map and freed with it, sized from the points and
+ * scans of the largest call.  Stream-ordered against accumulate, merge, clear and query.
+ * Refused with SCVOD_ERR_INVALID before anything is launched, written or allocated: everything scvod_map_query refuses; reserved != 0;
+ * an unknown flag bit; vote_den < 1, vote_num < 0, vote_num > vote_den, vote_den > 1 << 20; min_points < 1; the vote flag on
+ * scvod_map_filter; d_votes without the flag, or cap_votes < 0; an output that overlaps the input cloud; a d_xyzi_out that is not
+ * 16-byte aligned (d_order, d_bounds, the payloads: 4-byte; d_votes: 4-byte); d_payload_out without d_payload_in.  scvod_batch_map_filter:
+ * SCVOD_ERR_STATE as scvod_batch_map_query (no processed batch) and, with the vote, as scvod_batch_object_truth (no usable table). */
+#define SCVOD_MAPF_KNOWN 0 /* the map knows the point (own cell occupied, or a representative within the radius) or its object */
+#define SCVOD_MAPF_NOVEL 1
+#define SCVOD_MAPF_OUT 2   /* SCVOD_MAPQ_OUT: the point has no cell; a vote never moves a point into or out of this side */
+#define SCVOD_MAPF_OBJECT_VOTE 1 /* flags bit 0, batch form only */
+#define SCVOD_MAP_FILTER_TILE 2048 /* points per tile of the partition */
+typedef struct scvod_map_filter_params { /* 24 bytes */
+    float radius;               /* as scvod_map_query: 0 = own cell only, at most 0.99f * leaf */
+    int32_t flags;
+    int32_t vote_num, vote_den; /* an object is KNOWN iff (int64)(n_cell + n_near) * vote_den >= (int64)vote_num * n_points */
+    int32_t min_points;         /* objects with fewer members do not vote: their points keep their own side */
+    int32_t reserved;           /* 0 */
+} scvod_map_filter_params;
+/* radius 0, flags 0, vote 1 / 2, min_points 1, reserved 0 */
+void scvod_map_filter_params_default(scvod_map_filter_params* p);
+typedef struct scvod_map_filter_object { /* 32 bytes, one per object of the table, table order */
+    int32_t n_cell, n_near, n_miss, n_out; /* the members' SCVOD_MAPQ_* results */
+    int32_t n_points;                      /* == scvod_object::n_points */
+    int32_t verdict;                       /* SCVOD_MAPF_KNOWN / SCVOD_MAPF_NOVEL; -1: below min_points, did not vote */
+    int32_t reserved[2];                   /* 0 */
+} scvod_map_filter_object;
+int scvod_map_filter(scvod_map* map, const void* d_xyzi, const int32_t* h_scan_offsets, int32_t n_scans, const float* h_poses,
+                     const scvod_map_filter_params* params, const uint8_t* h_select256, uint8_t* d_result, uint8_t* d_side, int32_t* d_order,
+                     int32_t* d_bounds, void* d_xyzi_out, const uint32_t* d_payload_in, uint32_t* d_payload_out, void* stream);
+/* The same for every input point of the ctx's last batch, as scvod_batch_map_query; h_poses [n_scans][6]; stream NULL = the stream of
+ * the ctx's last batch call.  d_votes: [cap_votes] scvod_map_filter_object records or NULL. */
+int scvod_batch_map_filter(scvod_ctx* ctx, scvod_map* map, const float* h_poses, const scvod_map_filter_params* params,
+                           const uint8_t* h_select256, uint8_t* d_result, uint8_t* d_side, int32_t* d_order, int32_t* d_bounds, void* d_xyzi_out,
+                           const uint32_t* d_payload_in, uint32_t* d_payload_out, void* d_votes, int64_t cap_votes, void* stream);
+/* h_out8 = {points, KNOWN, NOVEL, OUT, points the vote moved NOVEL->KNOWN, points it moved KNOWN->NOVEL, objects that voted, objects
+ * that voted and came out KNOWN} of the last filter (without the vote flag the last four are 0).  Synchronises that filter's stream.
+ * SCVOD_ERR_CAPACITY after a d_votes overflow, with h_out8 filled; SCVOD_ERR_STATE before the first filter. */
+int scvod_map_filter_stats(scvod_map* map, int64_t* h_out8);
+/* bytes of device memory the filter holds on this map (0 before the first call, and for NULL) */
+int64_t scvod_map_filter_scratch_bytes(const scvod_map* map);
+
 /* ---- the result of a batch handed on: per-point labels and the cleaned scans, on the device -------------------------------
  * Reference analogue: the `static_pt` / `dynamic_pt` lists of SSC::saveSegCloud mode 3 (src/ssc.cpp:477-554) and the clouds of the
  * evaluation block (`cloud_eva_static`, `g_cloud_vec`, the _static / _dynamic / _original .pcd files, ssc.cpp:1454-1540).  The
