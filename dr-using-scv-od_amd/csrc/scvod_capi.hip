@@ -252,6 +252,7 @@ struct scvod_ctx {
     bool voxels_valid = false;   // the last batch ran the voxel stage in descriptor mode (not VoxelGrid)
     int desc_mode = 0;           // scvod_set_voxel_descriptors: 0 vox_av / vox_cov of a batch on demand (lean voxel stage), 1 eager
     bool desc_valid = false;     // vox_av / vox_cov hold the last batch's values (ensure_descriptors fills them otherwise)
+    bool int_valid = true;       // apri_int holds the last batch's intensities (a lean emission leaves them out: ensure_intensities)
     bool clusters_valid = false;
     bool clustered_this_batch = false;       // the batch's pt_mapcls bytes carry car / dynamic marks of an earlier clustering (cleared before the next one)
     bool types_valid = false;
@@ -816,6 +817,10 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
     // 0.7 ms slower for it, profiles/lazy_voxel_descriptors_cost.md; SCVOD_VOX_LEAN_MERGE: development, that measurement)
     static const bool lean_merge = getenv("SCVOD_VOX_LEAN_MERGE") != nullptr;
     const int lean = (lean_ok && do_voxels && do_patchwork != 3 && c->desc_mode == 0 && (c->im_iterations == 0 || lean_merge)) ? 1 : 0;
+    // the lean emission (k_emit<true>: no point gather, no apri_int) goes with the lean voxel stage, whose kernels never read an
+    // intensity; the calibration reads and patches apri_int right behind the emission, and a grid beyond the packed triple's limits
+    // cannot have its voxel key recomputed from it: both keep the gather form
+    const int lean_emit = (lean && do_patchwork == 1 && !c->cal_on && idx3_roundtrip_ok(c->dev.bin)) ? 1 : 0;
     // marks per input point for the static map (car-cluster member / dynamic / list marks): clean for every new batch
     if (mx > 0 && do_patchwork != 2 && do_patchwork != 3) HIPCHK(c, hipMemsetAsync(c->A.pt_mapcls, 0, (size_t)total, st));
     c->clustered_this_batch = false;
@@ -826,7 +831,7 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
         if (rc_cal) return rc_cal;
         if (do_voxels) launch_process(c->dev, c->A, st, 4, apply_filter, 1, timer_hook, c, lean);
     } else if (mx > 0) {
-        launch_process(c->dev, c->A, st, do_patchwork, apply_filter, do_voxels, timer_hook, c, lean);
+        launch_process(c->dev, c->A, st, do_patchwork, apply_filter, do_voxels, timer_hook, c, lean, lean_emit);
     }
     c->cal_done = c->cal_on && do_patchwork == 1;  // (a batch of empty scans is a calibrated batch of no points)
     HIPCHK(c, hipGetLastError());
@@ -837,6 +842,7 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
     c->batch_valid = true;
     c->voxels_valid = (do_voxels != 0);
     c->desc_valid = (do_voxels != 0) && !lean;  // (every process call decides it again: a lean batch's descriptors are not there yet)
+    c->int_valid = !(lean_emit && mx > 0);
     c->have_patchwork = (do_patchwork == 1);
     c->batch_mode = do_patchwork;
     c->apri_compact = (do_patchwork == 1);
@@ -855,11 +861,24 @@ int ensure_counts(scvod_ctx* c) {
     return SCVOD_OK;
 }
 
+// Every reader of apri_int comes through here first: a lean emission left it unwritten, k_apri_intensity fills it for the whole batch
+// on stream st at the first request.  Its inputs (the input cloud, apri_src, counts) outlive the batch's chain.  Today's readers:
+// k_vx_descriptors (below).  The fused voxel tiers, the calibration and its k_cal_apri run only in a ctx that emitted eagerly; the
+// expansion to PointAPRI records reads the input cloud itself.
+int ensure_intensities(scvod_ctx* c, hipStream_t st) {
+    if (c->int_valid) return SCVOD_OK;
+    launch_apri_intensity(c->A, st, timer_hook, c);
+    HIPCHK(c, hipGetLastError());
+    c->int_valid = true;
+    return SCVOD_OK;
+}
+
 // Every reader of vox_av / vox_cov comes through here first: a lean voxel stage left them unwritten, k_vx_descriptors fills them for the
 // whole batch on stream st -- ordered behind the batch's own kernels there -- at the first request.  Its inputs (vox_pt_begin, vox_pts,
 // apri_int) are written by the voxel stage and its predecessors only; no later stage uses them as scratch.
 int ensure_descriptors(scvod_ctx* c, hipStream_t st) {
     if (!c->voxels_valid || c->desc_valid) return SCVOD_OK;
+    if (int rc_int = ensure_intensities(c, st)) return rc_int;
     launch_vox_descriptors(c->A, 0, c->A.n_scans, st, timer_hook, c);
     HIPCHK(c, hipGetLastError());
     c->desc_valid = true;

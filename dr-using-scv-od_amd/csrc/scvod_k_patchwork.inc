@@ -94,11 +94,12 @@ __global__ __launch_bounds__(kClsThreads) void k_pw_scatter(DevParams P, Arena A
 //   k_pw_sort*    tiers by size class: LDS bitonic sort of the patch's (z, idx) keys, then the patch's points are
 //                 written in sorted order (packed xyz + input index).
 //   k_pw_fit_coop patches of >= 512 points (>= 64 for a handful of scans): GL lanes per patch; products in parallel,
-//                 the nine sequential fp32 sums on nine lanes; then the same lanes arrange the patch (arrange_group).
+//                 the nine sequential fp32 sums on nine lanes; then the same lanes arrange the patch (arrange_group); LEAN form:
+//                 they also bin its kept non-ground points (packed index triple into zkey).
 //   k_pw_fit      the smaller patches, ONE LANE PER PATCH (the 3x3 Jacobi SVD then costs one lane, not one wave),
 //                 reads staged cooperatively through LDS.
 //   k_pw_arrange  the patches of k_pw_fit, one wave per patch: final plane test, [ground part | non-ground part] arrangement
-//                 and the per-patch counters the ordered emission needs.
+//                 and the per-patch counters the ordered emission needs; LEAN form as arrange_group's.
 // ------------------------------------------------------------------------------------------
 // size classes (pw_size_class) that bound the sort tiers: class 40 <=> n >= 1024, class 48 <=> n >= 4096
 constexpr int kClassXS = 32, kClassM = 40, kClassM2 = 44, kClassL = 48;  // n >= 256 / 1024 / 2048 / 4096
@@ -464,13 +465,29 @@ __device__ __forceinline__ void fit_finish(const DevParams& P, const Arena& A, i
     A.fit_thd[s * kMaxPatches + p] = thd;
 }
 
+// index triple of a point that passed the range/FOV test, packed (pack_idx3): the guarded estimate decides it away from the bin
+// edges, the reference arithmetic next to one.  The lean emission's arrange pass computes it from the coordinates it holds anyway.
+__device__ __forceinline__ uint32_t triple_of_point(const DevParams& P, float x, float y, float z) {
+    int32_t ri, si, ai;
+    if (!idx3_fast(P.bin, P.binfast, x, y, z, &ri, &si, &ai)) {
+        Apri a;
+        apri_of_point(P.bin, x, y, z, 0.f, a);
+        ri = a.range_idx;
+        si = a.sector_idx;
+        ai = a.azimuth_idx;
+    }
+    return (uint32_t)pack_idx3(ri, si, ai);
+}
+
 // Final plane test of every point of a fitted patch (patchwork.h:488-501) by the GL lanes that fitted it: [ground part -> | <- non-ground
 // part] arrangement in z order (element r of the non-ground part lives at seg[n - 1 - r]; k_emit reads it that way), the range/FOV
 // verdict of makeApriVec for the points that reach the non-ground stream, the per-patch counters the ordered emission needs.
 // Wave-uniform call (ballots): groups without a patch pass n = 0.  n_max = largest n of the wave's groups.
-template <int GL>
+// LEAN (the lean emission): a kept point's packed index triple goes to stage[] at the position of its seg word, so that k_emit<true>
+// never fetches the point again.
+template <int GL, bool LEAN>
 __device__ __forceinline__ void arrange_group(const DevParams& P, const Arena& A, const Xyz* __restrict__ sp, const uint32_t* __restrict__ si, uint32_t* seg,
-                                              int n, int n_max, int slot, bool live, int r, int gbase, float n0, float n1, float n2, float thd, int status) {
+                                              uint32_t* stage, int n, int n_max, int slot, bool live, int r, int gbase, float n0, float n1, float n2, float thd, int status) {
     constexpr unsigned long long FULL = (GL == 64) ? ~0ull : ((1ull << (GL & 63)) - 1ull);
     auto group_bits = [&](unsigned long long ballot) -> unsigned long long { return (ballot >> gbase) & FULL; };
     const bool rejected = (status >= 2);
@@ -500,6 +517,9 @@ __device__ __forceinline__ void arrange_group(const DevParams& P, const Arena& A
                 seg[n_g + __popcll(bg & below)] = w;
             else
                 seg[n - 1 - (n_ng + __popcll(bn & below))] = w;
+            if constexpr (LEAN) {
+                if (keep) stage[g ? n_g + __popcll(bg & below) : n - 1 - (n_ng + __popcll(bn & below))] = triple_of_point(P, q.x, q.y, q.z);
+            }
         }
         a_g += __popcll(group_bits(__ballot(g && keep)));
         a_ng += __popcll(group_bits(__ballot(!g && keep && j < n)));
@@ -711,7 +731,8 @@ __global__ __launch_bounds__(64) void k_pw_fit(DevParams P, Arena A, int coop_cl
 #ifndef SCVOD_COOP_PF
 #define SCVOD_COOP_PF 4
 #endif
-template <int GL>
+// LEAN: the arrangement behind the fit stages the kept points' index triples for the lean emission (arrange_group).
+template <int GL, bool LEAN>
 __global__ __launch_bounds__(64, GL == 16 ? SCVOD_COOP_WAVES : 1) void k_pw_fit_coop(DevParams P, Arena A, int coop_class) {
     constexpr int NG = 64 / GL;
     constexpr int ROW = GL + 4;             // floats per product row: padded so the nine row reads spread over the banks
@@ -860,7 +881,7 @@ __global__ __launch_bounds__(64, GL == 16 ? SCVOD_COOP_WAVES : 1) void k_pw_fit_
     if (live && r == 0) fit_finish(P, A, s, p, n, zone, ring, concentric_idx, F);
     // the arrangement by the lanes that fitted the patch (round 5; was k_pw_arrange, a pass of its own over every patch)
     const int status = fit_status(P, zone, ring, concentric_idx, F);
-    arrange_group<GL>(P, A, sp, A.sorted_idx + (size_t)item.z + item.w, A.seg + (size_t)item.z + item.w, n, n_max, code, live, r, gbase, F.n0, F.n1, F.n2,
+    arrange_group<GL, LEAN>(P, A, sp, A.sorted_idx + (size_t)item.z + item.w, A.seg + (size_t)item.z + item.w, A.zkey + (size_t)item.z + item.w, n, n_max, code, live, r, gbase, F.n0, F.n1, F.n2,
                       F.thd, status);
 }
 
@@ -869,7 +890,8 @@ __global__ __launch_bounds__(64, GL == 16 ? SCVOD_COOP_WAVES : 1) void k_pw_fit_
 // z order inside the ground part and the non-ground part, counts what k_emit_offsets needs.
 // GL lanes per patch: 64 for patches of 64 points or more, 16 (four patches per wave) for the many smaller ones, whose
 // cost is the per-patch latency chain, not the points.
-template <int GL>
+// LEAN: as arrange_group<GL, true>, the staging words live in zkey (dead since k_pw_scatter, free until the max_name pass).
+template <int GL, bool LEAN>
 __global__ __launch_bounds__(256) void k_pw_arrange(DevParams P, Arena A, int c_lo, int c_hi) {
     constexpr int NG = 64 / GL;
     constexpr unsigned long long FULL = (GL == 64) ? ~0ull : ((1ull << (GL & 63)) - 1ull);
@@ -932,6 +954,7 @@ __global__ __launch_bounds__(256) void k_pw_arrange(DevParams P, Arena A, int c_
         // (element r of the non-ground part lives at seg[n - 1 - r]; k_emit reads it that way)
         int n_g = 0, n_ng = 0, a_g = 0, a_ng = 0;
         uint32_t* seg = A.seg + (size_t)base + off;
+        uint32_t* stage = A.zkey + (size_t)base + off;
         // the next GL points are in flight while this step is classified (clamped, unconditional loads)
         Xyz q_next = head.q;
         uint32_t w_next = head.w;
@@ -958,6 +981,9 @@ __global__ __launch_bounds__(256) void k_pw_arrange(DevParams P, Arena A, int c_
                     seg[n_g + __popcll(bg & below)] = w;
                 else
                     seg[n - 1 - (n_ng + __popcll(bn & below))] = w;
+                if constexpr (LEAN) {
+                    if (keep) stage[g ? n_g + __popcll(bg & below) : n - 1 - (n_ng + __popcll(bn & below))] = triple_of_point(P, q.x, q.y, q.z);
+                }
             }
             a_g += __popcll(group_bits(__ballot(g && keep)));
             a_ng += __popcll(group_bits(__ballot(!g && keep && j < n)));
@@ -982,9 +1008,8 @@ __global__ __launch_bounds__(256) void k_pw_arrange(DevParams P, Arena A, int c_
 
 // ------------------------------------------------------------------------------------------
 // Emission: per-scan exclusive scans over patches (reference emission order = patch order),
-// then one workgroup per patch writes cloud_out / cloud_nonground indices, per-point class,
-// apri_vec (ordered compaction of the non-ground stream by the range/FOV verdict) and the
-// rejected list.
+// then one wave per patch writes cloud_out / cloud_nonground indices, apri_vec (ordered
+// compaction of the non-ground stream by the range/FOV verdict) and the rejected list.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_emit_offsets(DevParams P, Arena A) {
     __shared__ int wsum[17];
@@ -1031,7 +1056,12 @@ __global__ __launch_bounds__(1024) void k_emit_offsets(DevParams P, Arena A) {
     }
 }
 
+// Two forms.  The eager one (LEAN = false) gathers every kept point from the input cloud: index triple, voxel key and the compact
+// intensity come from its coordinates.  The lean one is a pure compaction: the arrange pass staged the packed triple next to the
+// seg word (zkey), the key is recomputed from it (exact while the grid fits the packing: idx3_roundtrip_ok, decided on the host),
+// and apri_int stays unwritten until somebody asks (k_apri_intensity).
 constexpr int kEmitThreads = 256;
+template <bool LEAN>
 __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -1065,6 +1095,7 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
         const int xg = meta.o.x, xng = meta.o.y, xa = meta.o.z, xr = meta.o.w;
         const bool kept = (r.status == 1);
         const uint32_t* seg = A.seg + (size_t)base + off;
+        const uint32_t* stage = A.zkey + (size_t)base + off;
         // ground part of a kept patch -> cloud_out
         if (kept) {
             for (int e = lane; e < r.n_g; e += 64) {
@@ -1076,26 +1107,43 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
         // by the non-ground part; the latter is stored back to front by k_pw_arrange
         const int e0 = kept ? r.n_g : 0;
         int run_keep = 0;
-        auto seg_at = [&](int e) -> uint32_t {  // clamped, unconditional load (callers test e < r.n)
+        auto seg_pos = [&](int e) -> int {  // clamped position of stream element e in the patch (callers test e < r.n)
             const int k = (e < r.n_g) ? e : r.n - 1 - (e - r.n_g);
-            return seg[min(max(k, 0), r.n - 1)];
+            return min(max(k, 0), r.n - 1);
         };
-        // two steps of seg words and one step of point gathers are in flight while a step is emitted; lanes that keep
-        // nothing gather the scan's first point (one shared line) so the load needs no branch
+        auto seg_at = [&](int e) -> uint32_t { return seg[seg_pos(e)]; };  // clamped, unconditional load
+        // eager form: two steps of seg words and one step of point gathers are in flight while a step is emitted; lanes that
+        // keep nothing gather the scan's first point (one shared line) so the load needs no branch.
+        // lean form: two steps of seg words and of staged triples (a word of a point that was not kept holds anything: never used)
         auto gather = [&](uint32_t v, int e) -> float4 {
-            const bool k = (e < r.n) && (v >> 31);
-            return A.pts[base + (k ? (v & 0x7fffffffu) : 0u)];
+            if constexpr (LEAN) {
+                return make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                const bool k = (e < r.n) && (v >> 31);
+                return A.pts[base + (k ? (v & 0x7fffffffu) : 0u)];
+            }
+        };
+        auto stage_at = [&](int e) -> uint32_t {
+            if constexpr (LEAN)
+                return stage[seg_pos(e)];
+            else
+                return 0u;
         };
         uint32_t v0 = seg_at(e0 + lane), v1 = seg_at(e0 + 64 + lane);
+        uint32_t t0 = stage_at(e0 + lane), t1 = stage_at(e0 + 64 + lane);
         float4 q0 = gather(v0, e0 + lane);
         for (int c0 = e0; c0 < r.n; c0 += 64) {
             const int e = c0 + lane;
             const uint32_t v = v0;
+            const uint32_t t = t0;
             const float4 q = q0;
             const uint32_t v2 = seg_at(e + 128);
+            const uint32_t t2 = stage_at(e + 128);
             q0 = gather(v1, e + 64);
             v0 = v1;
             v1 = v2;
+            t0 = t1;
+            t1 = t2;
             const int keep = (e < r.n) ? (int)(v >> 31) : 0;
             const unsigned long long bk = __ballot(keep);
             const int ek = __popcll(bk & ((1ull << lane) - 1ull));
@@ -1110,7 +1158,9 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
                     // PointAPRI records are expanded from it on request (k_apri_expand).  Only the indices are needed here: the
                     // guarded estimate decides them away from the bin edges, the reference arithmetic next to one
                     int32_t ri, si, ai;
-                    if (!idx3_fast(P.bin, P.binfast, q.x, q.y, q.z, &ri, &si, &ai)) {
+                    if constexpr (LEAN) {
+                        unpack_idx3((int32_t)t, &ri, &si, &ai);  // (exactly the point's indices: the host checked that the grid fits the packing)
+                    } else if (!idx3_fast(P.bin, P.binfast, q.x, q.y, q.z, &ri, &si, &ai)) {
                         Apri a;
                         apri_of_point(P.bin, q.x, q.y, q.z, q.w, a);
                         ri = a.range_idx;
@@ -1119,8 +1169,12 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
                     }
                     A.apri_src[dst0 + ek] = (int32_t)id;
                     A.apri_key[dst0 + ek] = ai * P.bin.range_num * P.bin.sector_num + ri * P.bin.sector_num + si;
-                    A.apri_int[dst0 + ek] = q.w;
-                    A.apri_idx3[dst0 + ek] = pack_idx3(ri, si, ai);
+                    if constexpr (LEAN) {
+                        A.apri_idx3[dst0 + ek] = (int32_t)t;
+                    } else {
+                        A.apri_int[dst0 + ek] = q.w;
+                        A.apri_idx3[dst0 + ek] = pack_idx3(ri, si, ai);
+                    }
                     if ((unsigned)ri >= (unsigned)P.bin.range_num || (unsigned)si >= (unsigned)P.bin.sector_num || (unsigned)ai >= (unsigned)P.bin.azimuth_num)
 {
                         A.scan_irr[s] = 1;  // (rare: a -1 bin; every writer stores the same value)
@@ -1140,3 +1194,11 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
     }
 }
 
+// the compact intensities a lean emission left out, on request (ensure_intensities): apri_int[i] = intensity of apri point i's input
+// point.  Streams apri_src, gathers 4 of the point's 16 bytes.  grid = (blocks along a scan, B).
+__global__ __launch_bounds__(256) void k_apri_intensity(Arena A) {
+    const int s = blockIdx.y;
+    const size_t base = (size_t)A.scan_off[s];
+    const int n = A.counts[s * 8 + 4];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) A.apri_int[base + i] = A.pts[base + A.apri_src[base + i]].w;
+}

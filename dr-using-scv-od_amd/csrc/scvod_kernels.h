@@ -67,7 +67,8 @@ struct Arena {
     uint32_t* seg;            // [N] per patch: [ground part -> | <- non-ground part (stored back to front)], bit31 = passes bin filter
     Xyz* sorted_xyz;          // [N] per patch: points in (z, idx) order, packed 12-byte xyz
     uint32_t* sorted_idx;     // [N] same order: input index | (passes the range/FOV test) << 31
-    uint32_t* zkey;           // [N] sortable z key per input point
+    uint32_t* zkey;           // [N] sortable z key per input point (k_pw_classify -> k_pw_scatter); then, lean emission: packed index triple of
+                              //   the kept points at the position of their seg word (arrange pass -> k_emit<true>); then scratch of the max_name pass
     float* fit_thd;           // [B][kMaxPatches] th_dist_d_ of the last plane fit
     int4* order;              // [B * kMaxPatches] live patches by descending size class: {scan*1024+patch, n, scan base, patch offset}
     int32_t* order_hist;      // [64]
@@ -86,7 +87,7 @@ struct Arena {
     scvod_apri* apri;         // [N]
     int32_t* apri_src;        // [N]
     int32_t* apri_key;        // [N] PointAPRI::voxel_idx, compact copy for the voxel stage
-    float* apri_int;          // [N] PointAPRI::intensity, compact copy for the voxel stage
+    float* apri_int;          // [N] PointAPRI::intensity, compact copy for the voxel stage (a lean emission leaves it to k_apri_intensity, on demand)
     int32_t* apri_idx3;       // [N] PointAPRI::{range,sector,azimuth}_idx packed 11+11+10 bits (clustering)
     int32_t* rejected_src;    // [N]
     int32_t* counts;          // [B][8]
@@ -370,10 +371,13 @@ typedef void (*TimerHook)(void* user, const char* name, int begin);
 // 2 = neither (apri / counts already in the arena: voxel stage only), 4 = the voxel stage alone on the compact arrays a
 // do_patchwork = 1 call without voxels left (the intensity calibration runs between the two).
 void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_patchwork, int apply_filter,
-                    int do_voxels, TimerHook th, void* tu, int lean_voxels = 0);
+                    int do_voxels, TimerHook th, void* tu, int lean_voxels = 0, int lean_emit = 0);
 // lean_voxels = 1: the voxel stage leaves vox_av / vox_cov unwritten; launch_vox_descriptors fills them for scans [s0, s0 + n_scans)
 // from vox_pt_begin / vox_pts / apri_int when somebody asks
 void launch_vox_descriptors(const Arena& A, int s0, int n_scans, hipStream_t st, TimerHook th, void* tu);
+// lean_emit = 1 (do_patchwork = 1 only; the caller checked idx3_roundtrip_ok): the arrange pass stages the kept points' index triples
+// in zkey, k_emit compacts them without fetching a point and leaves apri_int unwritten; launch_apri_intensity fills it for the batch
+void launch_apri_intensity(const Arena& A, hipStream_t st, TimerHook th, void* tu);
 void launch_apri_expand(const DevParams& P, const Arena& A, int s0, int n_scans, int max_pts, hipStream_t st);
 struct VgJob {                // SSC::getCloud label filter + pcl::VoxelGrid (ssc.cpp:1063-1076, 1103-1106)
     const uint32_t* labels;   // per input point, or nullptr (no filter, no intensity scaling)

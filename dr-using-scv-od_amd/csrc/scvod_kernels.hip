@@ -5,7 +5,7 @@
 //                                                                                  k_pw_order_*, k_pw_sort_wave, k_pw_sort<...>
 //   extract_piecewiseground / seeds / plane fit    patchwork.h:217-268,463-504 -> k_pw_fit_coop<16|64>, k_pw_fit
 //   gating + emission order                        patchwork.h:326-391         -> fit_status / fit_finish, arrange_group (in k_pw_fit_coop), k_pw_arrange, k_emit_offsets, k_emit
-//   SSC::makeApriVec                               ssc.cpp:155-195             -> k_emit (fused, compact apri_vec), k_apri_expand,
+//   SSC::makeApriVec                               ssc.cpp:155-195             -> k_emit (fused, compact apri_vec; lean form: binned by the arrange pass, k_apri_intensity on demand), k_apri_expand,
 //                                                                                  k_bin_direct
 //   SSC::makeHashCloud                             ssc.cpp:253-289             -> k_vx_partition (count + offsets + scatter per scan), k_vx_order_*,
 //                                                                                  k_vx_bucket<...>, k_vx_final*
@@ -230,15 +230,7 @@ __device__ __forceinline__ unsigned long long pack_key(uint32_t key, uint32_t id
 __device__ __forceinline__ uint32_t key_idx(unsigned long long k) { return (uint32_t)k & ((1u << kKeyIdxBits) - 1u); }
 __device__ __forceinline__ uint32_t key_major(unsigned long long k) { return (uint32_t)(k >> kKeyIdxBits); }
 
-// index triple of an apri point, packed by k_emit / k_bin_direct / k_apri_split: 11 + 11 + 10 bits, each index clamped
-// to [-2, limit] and biased by 2 (indices at or beyond -2 / dim + 1 have no in-grid neighbour at all, so clamping them
-// keeps both the run comparison and the neighbourhood exact)
-__device__ __forceinline__ int32_t pack_idx3(int r, int s, int a) {
-    r = min(max(r, -2), 2045) + 2;
-    s = min(max(s, -2), 2045) + 2;
-    a = min(max(a, -2), 1021) + 2;
-    return r | (s << 11) | (a << 22);
-}
+// (pack_idx3 / unpack_idx3, the packed index triple of an apri point: scvod_math.h, where the CPU checks the lean emission's bound)
 
 __device__ __forceinline__ void cswap_asc(unsigned long long& x, unsigned long long& y) {
     double lo, hi;
@@ -453,7 +445,7 @@ constexpr int kVoxCapS = 1024, kVoxThreadsS = 64;
 constexpr int kVoxCapL = 8192, kVoxThreadsL = 512;
 
 void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_patchwork, int apply_filter,
-                    int do_voxels, TimerHook th, void* tu, int lean_voxels) {
+                    int do_voxels, TimerHook th, void* tu, int lean_voxels, int lean_emit) {
     const int B = A.n_scans;
     if (B <= 0) return;
     if (do_patchwork == 1) {
@@ -514,24 +506,41 @@ void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_p
         const int coop_class = (B <= 8) ? kClassWave : kClassFitCoop;
         const int coop_min = 1 << (coop_class / 4);
         TH_BEGIN("pw_fit_large");
-        if (B <= 8)
-            hipLaunchKernelGGL(k_pw_fit_coop<64>, dim3((int)(A.total_pts / coop_min) + 1), dim3(64), 0, st, P, A, coop_class);
-        else
-            hipLaunchKernelGGL(k_pw_fit_coop<16>, dim3((int)(A.total_pts / coop_min / 4) + 1), dim3(64), 0, st, P, A, coop_class);
+        // (lean_emit: the arrangements stage the kept points' index triples in zkey and k_emit<true> compacts them, see k_emit)
+        const dim3 gfit((int)(A.total_pts / coop_min / (B <= 8 ? 1 : 4)) + 1);
+        if (B <= 8) {
+            if (lean_emit)
+                hipLaunchKernelGGL((k_pw_fit_coop<64, true>), gfit, dim3(64), 0, st, P, A, coop_class);
+            else
+                hipLaunchKernelGGL((k_pw_fit_coop<64, false>), gfit, dim3(64), 0, st, P, A, coop_class);
+        } else {
+            if (lean_emit)
+                hipLaunchKernelGGL((k_pw_fit_coop<16, true>), gfit, dim3(64), 0, st, P, A, coop_class);
+            else
+                hipLaunchKernelGGL((k_pw_fit_coop<16, false>), gfit, dim3(64), 0, st, P, A, coop_class);
+        }
         TH_END("pw_fit_large");
         TH_BEGIN("pw_fit");
         hipLaunchKernelGGL(k_pw_fit, dim3((n_all + 63) / 64), dim3(64), 0, st, P, A, coop_class);
         TH_END("pw_fit");
         TH_BEGIN("pw_arrange");
         // (patches of the 16-lane fit are arranged by the lanes that fitted them; what is left: the lane-per-patch fit's)
-        if (coop_class > kClassWave) hipLaunchKernelGGL((k_pw_arrange<64>), dim3(kPersistCUs * 8), dim3(256), 0, st, P, A, kClassWave, coop_class - 1);
-        hipLaunchKernelGGL((k_pw_arrange<16>), dim3(kPersistCUs * 4), dim3(256), 0, st, P, A, 0, kClassWave - 1);
+        if (lean_emit) {
+            if (coop_class > kClassWave) hipLaunchKernelGGL((k_pw_arrange<64, true>), dim3(kPersistCUs * 8), dim3(256), 0, st, P, A, kClassWave, coop_class - 1);
+            hipLaunchKernelGGL((k_pw_arrange<16, true>), dim3(kPersistCUs * 4), dim3(256), 0, st, P, A, 0, kClassWave - 1);
+        } else {
+            if (coop_class > kClassWave) hipLaunchKernelGGL((k_pw_arrange<64, false>), dim3(kPersistCUs * 8), dim3(256), 0, st, P, A, kClassWave, coop_class - 1);
+            hipLaunchKernelGGL((k_pw_arrange<16, false>), dim3(kPersistCUs * 4), dim3(256), 0, st, P, A, 0, kClassWave - 1);
+        }
         TH_END("pw_arrange");
         TH_BEGIN("emit_offsets");
         hipLaunchKernelGGL(k_emit_offsets, dim3(B), dim3(1024), 0, st, P, A);
         TH_END("emit_offsets");
         TH_BEGIN("emit");
-        hipLaunchKernelGGL(k_emit, dim3(kPersistCUs * 8), dim3(kEmitThreads), 0, st, P, A);
+        if (lean_emit)
+            hipLaunchKernelGGL(k_emit<true>, dim3(kPersistCUs * 8), dim3(kEmitThreads), 0, st, P, A);
+        else
+            hipLaunchKernelGGL(k_emit<false>, dim3(kPersistCUs * 8), dim3(kEmitThreads), 0, st, P, A);
         TH_END("emit");
     } else if (do_patchwork == 0) {  // (2: a caller's apri_vec, 3: the VoxelGrid run, 4: the compact arrays of an earlier do_patchwork = 1 call
                                      //  without voxels, the intensity calibration having run in between: nothing to do before the voxel stage)
@@ -633,6 +642,13 @@ void launch_vox_descriptors(const Arena& A, int s0, int n_scans, hipStream_t st,
     TH_BEGIN("vx_descriptors");
     hipLaunchKernelGGL(k_vx_descriptors, dim3((A.max_scan_pts + 4095) / 4096, n_scans), dim3(256), 0, st, A, s0);  // (voxels <= points; grid-stride)
     TH_END("vx_descriptors");
+}
+
+void launch_apri_intensity(const Arena& A, hipStream_t st, TimerHook th, void* tu) {
+    if (A.n_scans <= 0 || A.max_scan_pts <= 0) return;
+    TH_BEGIN("emit_intensity");
+    hipLaunchKernelGGL(k_apri_intensity, dim3((A.max_scan_pts + 2047) / 2048, A.n_scans), dim3(256), 0, st, A);
+    TH_END("emit_intensity");
 }
 
 void launch_apri_expand(const DevParams& P, const Arena& A, int s0, int n_scans, int max_pts, hipStream_t st) {

@@ -461,6 +461,28 @@ SCVOD_HD bool voxel_idx_fast(const BinParams& g, const BinFast& f, float x, floa
     return true;
 }
 
+// ---- index triple of an apri point, packed by the arrange kernels (lean emission) / k_emit / k_bin_direct / k_apri_split:
+// 11 + 11 + 10 bits, each index clamped to [-2, limit] and biased by 2 (indices at or beyond -2 / dim + 1 have no in-grid
+// neighbour at all, so clamping them keeps both the run comparison and the neighbourhood exact).
+// A point that passed the range / FOV test has its indices in [-1, dim] (the quotient at the upper limit may round one bin up),
+// so unpacking returns them -- and with them voxel_idx -- exactly as long as dim <= kIdx3Max*: the lean emission's condition
+// (idx3_roundtrip_ok; tests/test_gpu_lean_emission.py checks the bound against apri_of_point on the CPU).
+constexpr int32_t kIdx3MaxRS = 2045, kIdx3MaxA = 1021;
+SCVOD_HD int32_t pack_idx3(int32_t r, int32_t s, int32_t a) {
+    r = (r < -2 ? -2 : (r > kIdx3MaxRS ? kIdx3MaxRS : r)) + 2;
+    s = (s < -2 ? -2 : (s > kIdx3MaxRS ? kIdx3MaxRS : s)) + 2;
+    a = (a < -2 ? -2 : (a > kIdx3MaxA ? kIdx3MaxA : a)) + 2;
+    return r | (s << 11) | (int32_t)((uint32_t)a << 22);
+}
+SCVOD_HD void unpack_idx3(int32_t t, int32_t* r, int32_t* s, int32_t* a) {
+    *r = (t & 2047) - 2;
+    *s = ((t >> 11) & 2047) - 2;
+    *a = ((t >> 22) & 1023) - 2;
+}
+inline bool idx3_roundtrip_ok(const BinParams& g) {  // every index in [-1, dim] survives the clamp
+    return g.range_num < kIdx3MaxRS && g.sector_num < kIdx3MaxRS && g.azimuth_num < kIdx3MaxA;
+}
+
 // ---- range / FOV verdict of makeApriVec WITHOUT the two atan2f of apri_of_point, for callers that only need the
 // verdict (k_pw_arrange).  Same result by construction:
 //   * range: the same fp32 sqrt and comparisons.
@@ -470,6 +492,8 @@ SCVOD_HD bool voxel_idx_fast(const BinParams& g, const BinFast& f, float x, floa
 //   * azimuth: atan2f(z, dis) and the conversion to degrees are within 1.2e-5 deg of atan(z / dis) * 180 / pi, so when
 //     t = z / dis is farther than 2e-6 * (1 + t^2) (six times that error, in units of t) from tan(min_azimuth) and
 //     tan(max_azimuth) the decision is known; only points inside that sliver evaluate apri_of_point.
+//   * y == +-0 takes the reference arithmetic: atan2f(-0, x < 0) is -pi, the one direction whose polar angle IS negative
+//     (-180 degrees: the reference drops the point).
 struct KeepFast {
     int32_t ok;      // the shortcut is valid for this parameter set
     float tan_lo, tan_hi;
@@ -485,7 +509,7 @@ inline KeepFast keep_fast_of(const BinParams& g) {
     return k;
 }
 SCVOD_HD int keep_of_point(const BinParams& g, const KeepFast& k, float x, float y, float z) {
-    if (k.ok) {
+    if (k.ok && y != 0.0f) {
         const float dis = point_distance2d(x, y);
         if (dis < g.min_dis || dis > g.max_dis) return 0;
         const float t = z / dis;  // dis == 0: inf / NaN, which fails every comparison below -> reference arithmetic
