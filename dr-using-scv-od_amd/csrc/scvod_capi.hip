@@ -253,6 +253,7 @@ struct scvod_ctx {
     int desc_mode = 0;           // scvod_set_voxel_descriptors: 0 vox_av / vox_cov of a batch on demand (lean voxel stage), 1 eager
     bool desc_valid = false;     // vox_av / vox_cov hold the last batch's values (ensure_descriptors fills them otherwise)
     bool int_valid = true;       // apri_int holds the last batch's intensities (a lean emission leaves them out: ensure_intensities)
+    bool lists_valid = true;     // ground_idx / nonground_idx / rejected_src hold the last batch's lists (a lean emission leaves them out: ensure_lists)
     bool clusters_valid = false;
     bool clustered_this_batch = false;       // the batch's pt_mapcls bytes carry car / dynamic marks of an earlier clustering (cleared before the next one)
     bool types_valid = false;
@@ -310,6 +311,7 @@ void carve(scvod_ctx* c, unsigned char* base, size_t* total) {
     A.pid = k.take<int16_t>(N);
     A.keys = k.take<uint64_t>(N);
     A.seg = k.take<uint32_t>(N);
+    A.ln_scratch = A.seg;  // (scvod_batch_cluster decides it again)
     A.sorted_xyz = k.take<Xyz>(N + 8);
     A.sorted_idx = k.take<uint32_t>(N);
     A.zkey = k.take<uint32_t>(N);
@@ -843,6 +845,7 @@ int run_batch(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int32_t n_
     c->voxels_valid = (do_voxels != 0);
     c->desc_valid = (do_voxels != 0) && !lean;  // (every process call decides it again: a lean batch's descriptors are not there yet)
     c->int_valid = !(lean_emit && mx > 0);
+    c->lists_valid = !(lean_emit && mx > 0);  // (every process call decides it again, as int_valid)
     c->have_patchwork = (do_patchwork == 1);
     c->batch_mode = do_patchwork;
     c->apri_compact = (do_patchwork == 1);
@@ -885,6 +888,22 @@ int ensure_descriptors(scvod_ctx* c, hipStream_t st) {
     return SCVOD_OK;
 }
 
+// Every reader of ground_idx / nonground_idx / rejected_src comes through here first: a lean emission left them unwritten, k_emit_lists
+// fills the three for the whole batch on stream st -- ordered behind the batch's own kernels there -- at the first request.  Today's
+// readers: fetch_scan (the lists and, through k_cls_from_lists, cls), the label / class kernels of scvod_export.hip, k_map_mark_lists
+// (scvod__ctx_ensure_lists) and the calibration, whose ctx emits eagerly anyway.  Its inputs (order, order_off, patch_rec, emit_off, seg)
+// are written by the Patchwork kernels only; the one stage that takes scratch from them, the max_name pass with its tables in the arena,
+// takes the scan's slice of ground_idx instead while the lists are pending (Arena::ln_scratch): this call waits for that pass and
+// then rewrites the slice wholly.
+int ensure_lists(scvod_ctx* c, hipStream_t st) {
+    if (c->lists_valid) return SCVOD_OK;
+    if (c->ln_done) HIPCHK(c, hipStreamWaitEvent(st, c->ln_done, 0));  // (whichever stream joined the pass before: this one reads after it too)
+    launch_emit_lists(c->A, st, timer_hook, c);
+    HIPCHK(c, hipGetLastError());
+    c->lists_valid = true;
+    return SCVOD_OK;
+}
+
 int fetch_scan(scvod_ctx* c, int32_t s, scvod_scan_result* out) {
     int rc = ensure_counts(c);
     if (rc) return rc;
@@ -907,6 +926,7 @@ int fetch_scan(scvod_ctx* c, int32_t s, scvod_scan_result* out) {
     const Arena& A = c->A;
     hipStream_t st = c->last_stream;
     if (int rc_desc = ensure_descriptors(c, st)) return rc_desc;
+    if (int rc_lists = ensure_lists(c, st)) return rc_lists;
     if (c->have_patchwork) launch_cls(A, s, base, k[0], st);
     if (c->apri_compact && k[4] > 0) launch_apri_expand(c->dev, A, s, 1, k[4], st);  // PointAPRI records of this scan only
     if (c->apri_compact && c->cal_done) launch_calib_apri(A, s, k[4], st);             // ... with the calibrated intensity (a second small
@@ -1333,6 +1353,8 @@ extern "C" int scvod__ctx_view(scvod_ctx* c, Arena* arena, int* device, int* tra
     return 0;
 }
 // the stream a stream-ordered batch call runs on: the caller's, or (NULL) the stream of the ctx's last batch call
+// the three index lists of the batch, written before anything queued on `stream` behind this call reads them (k_map_mark_lists)
+extern "C" int scvod__ctx_ensure_lists(scvod_ctx* c, void* stream) { return ensure_lists(c, (hipStream_t)stream); }
 extern "C" void* scvod__ctx_stream(scvod_ctx* c, void* stream) { return stream ? stream : (void*)(c->last_stream ? c->last_stream : c->stream); }
 
 extern "C" {
@@ -1716,6 +1738,8 @@ int scvod_batch_cluster(scvod_ctx* c, void* stream, int32_t sync) {
         int rc = ensure_merge(c);
         if (rc) return rc;
     }
+    // the max_name pass takes its arena scratch from whichever of {seg, the three index lists} is not needed any more (ensure_lists)
+    c->A.ln_scratch = c->lists_valid ? c->A.seg : (uint32_t*)c->A.ground_idx;
     launch_cluster(c->dev, c->A, c->batch_mode == 2 ? 1 : 0, st, timer_hook, c);
     if (c->im_iterations > 0) {  // (before the max_name passes: they read pt_cluster, left as it was, and the post-merge pt_type)
         if (int rc_desc = ensure_descriptors(c, st)) return rc_desc;  // (the merge compares vox_av / vox_cov)
@@ -1945,6 +1969,7 @@ int scvod_batch_fetch_intensity_calibration(scvod_ctx* c, int32_t s, float* h_no
     J.s0 = s;
     J.ns = 1;
     J.off0 = c->h_scan_off[s];
+    if (int rc_lists = ensure_lists(c, st)) return rc_lists;  // (k_cal_* walk nonground_idx; a calibrated batch emitted eagerly: a no-op today)
     launch_calib(c->A, J, (int)pts, st, nullptr, nullptr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));
@@ -2544,6 +2569,7 @@ int scvod_batch_point_labels(scvod_ctx* c, uint8_t* d_labels, int64_t cap, int32
     hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
     if (c->A.total_pts > 0) {
         HIPCHK(c, hipMemsetAsync(d_labels, SCVOD_PT_DROPPED, (size_t)c->A.total_pts, st));
+        if (int rc = ensure_lists(c, st)) return rc;
         launch_point_labels(c->A, d_labels, use_dyn, st);
         HIPCHK(c, hipGetLastError());
     }
@@ -2561,6 +2587,7 @@ int scvod_batch_point_classes(scvod_ctx* c, uint8_t* d_classes, int64_t cap, int
     hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
     if (c->A.total_pts > 0) {
         HIPCHK(c, hipMemsetAsync(d_classes, SCVOD_PT_DROPPED, (size_t)c->A.total_pts, st));
+        if (int rc = ensure_lists(c, st)) return rc;
         if (c->rg_done)
             launch_point_classes(c->A, c->rg.cls, d_classes, use_dyn, st);
         else
@@ -2607,6 +2634,7 @@ int scvod_batch_export_points(scvod_ctx* c, int32_t flags, const float* h_poses,
     }
     if (c->A.total_pts > 0) {
         HIPCHK(c, hipMemsetAsync(c->exp_labels, SCVOD_PT_DROPPED, (size_t)c->A.total_pts, st));
+        if (int rc = ensure_lists(c, st)) return rc;
         launch_point_labels(c->A, c->exp_labels, use_dyn, st);
     }
     ExportJob J;
@@ -3162,6 +3190,7 @@ static int batch_cloud(scvod_ctx* c, const char* who, const uint32_t* d_gt_label
     if (!use_dyn) keep_mask |= 1u << SCVOD_PT_DYNAMIC;
     if (N > 0) {
         HIPCHK(c, hipMemsetAsync(byte, SCVOD_PT_DROPPED, (size_t)N, st));
+        if (int rc = ensure_lists(c, st)) return rc;
         if (class_byte && c->rg_done)
             launch_point_classes(c->A, c->rg.cls, byte, use_dyn, st);
         else

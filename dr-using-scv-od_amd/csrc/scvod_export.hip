@@ -4,7 +4,8 @@
 //
 // Reference analogue: the `static_pt` / `dynamic_pt` lists of SSC::saveSegCloud mode 3 (ssc.cpp:477-554) and the clouds of the
 // evaluation block (`cloud_eva_static`, `g_cloud_vec`, the _static / _dynamic / _original .pcd files, ssc.cpp:1454-1540).  The
-// reference builds them by appending cluster clouds on one thread; here every array they are made of is in the arena already:
+// reference builds them by appending cluster clouds on one thread; here every array they are made of is in the arena, or is put
+// there by one pass before the first of these calls (ground_idx / rejected_src of a lean batch: ensure_lists, scvod_capi.hip):
 //     ground_idx / rejected_src / apri_src   which cloud an input point went to (a point in none of them was dropped by Patchwork)
 //     pt_type                                the segmentation's type of an apri point's cluster (0 erased, 1 other, 2 car)
 //     pt_dyn                                 what scvod_batch_track decided for it

@@ -1057,9 +1057,11 @@ __global__ __launch_bounds__(1024) void k_emit_offsets(DevParams P, Arena A) {
 }
 
 // Two forms.  The eager one (LEAN = false) gathers every kept point from the input cloud: index triple, voxel key and the compact
-// intensity come from its coordinates.  The lean one is a pure compaction: the arrange pass staged the packed triple next to the
-// seg word (zkey), the key is recomputed from it (exact while the grid fits the packing: idx3_roundtrip_ok, decided on the host),
-// and apri_int stays unwritten until somebody asks (k_apri_intensity).
+// intensity come from its coordinates, and it writes the three index lists (ground_idx, nonground_idx, rejected_src).  The lean one
+// is a pure compaction: the arrange pass staged the packed triple next to the seg word (zkey), the key is recomputed from it (exact
+// while the grid fits the packing: idx3_roundtrip_ok, decided on the host), apri_int stays unwritten until somebody asks
+// (k_apri_intensity), and so do the three lists (k_emit_lists): no kernel of the batch chain reads them.  It never touches the
+// ground part of a kept patch.
 constexpr int kEmitThreads = 256;
 template <bool LEAN>
 __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
@@ -1097,15 +1099,25 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
         const uint32_t* seg = A.seg + (size_t)base + off;
         const uint32_t* stage = A.zkey + (size_t)base + off;
         // ground part of a kept patch -> cloud_out
-        if (kept) {
-            for (int e = lane; e < r.n_g; e += 64) {
-                const uint32_t id = seg[e] & 0x7fffffffu;
-                A.ground_idx[(size_t)base + xg + e] = (int32_t)id;
+        if constexpr (!LEAN) {
+            if (kept) {
+                for (int e = lane; e < r.n_g; e += 64) {
+                    const uint32_t id = seg[e] & 0x7fffffffu;
+                    A.ground_idx[(size_t)base + xg + e] = (int32_t)id;
+                }
             }
         }
         // non-ground stream of this patch: for a rejected patch the ground part (front, ascending) followed
         // by the non-ground part; the latter is stored back to front by k_pw_arrange
         const int e0 = kept ? r.n_g : 0;
+        if constexpr (LEAN) {
+            if (e0 >= r.n) {  // a kept patch that is all ground: nothing to compact
+                item = item1;
+                item1 = item2;
+                meta = meta1;
+                continue;
+            }
+        }
         int run_keep = 0;
         auto seg_pos = [&](int e) -> int {  // clamped position of stream element e in the patch (callers test e < r.n)
             const int k = (e < r.n_g) ? e : r.n - 1 - (e - r.n_g);
@@ -1152,7 +1164,7 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
             if (e < r.n) {
                 const uint32_t id = v & 0x7fffffffu;
                 const int spos = e - e0;  // position in the non-ground stream of this patch
-                A.nonground_idx[(size_t)base + xng + spos] = (int32_t)id;
+                if constexpr (!LEAN) A.nonground_idx[(size_t)base + xng + spos] = (int32_t)id;
                 if (keep) {
                     // apri_vec is kept in its compact form (source index, voxel key, intensity, index triple); the 44-byte
                     // PointAPRI records are expanded from it on request (k_apri_expand).  Only the indices are needed here: the
@@ -1182,11 +1194,73 @@ __global__ __launch_bounds__(kEmitThreads) void k_emit(DevParams P, Arena A) {
                         const int x = atomicAdd(&il[0], 1);
                         if (x < kIrrListCap) il[1 + x] = (int32_t)(xa + run_keep + ek);
                     }
-                } else {
+                } else if constexpr (!LEAN) {
                     A.rejected_src[(size_t)base + xr + (spos - (run_keep + ek))] = (int32_t)id;
                 }
             }
             run_keep += nk;
+        }
+        item = item1;
+        item1 = item2;
+        meta = meta1;
+    }
+}
+
+// the three index lists a lean emission left out, for the whole batch, on request (ensure_lists): k_emit's walk -- one wave per
+// item of A.order -- over patch_rec, emit_off and seg only, and exactly the words k_emit<false> writes, at the same positions.
+// Neither the staged triples nor the input cloud are read: later stages reuse zkey, keys, sorted_xyz and sorted_idx.
+__global__ __launch_bounds__(kEmitThreads) void k_emit_lists(Arena A) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int total = A.order_off[64];
+    if ((int)(blockIdx.x * 4 + wave) >= total) return;
+    const int stride = gridDim.x * 4;
+    struct Meta {
+        PatchRec r;
+        int4 o;
+    };
+    auto load_item = [&](int k) -> int4 { return A.order[min(k, total - 1)]; };
+    auto load_meta = [&](const int4& it) -> Meta {
+        Meta m;
+        m.r = A.patch_rec[it.x];
+        m.o = *reinterpret_cast<const int4*>(A.emit_off + (size_t)it.x * 4);
+        return m;
+    };
+    int w = blockIdx.x * 4 + wave;
+    int4 item = load_item(w), item1 = load_item(w + stride);
+    Meta meta = load_meta(item);
+    for (; w < total; w += stride) {  // (the same pipeline across patches as k_emit: item two ahead, record + offsets one ahead)
+        const int4 item2 = load_item(w + 2 * stride);
+        const Meta meta1 = load_meta(item1);
+        const PatchRec r = meta.r;
+        const int base = item.z, off = item.w;
+        const int xg = meta.o.x, xng = meta.o.y, xr = meta.o.w;
+        const bool kept = (r.status == 1);
+        const uint32_t* seg = A.seg + (size_t)base + off;
+        if (kept) {
+            for (int e = lane; e < r.n_g; e += 64) A.ground_idx[(size_t)base + xg + e] = (int32_t)(seg[e] & 0x7fffffffu);
+        }
+        const int e0 = kept ? r.n_g : 0;
+        auto seg_at = [&](int e) -> uint32_t {  // stream element e of the patch, clamped (callers test e < r.n)
+            const int k = (e < r.n_g) ? e : r.n - 1 - (e - r.n_g);
+            return seg[min(max(k, 0), r.n - 1)];
+        };
+        int run_keep = 0;
+        uint32_t v0 = seg_at(e0 + lane);
+        for (int c0 = e0; c0 < r.n; c0 += 64) {
+            const int e = c0 + lane;
+            const uint32_t v = v0;
+            v0 = seg_at(e + 64);
+            const int keep = (e < r.n) ? (int)(v >> 31) : 0;
+            const unsigned long long bk = __ballot(keep);
+            const int ek = __popcll(bk & ((1ull << lane) - 1ull));
+            if (e < r.n) {
+                const int32_t id = (int32_t)(v & 0x7fffffffu);
+                const int spos = e - e0;
+                A.nonground_idx[(size_t)base + xng + spos] = id;
+                if (!keep) A.rejected_src[(size_t)base + xr + (spos - (run_keep + ek))] = id;
+            }
+            run_keep += __popcll(bk);
         }
         item = item1;
         item1 = item2;

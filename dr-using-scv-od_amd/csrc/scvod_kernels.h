@@ -65,6 +65,10 @@ struct Arena {
     int16_t* pid;             // [N] patch id or -1
     uint64_t* keys;           // [N] (sortable z << 32 | local idx), patch-major per scan
     uint32_t* seg;            // [N] per patch: [ground part -> | <- non-ground part (stored back to front)], bit31 = passes bin filter
+                              //   (input of k_emit_lists while the three index lists of a lean batch are pending)
+    uint32_t* ln_scratch;     // [N] 4 bytes per input point for the class tables of the max_name pass in arena scratch: seg once the three
+                              //   lists are written, ground_idx while they are pending (k_emit_lists rewrites it wholly): one of the two
+                              //   stays intact.  Set by the ctx before every clustering.
     Xyz* sorted_xyz;          // [N] per patch: points in (z, idx) order, packed 12-byte xyz
     uint32_t* sorted_idx;     // [N] same order: input index | (passes the range/FOV test) << 31
     uint32_t* zkey;           // [N] sortable z key per input point (k_pw_classify -> k_pw_scatter); then, lean emission: packed index triple of
@@ -82,8 +86,8 @@ struct Arena {
     int32_t* emit_off;        // [B][kMaxPatches][4]  ground / nonground / apri / rejected
     // outputs of the Patchwork + binning stage
     uint8_t* cls;             // [N] filled per scan on request (scvod_batch_fetch / per-scan API), see k_cls_from_lists
-    int32_t* ground_idx;      // [N]
-    int32_t* nonground_idx;   // [N]
+    int32_t* ground_idx;      // [N]  (the three lists: ground_idx, nonground_idx, rejected_src -- written by k_emit<false>; a lean batch
+    int32_t* nonground_idx;   // [N]   leaves them to k_emit_lists, on demand)
     scvod_apri* apri;         // [N]
     int32_t* apri_src;        // [N]
     int32_t* apri_key;        // [N] PointAPRI::voxel_idx, compact copy for the voxel stage
@@ -378,6 +382,9 @@ void launch_vox_descriptors(const Arena& A, int s0, int n_scans, hipStream_t st,
 // lean_emit = 1 (do_patchwork = 1 only; the caller checked idx3_roundtrip_ok): the arrange pass stages the kept points' index triples
 // in zkey, k_emit compacts them without fetching a point and leaves apri_int unwritten; launch_apri_intensity fills it for the batch
 void launch_apri_intensity(const Arena& A, hipStream_t st, TimerHook th, void* tu);
+// ... and writes none of ground_idx / nonground_idx / rejected_src; launch_emit_lists fills the three for the batch from order,
+// order_off, patch_rec, emit_off and seg
+void launch_emit_lists(const Arena& A, hipStream_t st, TimerHook th, void* tu);
 void launch_apri_expand(const DevParams& P, const Arena& A, int s0, int n_scans, int max_pts, hipStream_t st);
 struct VgJob {                // SSC::getCloud label filter + pcl::VoxelGrid (ssc.cpp:1063-1076, 1103-1106)
     const uint32_t* labels;   // per input point, or nullptr (no filter, no intensity scaling)

@@ -4,7 +4,7 @@
 //   PatchWork::estimate_ground prologue + pc2czm   patchwork.h:277-325,416-459 -> k_pw_classify, k_pw_offsets, k_pw_scatter,
 //                                                                                  k_pw_order_*, k_pw_sort_wave, k_pw_sort<...>
 //   extract_piecewiseground / seeds / plane fit    patchwork.h:217-268,463-504 -> k_pw_fit_coop<16|64>, k_pw_fit
-//   gating + emission order                        patchwork.h:326-391         -> fit_status / fit_finish, arrange_group (in k_pw_fit_coop), k_pw_arrange, k_emit_offsets, k_emit
+//   gating + emission order                        patchwork.h:326-391         -> fit_status / fit_finish, arrange_group (in k_pw_fit_coop), k_pw_arrange, k_emit_offsets, k_emit (lean form: the index lists by k_emit_lists, on demand)
 //   SSC::makeApriVec                               ssc.cpp:155-195             -> k_emit (fused, compact apri_vec; lean form: binned by the arrange pass, k_apri_intensity on demand), k_apri_expand,
 //                                                                                  k_bin_direct
 //   SSC::makeHashCloud                             ssc.cpp:253-289             -> k_vx_partition (count + offsets + scatter per scan), k_vx_order_*,
@@ -649,6 +649,13 @@ void launch_apri_intensity(const Arena& A, hipStream_t st, TimerHook th, void* t
     TH_BEGIN("emit_intensity");
     hipLaunchKernelGGL(k_apri_intensity, dim3((A.max_scan_pts + 2047) / 2048, A.n_scans), dim3(256), 0, st, A);
     TH_END("emit_intensity");
+}
+
+void launch_emit_lists(const Arena& A, hipStream_t st, TimerHook th, void* tu) {
+    if (A.n_scans <= 0 || A.max_scan_pts <= 0) return;
+    TH_BEGIN("emit_lists");
+    hipLaunchKernelGGL(k_emit_lists, dim3(kPersistCUs * 8), dim3(kEmitThreads), 0, st, A);
+    TH_END("emit_lists");
 }
 
 void launch_apri_expand(const DevParams& P, const Arena& A, int s0, int n_scans, int max_pts, hipStream_t st) {

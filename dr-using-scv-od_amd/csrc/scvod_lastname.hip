@@ -886,13 +886,14 @@ __device__ void ln_scan(const DevParams& P, const Arena& A, int s, unsigned char
     Rp<CAP> T;
     static_assert(GT == Rp<CAP>::kHbm, "the pass with its tables in arena scratch is the kLnCapHugeNodes one");
     if constexpr (GT) {
-        // the read-mostly class tables (times, first points, their minimum, flags: 13 bytes per node) in arena scratch -- `seg`, 4 bytes per input
-        // point, dead since k_emit -- and the one the rounds hammer with atomics in LDS: the next round's times, whose room the
+        // the read-mostly class tables (times, first points, their minimum, flags: 13 bytes per node) in arena scratch -- ln_scratch, 4 bytes
+        // per input point: `seg`, dead once the three index lists are written, or the scan's slice of ground_idx while they are pending
+        // (k_emit_lists still needs seg then) -- and the one the rounds hammer with atomics in LDS: the next round's times, whose room the
         // partition's parent array takes over when the rounds are done (the two are never live together)
         const int fit = (int)min((long long)CAP, (4ll * L.n_raw - 64) / 13);
         T.cap = fit > 0 ? (fit & ~3) : 0;
         T.in_hbm = true;
-        int32_t* g = (int32_t*)(A.seg + base);
+        int32_t* g = (int32_t*)(A.ln_scratch + base);
         T.T = g;
         T.fa = g + T.cap;
         T.lab = g + 2 * (size_t)T.cap;

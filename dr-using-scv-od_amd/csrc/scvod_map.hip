@@ -522,6 +522,7 @@ int scvod_batch_map_accumulate_range(scvod_ctx* ctx, scvod_map* m, const float* 
     if (max_pts > 0 && count > 0) {
         const int need_lists = (flags & (SCVOD_MAP_NO_GROUND | SCVOD_MAP_NO_REJECTED)) ? 1 : 0;
         if (need_lists) {  // rare: a map without the ground / without the range-FOV rejects needs those two lists marked
+            if (int rc = scvod__ctx_ensure_lists(ctx, st)) return mfail(m, rc, "%s", scvod_last_error(ctx));  // (a lean batch left them to their first reader)
             hipLaunchKernelGGL(k_map_mark_lists, dim3((max_pts + 2047) / 2048, n_scans), dim3(256), 0, st, A);
         }
         hipLaunchKernelGGL(k_map_accumulate, dim3((max_pts + kMapPts - 1) / kMapPts, count), dim3(256), 0, st, first, A, m->d_pose, m->table,

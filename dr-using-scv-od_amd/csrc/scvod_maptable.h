@@ -206,6 +206,7 @@ extern "C" int scvod__ctx_types_valid(scvod_ctx* c);
 extern "C" int scvod__ctx_view(scvod_ctx* ctx, scvod::Arena* arena, int* device, int* track_valid, int* batch_valid, int* n_scans,
                                int* max_scan_pts, int* batch_mode, int* num_min_pts);
 extern "C" void* scvod__ctx_stream(scvod_ctx* ctx, void* stream);
+extern "C" int scvod__ctx_ensure_lists(scvod_ctx* ctx, void* stream);  // ground_idx / nonground_idx / rejected_src of a lean batch, before their reader
 extern "C" int scvod__ctx_object_lists(scvod_ctx* ctx, const char* who, const long long** tab_stats, const uint64_t** key_out, const int32_t** begin,
                                        const char** err);
 

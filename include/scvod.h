@@ -255,7 +255,10 @@ int scvod_batch_counts(scvod_ctx* ctx, int32_t* h_out);
 /* Download the full result of scan `s` of the last batch.  vox_av / vox_cov: a batch's voxel stage leaves them out (nothing on the
  * device chain reads them unless the intensity merge is on); the first fetch of a batch computes them for all its scans with one
  * kernel on the batch's stream, later fetches find them there.  Same bits as the per-scan calls return
- * (scvod_set_voxel_descriptors chooses when they are computed, never what). */
+ * (scvod_set_voxel_descriptors chooses when they are computed, never what).  ground_idx / nonground_idx / rejected_src (and cls, built
+ * from them): the emission of such a batch leaves the three lists out as well -- the first reader of a list (this call, the label /
+ * class / export calls, a map accumulated without the ground or without the rejects) pays one pass over the batch, later readers
+ * find them there; a ctx in scvod_set_voxel_descriptors mode 1 writes them in the emission, as the per-scan calls do. */
 int scvod_batch_fetch(scvod_ctx* ctx, int32_t s, scvod_scan_result* out);
 
 /* When the per-voxel intensity descriptors (vox_av / vox_cov) of a batch are computed.  mode 0 (the default): on demand -- at the

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development tool: what the on-demand side of the lean emission costs.  A bench-shaped batch is processed in the default mode (lean
-emission, lean voxel stage) with the per-kernel timing on; the first batch_fetch then runs k_apri_intensity ("emit_intensity") and
-k_vx_descriptors for the whole batch.  Prints their hipEvent times next to the batch's own `emit`, and the same for a ctx forced eager.
+emission, lean voxel stage) with the per-kernel timing on; the first batch_fetch then runs k_apri_intensity ("emit_intensity"),
+k_emit_lists ("emit_lists") and k_vx_descriptors for the whole batch.  Prints their hipEvent times next to the batch's own `emit`, and the same for a ctx forced eager.
 usage: python tools/lean_emission_cost.py [--kind K64] [--scans 2761] [--reps 3]"""
 import argparse
 import json
@@ -45,7 +45,7 @@ def main():
                 kt[name] = kt.get(name, 0.0) + ms
             rows.append(kt)
         rows = rows[1:]  # (the first pass warms up)
-        out[tag] = {k: [round(r.get(k, 0.0), 3) for r in rows] for k in ("emit", "emit_intensity", "vx_descriptors", "pw_fit_large", "pw_arrange")}
+        out[tag] = {k: [round(r.get(k, 0.0), 3) for r in rows] for k in ("emit", "emit_intensity", "emit_lists", "vx_descriptors", "pw_fit_large", "pw_arrange")}
         out[tag]["binned_points"] = int(ctx.batch_counts()[:, 4].sum())
         ctx.close()
     print(json.dumps(out))
