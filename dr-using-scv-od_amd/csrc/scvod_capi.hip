@@ -226,6 +226,11 @@ struct scvod_ctx {
     // allocated by the first call; not part of the arena, not the evaluation's and not the class scores'
     Scratch sp;  // stream / ran: the last split (scvod_map_split_stats waits for it)
     unsigned long long* sp_stats = nullptr;
+    // seen-through points (scvod_visibility_device / scvod_batch_visibility, scvod_visibility.hip): a grow-only block (range images,
+    // pair / scan / tile tables, the batch form's mask) and 8 counter words of their own, allocated by the first call; not part of the arena
+    Scratch vis;  // stream / ran: the last vote (scvod_visibility_stats waits for it)
+    unsigned long long* vis_counters = nullptr;
+    std::vector<unsigned char> vis_host;  // the tables as built on the host (scratch of the call; the upload is staged from a copy)
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1552,6 +1557,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->ot.buf) hipFree(c->ot.buf);
     if (c->ot_counters) hipFree(c->ot_counters);
     if (c->stk.buf) hipFree(c->stk.buf);
+    if (c->vis.buf) hipFree(c->vis.buf);
+    if (c->vis_counters) hipFree(c->vis_counters);
     if (c->sp.buf) hipFree(c->sp.buf);
     if (c->sp_stats) hipFree(c->sp_stats);
     if (c->stage) hipHostFree(c->stage);
@@ -3771,6 +3778,164 @@ int scvod_stack_scans(scvod_ctx* c, const float* h_xyzi_in, const int32_t* h_in_
 }
 
 int64_t scvod_stack_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)c->stk.cap : 0; }
+
+// ---- seen-through points (scvod_visibility.hip) ----
+struct VisOut {
+    uint32_t* d_votes;
+    uint8_t* d_verdict;
+    float* d_images;
+    int64_t* d_scan_counts;
+};
+
+// what both forms refuse before a device is touched
+static int vis_check(scvod_ctx* c, const scvod_visibility_params* p, const VisOut& o) {
+    if (!p) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (vis_check_params(p))
+        return fail(c, SCVOD_ERR_INVALID,
+                    "visibility: before %d / after %d must be 0..%d and not both 0, halo %d 0 or 1, vote %d / %d with 0 <= num <= 1 << 20 and 1 <= den <= 1 << 20, gaps %g + %g * dis finite and >= 0",
+                    p->before, p->after, SCVOD_VIS_MAX_WINDOW, p->halo, p->vote_num, p->vote_den, (double)p->gap_abs, (double)p->gap_rel);
+    if ((uintptr_t)o.d_images & 15) return fail(c, SCVOD_ERR_INVALID, "d_images is not 16-byte aligned");
+    if ((uintptr_t)o.d_votes & 3) return fail(c, SCVOD_ERR_INVALID, "d_votes is not 4-byte aligned");
+    if ((uintptr_t)o.d_scan_counts & 7) return fail(c, SCVOD_ERR_INVALID, "d_scan_counts is not 8-byte aligned");
+    return SCVOD_OK;
+}
+
+// the vote over scans [0, n_scans) of a cloud on the device; h_off [n_scans + 1] checked by the caller; with_mask: the batch form, whose
+// mask of the non-ground list is scattered into the scratch here
+static int vis_run(scvod_ctx* c, const void* d_xyzi, const int32_t* h_off, int n_scans, const float* h_poses, const std::vector<int32_t>& begin,
+                   const std::vector<int32_t>& viewers, const uint8_t* d_mask, bool with_mask, const scvod_visibility_params* p, const VisOut& o,
+                   hipStream_t st, bool images_only = false) {
+    const BinParams& g = c->dev.bin;
+    const size_t img_words = (size_t)g.azimuth_num * (size_t)g.sector_num;
+    if (g.azimuth_num <= 0 || g.sector_num <= 0) return fail(c, SCVOD_ERR_INVALID, "the ctx's grid has no pixels");
+    const long long hi = n_scans > 0 ? h_off[n_scans] : 0;
+    size_t n_tiles = 0;
+    for (int s = 0; s < n_scans; ++s) n_tiles += (size_t)(((long long)h_off[s + 1] - h_off[s] + kStackTile - 1) / kStackTile);
+    if (n_tiles > 2147483647ull) return fail(c, SCVOD_ERR_CAPACITY, "too many tiles");
+    const size_t n_pairs = viewers.size();
+    // the block: [images unless the caller holds them][pairs][scans][tiles][mask of the batch form]
+    const size_t b_img = o.d_images ? 0 : align_up(sizeof(float) * img_words * (size_t)n_scans, 256);
+    const size_t b_pairs = align_up(sizeof(VisPair) * n_pairs, 256), b_scans = align_up(sizeof(VisScan) * (size_t)n_scans, 256);
+    const size_t b_tiles = align_up(sizeof(StackTile) * n_tiles, 256), b_tab = b_pairs + b_scans + b_tiles;
+    const size_t b_mask = with_mask ? align_up((size_t)hi, 256) : 0;
+    c->vis_host.assign(b_tab, 0);
+    VisPair* pairs = (VisPair*)c->vis_host.data();
+    VisScan* scans = (VisScan*)(c->vis_host.data() + b_pairs);
+    StackTile* tiles = (StackTile*)(c->vis_host.data() + b_pairs + b_scans);
+    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    size_t tile = 0;
+    for (int j = 0; j < n_scans; ++j) {
+        VisScan& S = scans[j];
+        S.base = h_off[j];
+        S.n = h_off[j + 1] - h_off[j];
+        S.pair_begin = begin[j];
+        S.n_pairs = begin[(size_t)j + 1] - begin[j];
+        for (int k = begin[j]; k < begin[(size_t)j + 1]; ++k) {
+            const int v = viewers[k];
+            pairs[k].viewer = v;
+            // trans_v^-1 * trans_j: a point of j's frame in v's frame (scvod_batch_stack_scans' argument order)
+            scvod_pose_delta(h_poses ? h_poses + 6 * (size_t)j : zero, h_poses ? h_poses + 6 * (size_t)v : zero, pairs[k].T);
+        }
+        for (int i = 0; i < S.n; i += kStackTile) tiles[tile++] = StackTile{(int32_t)j, i};
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = counter_block(c, &c->vis_counters, 8)) return rc;
+    if (int rc = scratch_reserve(c, c->vis, b_img + b_tab + b_mask + 256)) return rc;  // (waits for the vote in flight before the block moves)
+    unsigned char* blk = (unsigned char*)c->vis.buf;
+    c->vis.stream = st;
+    c->vis.ran = true;
+    HIPCHK(c, hipMemsetAsync(c->vis_counters, 0, 8 * sizeof(unsigned long long), st));
+    if (o.d_scan_counts && n_scans > 0) HIPCHK(c, hipMemsetAsync(o.d_scan_counts, 0, 6 * sizeof(int64_t) * (size_t)n_scans, st));
+    float* images = o.d_images ? o.d_images : (float*)blk;
+    if (n_scans > 0) HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)images, 0x7F800000, img_words * (size_t)n_scans, st));  // +inf
+    if (n_tiles == 0) return SCVOD_OK;
+    if (int rc = staged_upload(c, c->vis_host.data(), b_tab, blk + b_img, st)) return rc;
+    if (with_mask) {
+        uint8_t* mask = blk + b_img + b_tab;
+        if (int rc = ensure_lists(c, st)) return rc;
+        HIPCHK(c, hipMemsetAsync(mask, 0, (size_t)hi, st));
+        launch_vis_mask(c->A, mask, st);
+        d_mask = mask;
+    }
+    VisJob J;
+    memset(&J, 0, sizeof(J));
+    J.bin = g;
+    J.binfast = c->dev.binfast;
+    J.keep = c->dev.keep;
+    J.halo = p->halo;
+    J.min_through = p->min_through;
+    J.vote_num = p->vote_num;
+    J.vote_den = p->vote_den;
+    J.gap_abs = p->gap_abs;
+    J.gap_rel = p->gap_rel;
+    J.pts = (const float4*)d_xyzi;
+    J.mask = d_mask;
+    J.pairs = (const VisPair*)(blk + b_img);
+    J.scans = (const VisScan*)(blk + b_img + b_pairs);
+    J.tiles = (const StackTile*)(blk + b_img + b_pairs + b_scans);
+    J.n_tiles = (int32_t)n_tiles;
+    J.images = images;
+    J.votes = o.d_votes;
+    J.verdict = o.d_verdict;
+    J.scan_counts = (unsigned long long*)o.d_scan_counts;
+    J.counters = c->vis_counters;
+    launch_vis_image(J, st);
+    if (!images_only) launch_vis_vote(J, st);
+    HIPCHK(c, hipGetLastError());
+    return SCVOD_OK;
+}
+
+int scvod_visibility_device(scvod_ctx* c, const void* d_xyzi, const int32_t* h_scan_offsets, int32_t n_scans, const float* h_poses,
+                            const int32_t* h_next_scan, const uint8_t* d_query_mask, const scvod_visibility_params* params, uint32_t* d_votes,
+                            uint8_t* d_verdict, float* d_images, int64_t* d_scan_counts, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_scans < 0 || (n_scans > 0 && !h_scan_offsets)) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    const VisOut o = {d_votes, d_verdict, d_images, d_scan_counts};
+    if (int rc = vis_check(c, params, o)) return rc;
+    if (n_scans > 0 && h_scan_offsets[0] < 0) return fail(c, SCVOD_ERR_INVALID, "scan offsets must not start below 0");
+    for (int s = 0; s < n_scans; ++s)
+        if (h_scan_offsets[s + 1] < h_scan_offsets[s]) return fail(c, SCVOD_ERR_INVALID, "scan offsets decrease at scan %d", s);
+    std::vector<int32_t> begin, viewers;
+    if (vis_viewers(h_next_scan, n_scans, params->before, params->after, begin, viewers))
+        return fail(c, SCVOD_ERR_INVALID, "visibility: h_next_scan names a scan outside the batch, a scan itself, one successor twice or a ring");
+    const bool any = n_scans > 0 && h_scan_offsets[n_scans] > h_scan_offsets[0];
+    if (any && !d_xyzi) return fail(c, SCVOD_ERR_INVALID, "NULL points of a cloud that is not empty");
+    if ((uintptr_t)d_xyzi & 15u) return fail(c, SCVOD_ERR_INVALID, "d_xyzi is not 16-byte aligned");
+    return vis_run(c, d_xyzi, h_scan_offsets, n_scans, h_poses, begin, viewers, d_query_mask, false, params, o, stream ? (hipStream_t)stream : c->stream);
+}
+
+int scvod_batch_visibility(scvod_ctx* c, const float* h_poses, const int32_t* h_next_scan, const scvod_visibility_params* params, int32_t flags,
+                           uint32_t* d_votes, uint8_t* d_verdict, float* d_images, int64_t* d_scan_counts, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    const VisOut o = {d_votes, d_verdict, d_images, d_scan_counts};
+    if (int rc = vis_check(c, params, o)) return rc;
+    if (flags & ~(SCVOD_VIS_WITH_GROUND | SCVOD_VIS_IMAGES_ONLY))
+        return fail(c, SCVOD_ERR_INVALID, "scvod_batch_visibility: flags %d: SCVOD_VIS_WITH_GROUND and SCVOD_VIS_IMAGES_ONLY are known", flags);
+    const bool images_only = (flags & SCVOD_VIS_IMAGES_ONLY) != 0;
+    if (images_only && (d_votes || d_verdict || d_scan_counts)) return fail(c, SCVOD_ERR_INVALID, "SCVOD_VIS_IMAGES_ONLY writes the range images only");
+    const bool all = images_only || (flags & SCVOD_VIS_WITH_GROUND) != 0;
+    if (!c->batch_valid || c->batch_mode == 3 || !c->A.pts)
+        return fail(c, SCVOD_ERR_STATE, "scvod_batch_visibility needs a processed batch of input clouds");
+    if (!all && !c->have_patchwork) return fail(c, SCVOD_ERR_STATE, "the last batch ran without Patchwork: it has no non-ground list (SCVOD_VIS_WITH_GROUND asks every point)");
+    const int B = c->A.n_scans;
+    std::vector<int32_t> begin, viewers;
+    if (vis_viewers(h_next_scan, B, params->before, params->after, begin, viewers))
+        return fail(c, SCVOD_ERR_INVALID, "visibility: h_next_scan names a scan outside the batch, a scan itself, one successor twice or a ring");
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    return vis_run(c, c->A.pts, c->h_scan_off.data(), B, h_poses, begin, viewers, nullptr, !all, params, o, st, images_only);
+}
+
+int scvod_visibility_stats(scvod_ctx* c, int64_t* h_out8) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->vis.ran) return fail(c, SCVOD_ERR_STATE, "scvod_visibility_stats before the first vote");
+    if (int rc = read_counters(c, c->vis_counters, 8, c->vis.stream, h_out8)) return rc;
+    h_out8[6] = h_out8[2] + h_out8[3] + h_out8[4] + h_out8[5];
+    h_out8[7] = 0;
+    return SCVOD_OK;
+}
+
+int64_t scvod_visibility_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)(c->vis.cap + (c->vis_counters ? 8 * sizeof(unsigned long long) : 0)) : 0; }
 
 // ---- a map split by nearest-neighbour hits (scvod_split.hip) ----
 void scvod_split_params_default(scvod_split_params* p) {

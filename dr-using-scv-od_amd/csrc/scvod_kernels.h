@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/scvod.h"
 #include "scvod_math.h"
 
@@ -329,6 +331,46 @@ struct StackTile {
 };
 void launch_stack(const StackSeg* segs, const StackTile* tiles, int n_tiles, const float4* in, float4* out, const uint32_t* payload_in,
                   uint32_t* payload_out, int32_t* src_out, hipStream_t st);
+
+// seen-through points (scvod_visibility_device / scvod_batch_visibility; scvod_visibility.hip): the host lists the kStackTile-point tiles
+// of the non-empty scans, the scans and the (scan, viewer) pairs with their matrices; a workgroup owns one tile of ONE scan, so the
+// image base and every matrix are uniform over it.  All tables live in scratch of their own (not the arena).
+struct VisPair {        // 64 bytes
+    float T[12];        // row-major 3x4: the query scan's frame -> the viewer's frame
+    int32_t viewer;     // the viewer's scan (its image)
+    int32_t pad[3];
+};
+struct VisScan {        // 16 bytes
+    int32_t base;       // first record of the scan in the cloud
+    int32_t n;          // records
+    int32_t pair_begin; // first of its pairs in the pair table
+    int32_t n_pairs;    // viewers
+};
+struct VisJob {
+    BinParams bin;
+    BinFast binfast;
+    KeepFast keep;
+    int32_t halo, min_through, vote_num, vote_den;
+    float gap_abs, gap_rel;
+    const float4* pts;
+    const uint8_t* mask;               // per point, or nullptr: every point is a query
+    const VisScan* scans;
+    const VisPair* pairs;
+    const StackTile* tiles;            // {scan, first record of the tile inside it}
+    int32_t n_tiles;
+    float* images;                     // [n_scans][azimuth_num * sector_num]
+    uint32_t* votes;                   // per point or nullptr
+    uint8_t* verdict;                  // per point or nullptr
+    unsigned long long* scan_counts;   // [n_scans][6] or nullptr
+    unsigned long long* counters;      // [8]: the six sums
+};
+void launch_vis_image(const VisJob& J, hipStream_t st);
+void launch_vis_vote(const VisJob& J, hipStream_t st);
+// mask[scan_off[s] + nonground_idx[..]] = 1 for the non-ground list of every scan of the batch (the mask is cleared before)
+void launch_vis_mask(const Arena& A, uint8_t* mask, hipStream_t st);
+// host only: the stage's parameter check and the viewer lists (begin [n_scans + 1], viewers); SCVOD_OK or SCVOD_ERR_INVALID
+int vis_check_params(const scvod_visibility_params* p);
+int vis_viewers(const int32_t* h_next_scan, int n_scans, int before, int after, std::vector<int32_t>& begin, std::vector<int32_t>& viewers);
 
 // the clusters of a batch as an object table (scvod_batch_objects; scvod_objects.hip).  Tiles as in the export, over the APRI points of a
 // scan; per tile two words {objects, member points}, the first turned into its exclusive prefix inside the scan.  Scratch of its own (not

@@ -161,6 +161,20 @@ MAPF_OUTPUTS = ("result", "side", "order", "bounds", "xyzi", "payload", "votes")
 MAP_FILTER_STATS = ("points", "known", "novel", "out", "moved_to_known", "moved_to_novel", "objects_voted", "objects_known")
 
 
+class VisibilityParams(C.Structure):
+    """scvod_visibility_params (include/scvod.h), 32 bytes"""
+    _fields_ = [("before", C.c_int32), ("after", C.c_int32), ("halo", C.c_int32), ("gap_abs", C.c_float), ("gap_rel", C.c_float),
+                ("min_through", C.c_int32), ("vote_num", C.c_int32), ("vote_den", C.c_int32)]
+
+
+VIS_UNTESTED, VIS_KEEP, VIS_SEEN_THROUGH = 0, 1, 2   # SCVOD_VIS_*: the verdict byte
+VIS_WITH_GROUND = 1                                   # SCVOD_VIS_WITH_GROUND
+VIS_IMAGES_ONLY = 2                                   # SCVOD_VIS_IMAGES_ONLY
+VIS_MAX_WINDOW = 32                                   # SCVOD_VIS_MAX_WINDOW
+VIS_OUTPUTS = ("votes", "verdict", "images", "scan_counts")
+VIS_STATS = ("queries", "seen_through", "through", "agree", "occluded", "outside_or_empty", "pairs")
+
+
 class SplitParams(C.Structure):
     """struct scvod_split_params (include/scvod.h)"""
     _fields_ = [("cell", C.c_float), ("max_rings", C.c_int32), ("base_stride", C.c_int32), ("query_stride", C.c_int32),
@@ -377,6 +391,12 @@ def load_lib():
         "scvod_batch_stack_scans": (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
         "scvod_stack_scans": (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, vp, i64]),
         "scvod_stack_scratch_bytes": (i64, [vp]),
+        "scvod_visibility_params_default": (None, [C.POINTER(VisibilityParams)]),
+        "scvod_visibility_viewers": (C.c_int, [vp, i32, i32, i32, vp, vp, i32]),
+        "scvod_visibility_device": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, C.POINTER(VisibilityParams), vp, vp, vp, vp, vp]),
+        "scvod_batch_visibility": (C.c_int, [vp, vp, vp, C.POINTER(VisibilityParams), i32, vp, vp, vp, vp, vp]),
+        "scvod_visibility_stats": (C.c_int, [vp, vp]),
+        "scvod_visibility_scratch_bytes": (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # raises AttributeError if a declared symbol is not exported
@@ -415,6 +435,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_object_truth_params_default", "scvod_object_truth_finish",
                     "scvod_stack_offsets", "scvod_pose_from_matrix", "scvod_batch_stack_scans", "scvod_stack_scans",
                     "scvod_stack_scratch_bytes",
+                    "scvod_visibility_params_default", "scvod_visibility_viewers", "scvod_visibility_device", "scvod_batch_visibility",
+                    "scvod_visibility_stats", "scvod_visibility_scratch_bytes",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
                     "scvod_map_split"]
 
@@ -558,6 +580,31 @@ def instance_merge(a, b):
                                             b.ctypes.data_as(C.c_void_p) if b.size else None, b.size,
                                             out.ctypes.data_as(C.c_void_p) if out.size else None, out.size, C.byref(n)), "scvod_instance_merge")
     return out[:n.value].copy()
+
+
+def visibility_params_default(**kw):
+    """scvod_visibility_params with the defaults (2 viewers on each side, halo 0, gap 0.4 m + 2 %, min_through 2, vote 1 / 2),
+    overridden by keyword"""
+    p = VisibilityParams()
+    load_lib().scvod_visibility_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def visibility_viewers(n_scans, next_scan=None, before=2, after=2):
+    """the viewer lists of the vote (host only): (begin [n_scans + 1], viewers): per scan the successors along next_scan, nearest first,
+    then the predecessors"""
+    nx = None if next_scan is None else np.ascontiguousarray(next_scan, np.int32)
+    assert nx is None or nx.shape[0] == n_scans
+    begin = np.zeros(int(n_scans) + 1, np.int32)
+    cap = max(int(n_scans) * (int(before) + int(after)), 1) if 0 <= before <= 64 and 0 <= after <= 64 else 1
+    viewers = np.zeros(cap, np.int32)
+    n = load_lib().scvod_visibility_viewers(None if nx is None else nx.ctypes.data_as(C.c_void_p), int(n_scans), int(before), int(after),
+                                            begin.ctypes.data_as(C.c_void_p), viewers.ctypes.data_as(C.c_void_p), cap)
+    _status(min(n, 0), "scvod_visibility_viewers")
+    return begin, viewers[:n]
 
 
 def split_params_default(cell=None, max_rings=None, base_stride=None, query_stride=None, reject_classes=None):
@@ -1411,6 +1458,64 @@ class Ctx:
     def stack_scratch_bytes(self):
         """device scratch the stacking holds on this ctx (0 before the first batch_stack_scans)"""
         return int(self.lib.scvod_stack_scratch_bytes(self.h))
+
+    # ---- seen-through points (include/scvod.h: scvod_visibility_device) ----
+    def _visibility_outputs(self, n, n_scans, want):
+        """the device tensors a vote writes, by name (VIS_OUTPUTS), and the four pointers in the C order"""
+        import torch
+        want = VIS_OUTPUTS if want is None else tuple(want)
+        assert all(w in VIS_OUTPUTS for w in want), want
+        _, S, A, _ = grid_dims(self.params)
+        dev = torch.device("cuda", self.device)
+        shape = {"votes": ((n,), torch.int32), "verdict": ((n,), torch.uint8), "images": ((n_scans, A, S), torch.float32),
+                 "scan_counts": ((n_scans, 6), torch.int64)}
+        out = {w: torch.empty(shape[w][0], dtype=shape[w][1], device=dev) for w in want}
+        return out, [C.c_void_p(out[w].data_ptr()) if w in out else None for w in VIS_OUTPUTS]
+
+    def visibility_device(self, d_xyzi, scan_offsets, poses=None, next_scan=None, params=None, d_query_mask=None,
+                          want=("votes", "verdict"), stream=None):
+        """scvod_visibility_device of the caller's cloud (torch float32 [n, 4] on the ctx's device): a dict of device tensors, one per
+        name in `want` (VIS_OUTPUTS; None: all) -- votes int32 [n] (the bits of the uint32: bytes n_through, n_agree, n_occluded,
+        n_outside + n_empty), verdict uint8 [n] (VIS_*), images float32 [n_scans, A, S], scan_counts int64 [n_scans, 6].  Rows are at
+        the input index, so the offsets should start at 0.  d_query_mask: torch uint8 [n] or None (every point).  Stream-ordered."""
+        off = np.ascontiguousarray(scan_offsets, np.int32)
+        n_scans = len(off) - 1
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == n_scans
+        nx = None if next_scan is None else np.ascontiguousarray(next_scan, np.int32)
+        assert nx is None or nx.shape[0] == n_scans
+        prm = params if params is not None else visibility_params_default()
+        out, ptr = self._visibility_outputs(int(off[-1]) if len(off) else 0, n_scans, want)
+        self._chk(self.lib.scvod_visibility_device(self.h, C.c_void_p(d_xyzi.data_ptr()), off.ctypes.data_as(C.c_void_p), n_scans,
+                                                   None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                   None if nx is None else nx.ctypes.data_as(C.c_void_p),
+                                                   None if d_query_mask is None else C.c_void_p(d_query_mask.data_ptr()), C.byref(prm),
+                                                   *ptr, C.c_void_p(stream or 0)))
+        return out
+
+    def batch_visibility(self, poses, next_scan=None, params=None, flags=0, want=("votes", "verdict"), stream=None):
+        """scvod_batch_visibility: the same for the input cloud of the last batch; queries are Patchwork's non-ground points, or every
+        input point with flags=VIS_WITH_GROUND"""
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == self._n_scans
+        nx = None if next_scan is None else np.ascontiguousarray(next_scan, np.int32)
+        assert nx is None or nx.shape[0] == self._n_scans
+        prm = params if params is not None else visibility_params_default()
+        out, ptr = self._visibility_outputs(int(self._n_pts), self._n_scans, want)
+        self._chk(self.lib.scvod_batch_visibility(self.h, None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                  None if nx is None else nx.ctypes.data_as(C.c_void_p), C.byref(prm), int(flags), *ptr,
+                                                  C.c_void_p(stream or 0)))
+        return out
+
+    def visibility_stats(self):
+        """{queries, seen_through, through, agree, occluded, outside_or_empty, pairs} of the last vote (synchronises its stream)"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_visibility_stats(self.h, o))
+        return dict(zip(VIS_STATS, (int(v) for v in o[:7])))
+
+    def visibility_scratch_bytes(self):
+        """device scratch the vote holds on this ctx (0 before the first call)"""
+        return int(self.lib.scvod_visibility_scratch_bytes(self.h))
 
     def voxelgrid(self, xyzi, leaf=(0.08, 0.08, 0.08), labels=None, max_intensity=1.0):
         """SSC::getCloud label filter + pcl::VoxelGrid of one host scan (ssc.cpp:1063-1076, 1103-1106)."""

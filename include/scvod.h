@@ -1357,6 +1357,102 @@ int scvod_stack_scans(scvod_ctx* ctx, const float* h_xyzi_in, const int32_t* h_i
 /* bytes of device scratch the stacking holds on this ctx (0 before the first call) */
 int64_t scvod_stack_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- seen-through points: the range-image vote of neighbouring scans, on the device (opt-in: nothing runs or is allocated unless it
+ * is called) ---------------------------------------------------------------------------------------------------------------------------
+ * Reference analogue: none.  THIS PROJECT'S CONVENTION: SSC::tracking decides "dynamic" for car-typed clusters
+ * only; this stage adds free-space evidence for ANY point.  If a neighbouring scan measures a return well behind the place where this
+ * scan saw a point, a ray passed through that place and it was empty then.
+ *
+ * Grid and depth: the ctx's own binning.  A pixel is (azimuth_idx, sector_idx), A = azimuth_num rows by S = sector_num columns; the
+ * depth is PointAPRI::range, the 2-D distance `dis` of SSC::makeApriVec.  The range image of scan s, img[s][ai * S + si], is the
+ * minimum `dis` over the scan's input points whose x, y, z are finite, which pass makeApriVec's range / FOV test and whose indices lie
+ * in 0 <= si < S, 0 <= ai < A.  EVERY input point takes part, ground and Patchwork-dropped ones included: a ray that ends on the road
+ * behind an object is evidence.  A pixel without such a point holds +inf (0x7F800000).  The image is an integer minimum over the float
+ * bits: order-independent, the same on every run.
+ *
+ * Viewers of scan j: up to `after` successors along h_next_scan (the table of scvod_batch_track: NULL means s + 1, and the last scan has
+ * none; a negative entry -- none, or an external table -- ends the chain inside the batch) and up to `before` predecessors along the
+ * inverse of that table.  Scans at the ends of a chain have fewer viewers; interleaved chains follow from the table.  A table in which
+ * two scans name one successor, a scan names itself, the chain closes into a ring, or an entry is >= n_scans is refused.
+ *
+ * One pair (query point q of scan j, viewer s): T = scvod_pose_delta(pose_j, pose_s) moves a point of j's frame into s's frame
+ * (trans_s^-1 * trans_j); p' = T q with T0*x + T1*y + T2*z + T3 per row, left to right in fp32 without contraction (the map, export and
+ * stack kernels' expression); dis', si, ai and keep are makeApriVec's of p'.  The pair's class is the first that applies:
+ *   OUTSIDE   p' is not finite, keep == 0, or an index lies outside the image
+ *   otherwise, over the window [ai - halo, ai + halo] x [si - halo, si + halo] clipped to the image -- NO wrap across the sector seam
+ *   (the reference's neighbourhoods do not wrap there either) -- with gap = gap_abs + gap_rel * dis' (fp32, two operations) and r_min
+ *   the minimum of the window:
+ *   EMPTY     r_min == +inf
+ *   THROUGH   r_min > dis' + gap (strict: every return of the window lies behind the point)
+ *   AGREE     some pixel r of the window has fabsf(r - dis') <= gap
+ *   OCCLUDED  otherwise
+ * Per query point one uint32 of four byte counters: byte 0 n_through, byte 1 n_agree, byte 2 n_occluded, byte 3 n_outside + n_empty;
+ * they sum to the viewer count of the point's scan.  A point that is no query gets 0.  The verdict byte:
+ *   SCVOD_VIS_UNTESTED      not a query, or a scan without viewers
+ *   SCVOD_VIS_SEEN_THROUGH  n_through >= min_through && n_through * vote_den >= vote_num * (n_through + n_agree), in int
+ *   SCVOD_VIS_KEEP          every other query
+ * The intended use: scvod_batch_visibility, then scvod_map_accumulate_labelled with the verdict bytes as labels and a keep table that
+ * holds everything but SCVOD_VIS_SEEN_THROUGH. */
+#define SCVOD_VIS_UNTESTED 0
+#define SCVOD_VIS_KEEP 1
+#define SCVOD_VIS_SEEN_THROUGH 2
+#define SCVOD_VIS_WITH_GROUND 1 /* scvod_batch_visibility: every input point is a query, not only Patchwork's non-ground list */
+#define SCVOD_VIS_IMAGES_ONLY 2 /* scvod_batch_visibility: the range images only (into d_images or the scratch): no vote, no other output */
+#define SCVOD_VIS_MAX_WINDOW 32 /* viewers on each side */
+typedef struct scvod_visibility_params { /* 32 bytes */
+    int32_t before, after; /* viewers on each side: 0..SCVOD_VIS_MAX_WINDOW each, not both 0 */
+    int32_t halo;          /* 0 or 1: the window is (2 halo + 1)^2 pixels                    */
+    float gap_abs;         /* metres, >= 0 and finite                                        */
+    float gap_rel;         /* per metre of dis', >= 0 and finite                             */
+    int32_t min_through;   /* any value                                                      */
+    int32_t vote_num;      /* 0 .. 1 << 20                                                   */
+    int32_t vote_den;      /* 1 .. 1 << 20                                                   */
+} scvod_visibility_params;
+/* before = after = 2, halo 0, gap_abs 0.4f, gap_rel 0.02f, min_through 2, vote 1 / 2.  These values come from a float64 prototype of
+ * the rule on the synthetic scans of this repository, NOT from real data. */
+void scvod_visibility_params_default(scvod_visibility_params* p);
+/* Host only, no device: the viewer lists the two calls below use.  h_next_scan [n_scans] or NULL.  h_begin [n_scans + 1] receives the
+ * first viewer of every scan in h_viewers [cap]: per scan the successors, nearest first, then the predecessors, nearest first.  Either
+ * array may be NULL (count only).  Returns the number of (scan, viewer) pairs, SCVOD_ERR_INVALID for n_scans < 0, a window outside
+ * 0..SCVOD_VIS_MAX_WINDOW or 0 on both sides, or a table refused above, SCVOD_ERR_CAPACITY when h_viewers is too small. */
+int scvod_visibility_viewers(const int32_t* h_next_scan, int32_t n_scans, int32_t before, int32_t after, int32_t* h_begin,
+                             int32_t* h_viewers, int32_t cap);
+/* The vote on any cloud of 16-byte records resident in HBM.  d_xyzi, h_scan_offsets [n_scans + 1] and h_poses [n_scans][6] as
+ * scvod_map_query takes them (NULL poses: the zero pose for every scan; offsets ascending, starting at or above 0); every per-point
+ * array is indexed like d_xyzi.  d_query_mask: one byte per point, != 0 is a query; NULL: every point.  Outputs, each may be NULL:
+ *   d_votes       one uint32 per point (the four byte counters)
+ *   d_verdict     one byte per point
+ *   d_images      [n_scans][A * S] floats, the range images; without it they live in the stage's scratch
+ *   d_scan_counts [n_scans][6] int64 {queries, SEEN_THROUGH, pairs THROUGH, AGREE, OCCLUDED, OUTSIDE + EMPTY}
+ * Stream-ordered (stream NULL = the ctx's stream), never synchronises with the host; h_scan_offsets, h_poses and h_next_scan are
+ * turned into tile, scan and pair tables -- the matrices of all (scan, viewer) pairs come from scvod_pose_delta on the host -- and
+ * staged before the call returns.  The call touches neither the arena nor any batch state.  Integer counts and minima only: every
+ * output is bit-identical from run to run.  Each call overwrites the stats of the one before, and the calls of one ctx must be
+ * ordered among themselves (they share their scratch).  Argument errors (NULL ctx or params, n_scans < 0, NULL offsets with
+ * n_scans > 0, offsets that decrease or start below 0, a window outside 0..32 or 0 on both sides, halo outside 0..1, vote_den outside
+ * 1 .. 1 << 20, vote_num outside 0 .. 1 << 20, a negative or non-finite gap, a successor table refused above, a NULL cloud that is not
+ * empty, d_xyzi or d_images not 16-byte, d_votes not 4-byte, d_scan_counts not 8-byte aligned) are SCVOD_ERR_INVALID before any device
+ * is looked for.  Scratch (4 A S bytes per scan for the images unless d_images is given -- 72 KB per scan of the SemanticKITTI grid,
+ * 288 KB of the OS1-128 grid --, 64 bytes per (scan, viewer) pair, 16 bytes per scan, 8 bytes per 2048-point tile, in the batch form a
+ * mask byte per point, 8 counter words) is a grow-only allocation of its own, freed by scvod_destroy and NOT part of
+ * scvod_arena_bytes; a call that needs more than any before waits for the one in flight before it grows. */
+int scvod_visibility_device(scvod_ctx* ctx, const void* d_xyzi, const int32_t* h_scan_offsets, int32_t n_scans, const float* h_poses,
+                            const int32_t* h_next_scan, const uint8_t* d_query_mask, const scvod_visibility_params* params,
+                            uint32_t* d_votes, uint8_t* d_verdict, float* d_images, int64_t* d_scan_counts, void* stream);
+/* The same for the input cloud of the ctx's last batch.  Queries are the points of Patchwork's non-ground list (the three index lists
+ * are written first when a lean batch left them out; a mask is scattered into the stage's scratch), or with SCVOD_VIS_WITH_GROUND
+ * every input point.  Needs scvod_batch_process only (with Patchwork, unless SCVOD_VIS_WITH_GROUND; on an input cloud), otherwise
+ * SCVOD_ERR_STATE: clustering, types and tracking are not needed and not touched.  h_poses [n_scans][6] (NULL: the zero pose).
+ * With SCVOD_VIS_IMAGES_ONLY the call stops after the range images: d_votes, d_verdict and d_scan_counts must be NULL, no list is
+ * needed, and the stats of the call are all 0.  Stream NULL = the stream of the ctx's last batch call. */
+int scvod_batch_visibility(scvod_ctx* ctx, const float* h_poses, const int32_t* h_next_scan, const scvod_visibility_params* params,
+                           int32_t flags, uint32_t* d_votes, uint8_t* d_verdict, float* d_images, int64_t* d_scan_counts, void* stream);
+/* h_out8 = {queries, SEEN_THROUGH, pairs THROUGH, AGREE, OCCLUDED, OUTSIDE + EMPTY, (query, viewer) pairs, 0} of the last vote.
+ * Synchronises that call's stream.  SCVOD_ERR_STATE before the first call. */
+int scvod_visibility_stats(scvod_ctx* ctx, int64_t* h_out8);
+/* bytes of device scratch the vote holds on this ctx (0 before the first call) */
+int64_t scvod_visibility_scratch_bytes(scvod_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
