@@ -159,7 +159,8 @@ __global__ __launch_bounds__(256) void k_tk_probe(DevParams P, Arena A, TrackBat
         }
         int4 first[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) first[u] = N.tab[min(max(lo[u] - 1, 0) << shift, max(N.nv - 1, 0))];
+        for (int u = 0; u < U; ++u)  // (a table of no voxels may end behind its header: nothing to read, lo stays 0)
+            first[u] = N.nv > 0 ? N.tab[min(max(lo[u] - 1, 0) << shift, N.nv - 1)] : make_int4(0, -1, 0, 0);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int k = k0 + u * 256 + (int)threadIdx.x;
@@ -192,9 +193,11 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 
 // One WAVE per car cluster (persistent over the clusters of its scan), no workgroup barriers: a private bitset over the
 // successor's table in LDS turns the cluster's hits into the sorted unique list (sampleVec without a sort), the list is
-// grouped by label -> remap_name, then the state rule.  `words` = LDS words per wave (covers the largest table).
+// grouped by label -> remap_name, then the state rule.  `words` = LDS words per wave (covers the largest table of the batch).
+// `rest` (the last launch of the ladder): a table of more than 32 * words voxels -- an external one, from a shard whose scans
+// are larger than any of this batch -- is decided here too, its unique lists by selection from tk_hit instead of the bitset.
 template <int kTkWaves>
-__global__ __launch_bounds__(64 * kTkWaves) void k_tk_decide(Arena A, TrackBatch J, int words, int min_words) {
+__global__ __launch_bounds__(64 * kTkWaves) void k_tk_decide(Arena A, TrackBatch J, int words, int min_words, int rest) {
     extern __shared__ uint32_t tk_bits[];
     const int s = blockIdx.y;
     const int ncl = A.tk_scan[s * 4 + 0];
@@ -206,16 +209,18 @@ __global__ __launch_bounds__(64 * kTkWaves) void k_tk_decide(Arena A, TrackBatch
     const int base = A.scan_off[s];
     uint32_t* bits = tk_bits + (size_t)wave * words;
     // two launches share the scans: tables of up to `words` bitset words here, larger ones in the launch with more LDS per wave
-    if (((N.nv + 31) >> 5) > words || ((N.nv + 31) >> 5) <= min_words) return;
     const int nw = (N.nv + 31) >> 5;
-    for (int w = lane; w < nw; w += 64) bits[w] = 0u;
+    const bool oversize = nw > words;  // no launch has a bitset for it
+    if (nw <= min_words || (oversize && !rest)) return;
+    if (!oversize)
+        for (int w = lane; w < nw; w += 64) bits[w] = 0u;
     __builtin_amdgcn_wave_barrier();
     for (int ord = first; ord < ncl; ord += stride) {
         const int root = A.tk_clusters[(size_t)base + ord];
         const int k0 = A.tk_mbegin[(size_t)base + root];
         const int m = A.cl_count[(size_t)base + root];
         int wlo = 0x7fffffff, whi = -1;
-        for (int j = lane; j < m; j += 64) {
+        for (int j = lane; j < m && !oversize; j += 64) {
             const int slot = A.tk_hit[(size_t)base + k0 + j];
             if (slot >= 0 && (slot >> 5) < nw) {
                 atomicOr(&bits[slot >> 5], 1u << (slot & 31));
@@ -243,6 +248,20 @@ __global__ __launch_bounds__(64 * kTkWaves) void k_tk_decide(Arena A, TrackBatch
                 A.tk_uniq[(size_t)base + o++] = (w << 5) + b;
             }
             U += __shfl(inc, 63);
+        }
+        if (oversize) {  // the same list without a bitset: the smallest slot above the last one, one pass over the cluster's hits each
+            for (int cur = -1;;) {
+                int mn = 0x7fffffff;
+                for (int j = lane; j < m; j += 64) {
+                    const int slot = A.tk_hit[(size_t)base + k0 + j];
+                    if (slot > cur && slot < N.nv) mn = min(mn, slot);
+                }
+                mn = wave_min_i(mn);
+                if (mn == 0x7fffffff) break;
+                if (lane == 0) A.tk_uniq[(size_t)base + k0 + U] = mn;
+                ++U;
+                cur = mn;
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -376,27 +395,25 @@ void launch_track_batch(const DevParams& P, const Arena& A, const TrackBatch& J,
     const int words = (A.max_scan_pts + 31) / 32 + 1;  // SCVOD_MAX_SCAN_POINTS = 2^19 slots = 64 KB: one wave always fits
     const size_t per_wave = (size_t)words * 4;
     TH_BEGIN("tk_decide");
-    hipLaunchKernelGGL(k_tk_decide<4>, dim3(8, B), dim3(256), 4 * small_words * 4, st, A, J, small_words, -1);
+    // (the last launch of the ladder also takes the tables beyond `words`: external ones, whose size only the device knows)
+    hipLaunchKernelGGL(k_tk_decide<4>, dim3(8, B), dim3(256), 4 * small_words * 4, st, A, J, small_words, -1, words <= small_words ? 1 : 0);
     // (a 128-beam scan on a fine grid: 70 k voxels in a batch sized for 260 k points) tables of up to 81 920 voxels: 10 KB per wave,
     // four workgroups per CU; up to 131 072 voxels: 16 KB per wave, two workgroups per CU
     int done_words = small_words;
     for (const int mid_words : {2560, 4096}) {
         if (words <= mid_words) break;
         hipFuncSetAttribute((const void*)k_tk_decide<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * mid_words * 4);
-        hipLaunchKernelGGL(k_tk_decide<4>, dim3(8, B), dim3(256), 4 * mid_words * 4, st, A, J, mid_words, done_words);
+        hipLaunchKernelGGL(k_tk_decide<4>, dim3(8, B), dim3(256), 4 * mid_words * 4, st, A, J, mid_words, done_words, 0);
         done_words = mid_words;
     }
     if (words > small_words) {
-        const int small_words = done_words;  // (the launches below take the tables beyond what is done)
+        const int small_words = done_words;  // (the launch below takes the tables beyond what is done)
         if (4 * per_wave <= 64 * 1024) {  // two workgroups per CU
             hipFuncSetAttribute((const void*)k_tk_decide<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * per_wave));
-            hipLaunchKernelGGL(k_tk_decide<4>, dim3(8, B), dim3(256), 4 * per_wave, st, A, J, words, small_words);
-        } else if (2 * per_wave <= 150 * 1024) {
+            hipLaunchKernelGGL(k_tk_decide<4>, dim3(8, B), dim3(256), 4 * per_wave, st, A, J, words, small_words, 1);
+        } else {  // two waves always fit: per_wave <= 4 * (SCVOD_MAX_SCAN_POINTS / 32 + 1) = 65 540 bytes
             hipFuncSetAttribute((const void*)k_tk_decide<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * per_wave));
-            hipLaunchKernelGGL(k_tk_decide<2>, dim3(16, B), dim3(128), 2 * per_wave, st, A, J, words, small_words);
-        } else {
-            hipFuncSetAttribute((const void*)k_tk_decide<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)per_wave);
-            hipLaunchKernelGGL(k_tk_decide<1>, dim3(32, B), dim3(64), per_wave, st, A, J, words, small_words);
+            hipLaunchKernelGGL(k_tk_decide<2>, dim3(16, B), dim3(128), 2 * per_wave, st, A, J, words, small_words, 1);
         }
     }
     TH_END("tk_decide");

@@ -278,7 +278,10 @@ int scvod_set_voxel_descriptors(scvod_ctx* ctx, int32_t mode);
  *   h_next_scan  [n_scans] or NULL: successor of scan s -- an index of the batch, -1 = none (last scan of a sequence),
  *                -2 - e = the external table e.  NULL: s + 1, none for the last scan.
  *   h_ext_tables [n_ext] device pointers to tables written by scvod_batch_export_table on ANOTHER shard (the first scan of
- *                the next block of the sequence): how a block's last scan is tracked across a shard boundary.
+ *                the next block of the sequence): how a block's last scan is tracked across a shard boundary.  A table may
+ *                hold any number of voxels, 0 included (every car cluster tracked against it is then dynamic, and nothing
+ *                behind its header is read); it need not fit the scans of THIS batch: one with more voxels than the batch's
+ *                largest scan has points is decided all the same, by a slower path without the per-wave LDS bitset.
  * Per cluster: the transformed points are re-binned without range/FOV rejection (ssc.cpp:1280-1286) and looked up in the
  * successor's table; hits are grouped by label and de-duplicated (remap_name, ssc.cpp:1304-1321); Cluster::state follows
  * ssc.cpp:1323-1397, first against the successor in its freshly segmented state (all pairs in parallel), then -- mode
