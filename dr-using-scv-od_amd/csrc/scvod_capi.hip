@@ -231,6 +231,11 @@ struct scvod_ctx {
     Scratch vis;  // stream / ran: the last vote (scvod_visibility_stats waits for it)
     unsigned long long* vis_counters = nullptr;
     std::vector<unsigned char> vis_host;  // the tables as built on the host (scratch of the call; the upload is staged from a copy)
+    // a cloud against every scan's range image (scvod_cloud_visibility_device, scvod_cloudvis.hip): a grow-only block (matrices, the
+    // sort's keys, indices and temporary storage) and 10 counter words of their own, allocated by the first call; not part of the arena
+    Scratch cv;  // stream / ran: the last call (scvod_cloud_visibility_stats waits for it)
+    unsigned long long* cv_counters = nullptr;
+    std::vector<float> cv_host;  // the matrices as built on the host
     std::vector<int32_t> tk_stage;    // host staging of scvod_batch_fetch_track
     // streaming ingest (scvod_sequence_ingest): two device chunk buffers, a copy stream, pinned offsets
     hipStream_t copy_stream = nullptr;
@@ -1559,6 +1564,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->stk.buf) hipFree(c->stk.buf);
     if (c->vis.buf) hipFree(c->vis.buf);
     if (c->vis_counters) hipFree(c->vis_counters);
+    if (c->cv.buf) hipFree(c->cv.buf);
+    if (c->cv_counters) hipFree(c->cv_counters);
     if (c->sp.buf) hipFree(c->sp.buf);
     if (c->sp_stats) hipFree(c->sp_stats);
     if (c->stage) hipHostFree(c->stage);
@@ -3936,6 +3943,91 @@ int scvod_visibility_stats(scvod_ctx* c, int64_t* h_out8) {
 }
 
 int64_t scvod_visibility_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)(c->vis.cap + (c->vis_counters ? 8 * sizeof(unsigned long long) : 0)) : 0; }
+
+// ---- a cloud against every scan's range image (scvod_cloudvis.hip) ----
+int scvod_cloud_visibility_device(scvod_ctx* c, const void* d_xyzi, int64_t n, const float* d_images, const float* h_poses, int32_t n_scans,
+                                  const scvod_cloud_visibility_params* params, int32_t flags, uint16_t* d_votes, uint8_t* d_verdict,
+                                  void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!params || n < 0 || n_scans < 0 || n_scans > 65535) return fail(c, SCVOD_ERR_INVALID, "bad arguments (n_scans 0..65535)");
+    if (cvis_check_params(params))
+        return fail(c, SCVOD_ERR_INVALID,
+                    "cloud visibility: halo %d 0 or 1, vote %d / %d with 0 <= num <= 1 << 20 and 1 <= den <= 1 << 20, gaps %g + %g * dis and max_range %g finite and >= 0, reserved %d 0",
+                    params->halo, params->vote_num, params->vote_den, (double)params->gap_abs, (double)params->gap_rel, (double)params->max_range,
+                    params->reserved);
+    if (flags & ~SCVOD_CVIS_NO_SORT) return fail(c, SCVOD_ERR_INVALID, "scvod_cloud_visibility_device: flags %d: SCVOD_CVIS_NO_SORT is known", flags);
+    if (n_scans > 0 && !d_images) return fail(c, SCVOD_ERR_INVALID, "NULL images of %d scans", n_scans);
+    if (n > 0 && !d_xyzi) return fail(c, SCVOD_ERR_INVALID, "NULL points of a cloud that is not empty");
+    if ((uintptr_t)d_xyzi & 15u) return fail(c, SCVOD_ERR_INVALID, "d_xyzi is not 16-byte aligned");
+    if ((uintptr_t)d_images & 15u) return fail(c, SCVOD_ERR_INVALID, "d_images is not 16-byte aligned");
+    if ((uintptr_t)d_votes & 7u) return fail(c, SCVOD_ERR_INVALID, "d_votes is not 8-byte aligned");
+    if (n > 2147483647ll) return fail(c, SCVOD_ERR_CAPACITY, "more than 2^31 - 1 points");
+    const BinParams& g = c->dev.bin;
+    if (g.azimuth_num <= 0 || g.sector_num <= 0) return fail(c, SCVOD_ERR_INVALID, "the ctx's grid has no pixels");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const bool sorted = !(flags & SCVOD_CVIS_NO_SORT) && n > 0;
+    // the block: [matrices][keys in, out][indices in, out][rocprim's temporary storage]
+    const size_t b_T = align_up(sizeof(float) * 12 * (size_t)n_scans, 256), b_n = sorted ? align_up(4 * (size_t)n, 256) : 0;
+    const size_t b_tmp = sorted ? align_up(cvis_sort_bytes(n), 256) : 0;
+    c->cv_host.assign(12 * (size_t)n_scans, 0.f);
+    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < n_scans; ++s) scvod_pose_delta(zero, h_poses ? h_poses + 6 * (size_t)s : zero, c->cv_host.data() + 12 * (size_t)s);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = counter_block(c, &c->cv_counters, 10)) return rc;
+    if (int rc = scratch_reserve(c, c->cv, b_T + 4 * b_n + b_tmp + 256)) return rc;  // (waits for the call in flight before the block moves)
+    unsigned char* blk = (unsigned char*)c->cv.buf;
+    c->cv.stream = st;
+    c->cv.ran = true;
+    HIPCHK(c, hipMemsetAsync(c->cv_counters, 0, 10 * sizeof(unsigned long long), st));
+    if (n == 0) return SCVOD_OK;
+    if (n_scans > 0)
+        if (int rc = staged_upload(c, c->cv_host.data(), sizeof(float) * 12 * (size_t)n_scans, blk, st)) return rc;
+    const uint32_t* order = nullptr;
+    if (sorted) {
+        uint32_t* key_in = (uint32_t*)(blk + b_T);
+        uint32_t* key_out = (uint32_t*)(blk + b_T + b_n);
+        uint32_t* idx_in = (uint32_t*)(blk + b_T + 2 * b_n);
+        uint32_t* idx_out = (uint32_t*)(blk + b_T + 3 * b_n);
+        launch_cvis_key((const float4*)d_xyzi, n, key_in, idx_in, st);
+        const hipError_t e = launch_cvis_sort(blk + b_T + 4 * b_n, b_tmp, key_in, key_out, idx_in, idx_out, n, st);
+        if (e != hipSuccess) return fail(c, SCVOD_ERR_HIP, "rocprim radix sort: %s", hipGetErrorString(e));
+        order = idx_out;
+    }
+    CvisJob J;
+    memset(&J, 0, sizeof(J));
+    J.V.bin = g;
+    J.V.binfast = c->dev.binfast;
+    J.V.keep = c->dev.keep;
+    J.V.halo = params->halo;
+    J.V.min_through = params->min_through;
+    J.V.vote_num = params->vote_num;
+    J.V.vote_den = params->vote_den;
+    J.V.gap_abs = params->gap_abs;
+    J.V.gap_rel = params->gap_rel;
+    J.max_range = params->max_range;
+    J.reach = params->max_range > 0.f && params->max_range < g.max_dis ? params->max_range : g.max_dis;
+    J.pts = (const float4*)d_xyzi;
+    J.n = n;
+    J.order = order;
+    J.T = (const float*)blk;
+    J.images = d_images;
+    J.n_scans = n_scans;
+    J.votes = d_votes;
+    J.verdict = d_verdict;
+    J.counters = c->cv_counters;
+    launch_cvis_vote(J, st);
+    HIPCHK(c, hipGetLastError());
+    return SCVOD_OK;
+}
+
+int scvod_cloud_visibility_stats(scvod_ctx* c, int64_t* h_out10) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out10) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->cv.ran) return fail(c, SCVOD_ERR_STATE, "scvod_cloud_visibility_stats before the first call");
+    return read_counters(c, c->cv_counters, 10, c->cv.stream, h_out10);
+}
+
+int64_t scvod_cloud_visibility_scratch_bytes(scvod_ctx* c) { return c ? (int64_t)(c->cv.cap + (c->cv_counters ? 10 * sizeof(unsigned long long) : 0)) : 0; }
 
 // ---- a map split by nearest-neighbour hits (scvod_split.hip) ----
 void scvod_split_params_default(scvod_split_params* p) {

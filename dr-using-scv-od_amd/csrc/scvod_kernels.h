@@ -372,6 +372,32 @@ void launch_vis_mask(const Arena& A, uint8_t* mask, hipStream_t st);
 int vis_check_params(const scvod_visibility_params* p);
 int vis_viewers(const int32_t* h_next_scan, int n_scans, int before, int after, std::vector<int32_t>& begin, std::vector<int32_t>& viewers);
 
+// a world-frame cloud against the range images of every scan (scvod_cloud_visibility_device; scvod_cloudvis.hip): the points are keyed by
+// a coarse world tile and sorted, a workgroup owns one chunk of kCvisChunk consecutive sorted points and walks all scans, skipping those
+// whose image no point of the chunk can lie in.  Scratch of its own (not the arena, not the scan stage's).
+constexpr int kCvisThreads = 64;                // one wave per chunk: its bound is as tight as 512 neighbouring points allow
+constexpr int kCvisChunk = 8 * kCvisThreads;    // 8 records per thread stay in registers, as in the scan stage's tile
+struct CvisJob {
+    VisJob V;                          // grid, window, gaps and vote rule as vis_pair reads them (the scan stage's pointers stay 0)
+    float max_range;                   // 0: the grid's max_dis alone
+    float reach;                       // min(max_dis, max_range): a pair with dis' beyond it is OUTSIDE
+    const float4* pts;                 // [n] world frame
+    long long n;
+    const uint32_t* order;             // [n] the sorted index list, or nullptr: the input order
+    const float* T;                    // [n_scans][12] world -> viewer
+    const float* images;               // [n_scans][azimuth_num * sector_num]
+    int32_t n_scans;
+    uint16_t* votes;                   // [n][4] or nullptr
+    uint8_t* verdict;                  // [n] or nullptr
+    unsigned long long* counters;      // [10] scvod_cloud_visibility_stats
+};
+size_t cvis_sort_bytes(long long n);   // rocprim's temporary storage for n (key, index) pairs
+void launch_cvis_key(const float4* pts, long long n, uint32_t* key, uint32_t* idx, hipStream_t st);
+hipError_t launch_cvis_sort(void* tmp, size_t tmp_bytes, const uint32_t* key_in, uint32_t* key_out, const uint32_t* idx_in, uint32_t* idx_out,
+                            long long n, hipStream_t st);
+void launch_cvis_vote(const CvisJob& J, hipStream_t st);
+int cvis_check_params(const scvod_cloud_visibility_params* p);  // host only: SCVOD_OK or SCVOD_ERR_INVALID
+
 // the clusters of a batch as an object table (scvod_batch_objects; scvod_objects.hip).  Tiles as in the export, over the APRI points of a
 // scan; per tile two words {objects, member points}, the first turned into its exclusive prefix inside the scan.  Scratch of its own (not
 // the arena): per point of the ctx's capacity unless stated.

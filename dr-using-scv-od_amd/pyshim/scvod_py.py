@@ -175,6 +175,17 @@ VIS_OUTPUTS = ("votes", "verdict", "images", "scan_counts")
 VIS_STATS = ("queries", "seen_through", "through", "agree", "occluded", "outside_or_empty", "pairs")
 
 
+class CloudVisibilityParams(C.Structure):
+    """scvod_cloud_visibility_params (include/scvod.h), 32 bytes"""
+    _fields_ = [("halo", C.c_int32), ("gap_abs", C.c_float), ("gap_rel", C.c_float), ("max_range", C.c_float), ("min_through", C.c_int32),
+                ("vote_num", C.c_int32), ("vote_den", C.c_int32), ("reserved", C.c_int32)]
+
+
+CVIS_NO_SORT = 1                                      # SCVOD_CVIS_NO_SORT
+CVIS_OUTPUTS = ("votes", "verdict")
+CVIS_STATS = ("points", "finite", "seen_through", "keep", "untested", "through", "agree", "occluded", "empty", "steps")
+
+
 class SplitParams(C.Structure):
     """struct scvod_split_params (include/scvod.h)"""
     _fields_ = [("cell", C.c_float), ("max_rings", C.c_int32), ("base_stride", C.c_int32), ("query_stride", C.c_int32),
@@ -397,6 +408,10 @@ def load_lib():
         "scvod_batch_visibility": (C.c_int, [vp, vp, vp, C.POINTER(VisibilityParams), i32, vp, vp, vp, vp, vp]),
         "scvod_visibility_stats": (C.c_int, [vp, vp]),
         "scvod_visibility_scratch_bytes": (i64, [vp]),
+        "scvod_cloud_visibility_params_default": (None, [C.POINTER(CloudVisibilityParams)]),
+        "scvod_cloud_visibility_device": (C.c_int, [vp, vp, i64, vp, vp, i32, C.POINTER(CloudVisibilityParams), i32, vp, vp, vp]),
+        "scvod_cloud_visibility_stats": (C.c_int, [vp, vp]),
+        "scvod_cloud_visibility_scratch_bytes": (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # raises AttributeError if a declared symbol is not exported
@@ -437,6 +452,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_stack_scratch_bytes",
                     "scvod_visibility_params_default", "scvod_visibility_viewers", "scvod_visibility_device", "scvod_batch_visibility",
                     "scvod_visibility_stats", "scvod_visibility_scratch_bytes",
+                    "scvod_cloud_visibility_params_default", "scvod_cloud_visibility_device", "scvod_cloud_visibility_stats",
+                    "scvod_cloud_visibility_scratch_bytes",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
                     "scvod_map_split"]
 
@@ -587,6 +604,17 @@ def visibility_params_default(**kw):
     overridden by keyword"""
     p = VisibilityParams()
     load_lib().scvod_visibility_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def cloud_visibility_params_default(**kw):
+    """scvod_cloud_visibility_params with the defaults (halo 0, gap 0.4 m + 2 %, max_range 0, min_through 2, vote 1 / 2: the scan
+    stage's values, not tuned for maps), overridden by keyword"""
+    p = CloudVisibilityParams()
+    load_lib().scvod_cloud_visibility_params_default(C.byref(p))
     for k, v in kw.items():
         assert hasattr(p, k), k
         setattr(p, k, v)
@@ -1516,6 +1544,47 @@ class Ctx:
     def visibility_scratch_bytes(self):
         """device scratch the vote holds on this ctx (0 before the first call)"""
         return int(self.lib.scvod_visibility_scratch_bytes(self.h))
+
+    # ---- a cloud against every scan's range image (include/scvod.h: scvod_cloud_visibility_device) ----
+    def cloud_visibility(self, d_xyzi, d_images, poses, params=None, flags=0, want=("votes", "verdict"), stream=None):
+        """scvod_cloud_visibility_device: the world-frame cloud `d_xyzi` (torch float32 [n, 4] on the ctx's device) against the range
+        images `d_images` (torch float32 [n_scans, A, S], as batch_visibility / visibility_device write them) of the scans at `poses`
+        ([n_scans, 6] or None: the zero pose).  A dict of device tensors, one per name in `want` (CVIS_OUTPUTS; None: both): votes
+        int16 [n, 4] holding the uint16 bits {n_through, n_agree, n_occluded, n_empty}, verdict uint8 [n] (VIS_*).  Stream-ordered."""
+        import torch
+        want = CVIS_OUTPUTS if want is None else tuple(want)
+        assert all(w in CVIS_OUTPUTS for w in want), want
+        _, S, A, _ = grid_dims(self.params)
+        n = int(d_xyzi.shape[0])
+        n_scans = int(d_images.shape[0])
+        assert d_images.dtype == torch.float32 and d_images.is_contiguous() and d_images.numel() == n_scans * A * S
+        assert d_xyzi.dtype == torch.float32 and d_xyzi.is_contiguous() and (n == 0 or d_xyzi.shape[1] == 4)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == n_scans
+        prm = params if params is not None else cloud_visibility_params_default()
+        dev = torch.device("cuda", self.device)
+        out = {}
+        if "votes" in want:
+            out["votes"] = torch.empty((n, 4), dtype=torch.int16, device=dev)
+        if "verdict" in want:
+            out["verdict"] = torch.empty((n,), dtype=torch.uint8, device=dev)
+        ptr = [C.c_void_p(out[w].data_ptr()) if w in out and n > 0 else None for w in CVIS_OUTPUTS]
+        self._chk(self.lib.scvod_cloud_visibility_device(self.h, C.c_void_p(d_xyzi.data_ptr()) if n > 0 else None, n,
+                                                         C.c_void_p(d_images.data_ptr()) if n_scans > 0 else None,
+                                                         None if p is None else p.ctypes.data_as(C.c_void_p), n_scans, C.byref(prm),
+                                                         int(flags), *ptr, C.c_void_p(stream or 0)))
+        return out
+
+    def cloud_visibility_stats(self):
+        """{points, finite, seen_through, keep, untested (among the finite), through, agree, occluded, empty, steps} of the last
+        cloud_visibility (synchronises its stream); steps: the (chunk, scan) steps that were not skipped"""
+        o = (C.c_int64 * 10)()
+        self._chk(self.lib.scvod_cloud_visibility_stats(self.h, o))
+        return dict(zip(CVIS_STATS, (int(v) for v in o)))
+
+    def cloud_visibility_scratch_bytes(self):
+        """device scratch the stage holds on this ctx (0 before the first call)"""
+        return int(self.lib.scvod_cloud_visibility_scratch_bytes(self.h))
 
     def voxelgrid(self, xyzi, leaf=(0.08, 0.08, 0.08), labels=None, max_intensity=1.0):
         """SSC::getCloud label filter + pcl::VoxelGrid of one host scan (ssc.cpp:1063-1076, 1103-1106)."""

@@ -1456,6 +1456,68 @@ int scvod_visibility_stats(scvod_ctx* ctx, int64_t* h_out8);
 /* bytes of device scratch the vote holds on this ctx (0 before the first call) */
 int64_t scvod_visibility_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- a world-frame cloud against the range images of every scan in reach (csrc/scvod_cloudvis.hip) ----
+ * Reference analogue: none; this project's convention, the map-level step of Removert / ERASOR-style cleaners.
+ * The vote above looks at a point of scan j from a few scans along the successor table.  Here the query is ANY cloud in the world
+ * frame -- the representatives of a static map (scvod_map_points), a merged map, a scan moved to the world -- and EVERY scan of the
+ * call is a viewer of every point; there is no successor table.
+ *   d_xyzi    n 16-byte records in the world frame; the intensity word is ignored
+ *   d_images  [n_scans][A * S] floats, exactly what scvod_visibility_device / scvod_batch_visibility write on this ctx's grid
+ *             (SCVOD_VIS_IMAGES_ONLY writes them alone)
+ *   h_poses   [n_scans][6]; NULL: the zero pose for every scan
+ * The viewer of a pair is scan s: T_s = scvod_pose_delta(zero pose, pose_s), that is trans_s^-1, computed on the host as the scan stage
+ * computes its matrices; p' = T_s q with T0*x + T1*y + T2*z + T3 per row, left to right in fp32 without contraction.  The pair's class
+ * is the rule stated above on p' (one device function serves both stages), with its OUTSIDE / EMPTY cases told apart -- OUTSIDE, EMPTY,
+ * THROUGH, AGREE, OCCLUDED -- and one addition: with max_range > 0 a pair with dis' > max_range is OUTSIDE.
+ *   d_votes[i][4]  uint16 counters {n_through, n_agree, n_occluded, n_empty} of point i.  OUTSIDE pairs are not counted (on a
+ *                  trajectory they are nearly all pairs).  n_scans <= 65535, so no counter can wrap.
+ *   d_verdict[i]   SCVOD_VIS_UNTESTED      iff the record is not finite or all four counters are 0
+ *                  SCVOD_VIS_SEEN_THROUGH  iff n_through >= min_through &&
+ *                                          (int64)n_through * vote_den >= (int64)vote_num * (n_through + n_agree)
+ *                  SCVOD_VIS_KEEP          otherwise
+ * Either output may be NULL.  Every output is an integer count: it does not depend on the order of the points or of the work and is
+ * bit-identical from run to run.  The intended use: scvod_batch_visibility with SCVOD_VIS_IMAGES_ONLY, scvod_map_points, this call,
+ * then scvod_map_accumulate_labelled of the same points with the verdict bytes as labels and a keep table without
+ * SCVOD_VIS_SEEN_THROUGH: the cleaned map is a new labelled map.
+ * How it runs: the points are keyed by a 2 m world tile (x, y interleaved; records that are not finite and tiles beyond +-16.384 km
+ * share the last key, which costs time, never correctness), (key, index) pairs are radix-sorted on the 28 key bits, and a workgroup
+ * walks all scans for 512 consecutive sorted points, skipping a scan when no point of its chunk can lie within the reach
+ * min(max_dis, max_range) of that sensor (the bound: DESIGN.md section 2).  The skip changes no output bit.  SCVOD_CVIS_NO_SORT leaves
+ * the sort out and cuts the chunks from the input order: identical outputs, for a cloud that already is spatially coherent (a scan)
+ * and for measuring what the sort buys.
+ * Stream-ordered (stream NULL = the ctx's stream), never synchronises with the host; h_poses is turned into matrices and staged before
+ * the call returns.  The call touches neither the arena nor any batch state nor the scan stage's scratch or stats.  Each call
+ * overwrites the stats of the one before, and the calls of one ctx must be ordered among themselves (they share their scratch).
+ * Argument errors (NULL ctx or params, n < 0, n_scans < 0 or > 65535, reserved != 0, a parameter outside the ranges below, NULL
+ * d_images with n_scans > 0, a NULL cloud with n > 0, d_xyzi or d_images not 16-byte aligned, d_votes not 8-byte aligned, unknown flag
+ * bits) are SCVOD_ERR_INVALID before any device is looked for; n > 2^31 - 1 is SCVOD_ERR_CAPACITY.  n == 0 or n_scans == 0 is fine:
+ * every finite point is UNTESTED.  Scratch (48 bytes per scan; with the sort 16 bytes per point and rocprim's temporary storage; 10
+ * counter words) is a grow-only allocation of its own, freed by scvod_destroy and NOT part of scvod_arena_bytes; a call that needs
+ * more than any before waits for the one in flight before it grows. */
+typedef struct scvod_cloud_visibility_params { /* 32 bytes */
+    int32_t halo;        /* 0 or 1: the window is (2 halo + 1)^2 pixels                     */
+    float gap_abs;       /* metres, >= 0 and finite                                         */
+    float gap_rel;       /* per metre of dis', >= 0 and finite                              */
+    float max_range;     /* metres, >= 0 and finite; 0: the grid's max_dis alone            */
+    int32_t min_through; /* any value                                                       */
+    int32_t vote_num;    /* 0 .. 1 << 20                                                    */
+    int32_t vote_den;    /* 1 .. 1 << 20                                                    */
+    int32_t reserved;    /* 0                                                               */
+} scvod_cloud_visibility_params;
+#define SCVOD_CVIS_NO_SORT 1 /* chunks of consecutive INPUT points: no key, no sort; outputs identical */
+/* halo 0, gap_abs 0.4f, gap_rel 0.02f, max_range 0, min_through 2, vote 1 / 2: the scan stage's values.  They are NOT tuned for maps
+ * (a map point has hundreds of viewers, a scan point four) and NOT from real data. */
+void scvod_cloud_visibility_params_default(scvod_cloud_visibility_params* p);
+int scvod_cloud_visibility_device(scvod_ctx* ctx, const void* d_xyzi, int64_t n, const float* d_images, const float* h_poses,
+                                  int32_t n_scans, const scvod_cloud_visibility_params* params, int32_t flags, uint16_t* d_votes,
+                                  uint8_t* d_verdict, void* stream);
+/* h_out10 = {points, finite records, SEEN_THROUGH, KEEP, UNTESTED among the finite, pairs THROUGH, AGREE, OCCLUDED, EMPTY, (chunk, scan)
+ * steps that were not skipped} of the last call.  Word 9 depends on the implementation (chunk size, order, bound); it is at most
+ * ceil(n / 512) * n_scans.  Synchronises that call's stream.  SCVOD_ERR_STATE before the first call. */
+int scvod_cloud_visibility_stats(scvod_ctx* ctx, int64_t* h_out10);
+/* bytes of device scratch the stage holds on this ctx (0 before the first call) */
+int64_t scvod_cloud_visibility_scratch_bytes(scvod_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
