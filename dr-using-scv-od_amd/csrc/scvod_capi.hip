@@ -218,6 +218,10 @@ struct scvod_ctx {
     // fallback's regions) and 8 counter words of their own, allocated by the first call; not part of the arena or the table's scratch
     Scratch ot;  // stream / ran: the last call (scvod_batch_object_truth_stats waits for it)
     unsigned long long* ot_counters = nullptr;
+    // the objects' vote on the seen-through verdict (scvod_batch_object_visibility, scvod_objvis.hip): a grow-only block (the tiles'
+    // accumulators) and 8 counter words of their own, allocated by the first call; not part of the arena or the table's scratch
+    Scratch ov;  // stream / ran: the last call (scvod_batch_object_visibility_stats waits for it)
+    unsigned long long* ov_counters = nullptr;
     // scan stacking (scvod_batch_stack_scans, scvod_stack.hip): the segment and tile tables, one grow-only block of their own allocated
     // by the first call; not part of the arena
     Scratch stk;
@@ -1561,6 +1565,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->in_counters) hipFree(c->in_counters);
     if (c->ot.buf) hipFree(c->ot.buf);
     if (c->ot_counters) hipFree(c->ot_counters);
+    if (c->ov.buf) hipFree(c->ov.buf);
+    if (c->ov_counters) hipFree(c->ov_counters);
     if (c->stk.buf) hipFree(c->stk.buf);
     if (c->vis.buf) hipFree(c->vis.buf);
     if (c->vis_counters) hipFree(c->vis_counters);
@@ -3622,6 +3628,94 @@ int scvod__ctx_object_lists(scvod_ctx* c, const char* who, const long long** tab
 
 int64_t scvod_batch_object_truth_scratch_bytes(scvod_ctx* c) {
     return c ? (int64_t)c->ot.cap + (c->ot_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+}
+
+// ---- the objects of the table vote on the seen-through verdict (scvod_objvis.hip) ----
+void scvod_object_visibility_params_default(scvod_object_visibility_params* p) {
+    if (!p) return;
+    p->flags = 0;
+    p->min_points = 1;
+    p->min_tested = 1;
+    p->min_through = 2;
+    p->vote_num = 1;
+    p->vote_den = 2;
+    p->reserved[0] = p->reserved[1] = 0;
+}
+
+int scvod_batch_object_visibility(scvod_ctx* c, const uint8_t* d_verdict, const uint32_t* d_votes, const void* d_objects,
+                                  const scvod_object_visibility_params* params, void* d_records, int64_t cap_records, uint8_t* d_verdict_out,
+                                  void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    scvod_object_visibility_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_object_visibility_params_default(&p);
+    if (!d_verdict) return fail(c, SCVOD_ERR_INVALID, "NULL d_verdict");
+    if (p.flags & ~(SCVOD_OBJVIS_POOL_PAIRS | SCVOD_OBJVIS_WITH_TRACK)) return fail(c, SCVOD_ERR_INVALID, "unknown flag bit (flags %d)", p.flags);
+    if (p.reserved[0] != 0 || p.reserved[1] != 0) return fail(c, SCVOD_ERR_INVALID, "scvod_object_visibility_params::reserved must be 0");
+    if (p.min_points < 1 || p.min_tested < 1) return fail(c, SCVOD_ERR_INVALID, "min_points %d, min_tested %d: both at least 1", p.min_points, p.min_tested);
+    if (p.vote_den < 1 || p.vote_den > (1 << 20) || p.vote_num < 0 || p.vote_num > (1 << 20))
+        return fail(c, SCVOD_ERR_INVALID, "vote %d / %d: 0 <= vote_num <= 2^20, 1 <= vote_den <= 2^20", p.vote_num, p.vote_den);
+    const bool pool = (p.flags & SCVOD_OBJVIS_POOL_PAIRS) != 0, with_track = (p.flags & SCVOD_OBJVIS_WITH_TRACK) != 0;
+    if (pool && !d_votes) return fail(c, SCVOD_ERR_INVALID, "SCVOD_OBJVIS_POOL_PAIRS without d_votes");
+    if (with_track && !d_objects) return fail(c, SCVOD_ERR_INVALID, "SCVOD_OBJVIS_WITH_TRACK without d_objects");
+    if (cap_records < 0) return fail(c, SCVOD_ERR_INVALID, "cap_records below 0");
+    if (((uintptr_t)d_votes & 3u) || ((uintptr_t)d_records & 3u)) return fail(c, SCVOD_ERR_INVALID, "d_votes and d_records must be 4-byte aligned");
+    if ((uintptr_t)d_objects & 7u) return fail(c, SCVOD_ERR_INVALID, "d_objects is not 8-byte aligned");
+    if (d_verdict_out && d_verdict_out != d_verdict) {
+        const uintptr_t n = (uintptr_t)(c->batch_valid && c->A.total_pts > 0 ? c->A.total_pts : 0);
+        const uintptr_t o0 = (uintptr_t)d_verdict_out, o1 = o0 + n;
+        auto hits = [&](const void* q, uintptr_t bytes) { return q && bytes > 0 && o0 < (uintptr_t)q + bytes && (uintptr_t)q < o1; };
+        const uintptr_t recs = (uintptr_t)(cap_records > 0 ? cap_records : 0);
+        if (n > 0 && (hits(d_verdict, n) || hits(d_votes, 4 * n) || hits(d_records, sizeof(scvod_object_visibility) * recs) ||
+                      hits(d_objects, sizeof(scvod_object) * (recs > 0 ? recs : 1))))
+            return fail(c, SCVOD_ERR_INVALID, "d_verdict_out overlaps an input or d_records (only d_verdict_out == d_verdict works in place)");
+    }
+    const long long* tab_stats = nullptr;
+    const uint64_t* key_out = nullptr;
+    const int32_t* begin = nullptr;
+    const char* why = "";
+    if (int rc = scvod__ctx_object_lists(c, "scvod_batch_object_visibility", &tab_stats, &key_out, &begin, &why)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    if (int rc = counter_block(c, &c->ov_counters, 8)) return rc;
+    if (int rc = scratch_reserve(c, c->ov, objvis_work_bytes(c->A.total_pts))) return rc;
+    ObjVisJob J{};
+    J.tab_stats = tab_stats;  // what the table left in the scratch; of its caller's buffers d_objects alone, and only with WITH_TRACK
+    J.key_out = key_out;
+    J.begin = begin;
+    J.verdict = d_verdict;
+    J.votes = d_votes;
+    J.obj_bytes = with_track ? (const unsigned char*)d_objects : nullptr;
+    J.out = d_verdict_out;
+    J.rec = (scvod_object_visibility*)d_records;
+    J.cap = (long long)cap_records;
+    J.pool = pool ? 1 : 0;
+    J.min_points = p.min_points;
+    J.min_tested = p.min_tested;
+    J.min_through = p.min_through;
+    J.vote_num = p.vote_num;
+    J.vote_den = p.vote_den;
+    J.counters = c->ov_counters;
+    launch_object_visibility(c->A, J, c->ov.buf, st);
+    HIPCHK(c, hipGetLastError());
+    c->ov.stream = st;
+    c->ov.ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_object_visibility_stats(scvod_ctx* c, int64_t* h_out8) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->ov.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_batch_object_visibility on this ctx yet");
+    if (int rc = read_counters(c, c->ov_counters, 8, c->ov.stream, h_out8)) return rc;
+    if (h_out8[7]) return fail(c, SCVOD_ERR_CAPACITY, "the table holds %lld objects, the record buffer %lld", (long long)h_out8[0], (long long)h_out8[6]);
+    return SCVOD_OK;
+}
+
+int64_t scvod_batch_object_visibility_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->ov.cap + (c->ov_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
 }
 
 void scvod_object_truth_params_default(scvod_object_truth_params* p) {

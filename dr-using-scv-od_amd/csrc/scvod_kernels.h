@@ -563,6 +563,28 @@ struct TruthJob {
 size_t truth_work_bytes(long long total_pts, int max_scan_pts);
 void launch_object_truth(const Arena& A, TruthJob J, void* work, hipStream_t st);
 
+// the objects of the table vote on the seen-through verdict (scvod_batch_object_visibility; scvod_objvis.hip): reads key_out, begin and
+// stats[1] (objects) / stats[2] (members) of the ObjectJob that built the table.  work: objvis_work_bytes bytes (8 words per tile of
+// SCVOD_OBJVIS_TILE list positions, cleared by every launch); counters: the 8 words of scvod_batch_object_visibility_stats, cleared by
+// every launch
+enum { kOvStObjects = 0, kOvStVoted, kOvStForced, kOvStSeen, kOvStMovedSeen, kOvStMovedKeep, kOvStWritten, kOvStOverflow };
+struct ObjVisJob {
+    const uint64_t* key_out;       // the table's sorted member list: object << 32 | batch slot
+    const int32_t* begin;          // the table's run starts
+    const long long* tab_stats;    // the table's stats
+    const uint8_t* verdict;        // [total points] caller's verdict bytes
+    const uint32_t* votes;         // [total points] caller's pair counters, or nullptr
+    const unsigned char* obj_bytes;  // the caller's scvod_object records (SCVOD_OBJVIS_WITH_TRACK), or nullptr
+    uint8_t* out;                  // [total points] caller's, may be `verdict`, or nullptr
+    scvod_object_visibility* rec;  // [cap] caller's, or nullptr
+    long long cap;
+    int32_t pool, min_points, min_tested, min_through, vote_num, vote_den;
+    unsigned long long* counters;
+    unsigned* acc;                 // filled by launch_object_visibility
+};
+size_t objvis_work_bytes(long long total_pts);
+void launch_object_visibility(const Arena& A, ObjVisJob J, void* work, hipStream_t st);
+
 // a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the shared one (grid_buckets, grid_work_ints)
 // over the base cloud with the caller's cell edge; work: sp_work_bytes bytes; stats: the 8 words of scvod_map_split_stats, written by
 // every launch.  The optional outputs of SpJob are nullptr when not asked for; mark == nullptr: a byte array inside `work`

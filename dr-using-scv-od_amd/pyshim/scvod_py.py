@@ -186,6 +186,24 @@ CVIS_OUTPUTS = ("votes", "verdict")
 CVIS_STATS = ("points", "finite", "seen_through", "keep", "untested", "through", "agree", "occluded", "empty", "steps")
 
 
+class ObjectVisibilityParams(C.Structure):
+    """scvod_object_visibility_params (include/scvod.h), 32 bytes"""
+    _fields_ = [("flags", C.c_int32), ("min_points", C.c_int32), ("min_tested", C.c_int32), ("min_through", C.c_int32),
+                ("vote_num", C.c_int32), ("vote_den", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+OBJVIS_POOL_PAIRS = 1                                 # SCVOD_OBJVIS_POOL_PAIRS
+OBJVIS_WITH_TRACK = 2                                 # SCVOD_OBJVIS_WITH_TRACK
+OBJVIS_TILE = 2048                                    # SCVOD_OBJVIS_TILE
+OBJVIS_OUTPUTS = ("records", "verdict")
+OBJVIS_STATS = ("objects", "voted", "forced", "seen_through", "moved_to_seen_through", "moved_to_keep", "written", "overflow")
+# struct scvod_object_visibility: one object's share of the vote (scvod_batch_object_visibility), 48 bytes
+OBJECT_VISIBILITY_DTYPE = np.dtype([("n_points", "<i4"), ("n_untested", "<i4"), ("n_keep", "<i4"), ("n_seen", "<i4"),
+                                    ("sum_through", "<i4"), ("sum_agree", "<i4"), ("sum_occluded", "<i4"), ("sum_other", "<i4"),
+                                    ("verdict", "<i4"), ("how", "<i4"), ("reserved", "<i4", 2)])
+assert OBJECT_VISIBILITY_DTYPE.itemsize == 48
+
+
 class SplitParams(C.Structure):
     """struct scvod_split_params (include/scvod.h)"""
     _fields_ = [("cell", C.c_float), ("max_rings", C.c_int32), ("base_stride", C.c_int32), ("query_stride", C.c_int32),
@@ -412,6 +430,10 @@ def load_lib():
         "scvod_cloud_visibility_device": (C.c_int, [vp, vp, i64, vp, vp, i32, C.POINTER(CloudVisibilityParams), i32, vp, vp, vp]),
         "scvod_cloud_visibility_stats": (C.c_int, [vp, vp]),
         "scvod_cloud_visibility_scratch_bytes": (i64, [vp]),
+        "scvod_object_visibility_params_default": (None, [C.POINTER(ObjectVisibilityParams)]),
+        "scvod_batch_object_visibility": (C.c_int, [vp, vp, vp, vp, C.POINTER(ObjectVisibilityParams), vp, i64, vp, vp]),
+        "scvod_batch_object_visibility_stats": (C.c_int, [vp, vp]),
+        "scvod_batch_object_visibility_scratch_bytes": (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # raises AttributeError if a declared symbol is not exported
@@ -454,6 +476,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_visibility_stats", "scvod_visibility_scratch_bytes",
                     "scvod_cloud_visibility_params_default", "scvod_cloud_visibility_device", "scvod_cloud_visibility_stats",
                     "scvod_cloud_visibility_scratch_bytes",
+                    "scvod_object_visibility_params_default", "scvod_batch_object_visibility", "scvod_batch_object_visibility_stats",
+                    "scvod_batch_object_visibility_scratch_bytes",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
                     "scvod_map_split"]
 
@@ -615,6 +639,17 @@ def cloud_visibility_params_default(**kw):
     stage's values, not tuned for maps), overridden by keyword"""
     p = CloudVisibilityParams()
     load_lib().scvod_cloud_visibility_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def object_visibility_params_default(**kw):
+    """scvod_object_visibility_params with the defaults (flags 0, min_points 1, min_tested 1, min_through 2, vote 1 / 2: this project's
+    values, not from real data), overridden by keyword"""
+    p = ObjectVisibilityParams()
+    load_lib().scvod_object_visibility_params_default(C.byref(p))
     for k, v in kw.items():
         assert hasattr(p, k), k
         setattr(p, k, v)
@@ -1544,6 +1579,46 @@ class Ctx:
     def visibility_scratch_bytes(self):
         """device scratch the vote holds on this ctx (0 before the first call)"""
         return int(self.lib.scvod_visibility_scratch_bytes(self.h))
+
+    # ---- the objects of the table vote on the verdict (include/scvod.h: scvod_batch_object_visibility) ----
+    def batch_object_visibility(self, d_verdict, d_votes=None, d_objects=None, params=None, cap=None, want=("records", "verdict"), in_place=False,
+                                stream=None):
+        """scvod_batch_object_visibility on the table the last batch_objects (with lists) left: d_verdict uint8 [points] and d_votes
+        int32 [points] as batch_visibility wrote them, d_objects the table's OBJECT_DTYPE records as a contiguous device tensor (read
+        with OBJVIS_WITH_TRACK only).  A dict of device tensors, one per name in `want` (OBJVIS_OUTPUTS): records uint8 [cap, 48] (view
+        as OBJECT_VISIBILITY_DTYPE on the host; cap None: the batch's points, which holds every table; the rows behind the records
+        written are not initialised), verdict uint8 [points] -- with in_place=True d_verdict itself, rewritten.  Stream-ordered;
+        batch_object_visibility_stats() tells what happened"""
+        import torch
+        want = tuple(want)
+        assert all(w in OBJVIS_OUTPUTS for w in want), want
+        n = int(self._n_pts)
+        assert d_verdict.dtype == torch.uint8 and d_verdict.is_contiguous() and d_verdict.numel() >= n
+        assert d_votes is None or (d_votes.is_contiguous() and d_votes.element_size() == 4 and d_votes.numel() >= n)
+        assert d_objects is None or d_objects.is_contiguous()
+        out = {}
+        cap = int(n if cap is None else cap)
+        if "records" in want:
+            out["records"] = torch.empty((max(cap, 1), OBJECT_VISIBILITY_DTYPE.itemsize), dtype=torch.uint8, device=d_verdict.device)[:cap]
+        if "verdict" in want:
+            out["verdict"] = d_verdict if in_place else torch.empty((max(n, 1),), dtype=torch.uint8, device=d_verdict.device)[:n]
+        self._chk(self.lib.scvod_batch_object_visibility(
+            self.h, C.c_void_p(d_verdict.data_ptr()), None if d_votes is None else C.c_void_p(d_votes.data_ptr()),
+            None if d_objects is None else C.c_void_p(d_objects.data_ptr()), C.byref(params) if params is not None else None,
+            C.c_void_p(out["records"].data_ptr()) if "records" in out else None, cap if "records" in out else 0,
+            C.c_void_p(out["verdict"].data_ptr()) if "verdict" in out else None, C.c_void_p(stream or 0)))
+        return out
+
+    def batch_object_visibility_stats(self):
+        """{objects, voted, forced, seen_through, moved_to_seen_through, moved_to_keep, written, overflow} of the last
+        batch_object_visibility; synchronises its stream; raises after an overflow"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_batch_object_visibility_stats(self.h, o))
+        return dict(zip(OBJVIS_STATS, (int(v) for v in o)))
+
+    def batch_object_visibility_scratch_bytes(self):
+        """device scratch of the stage on this ctx (not part of arena_bytes or batch_objects_scratch_bytes)"""
+        return int(self.lib.scvod_batch_object_visibility_scratch_bytes(self.h))
 
     # ---- a cloud against every scan's range image (include/scvod.h: scvod_cloud_visibility_device) ----
     def cloud_visibility(self, d_xyzi, d_images, poses, params=None, flags=0, want=("votes", "verdict"), stream=None):

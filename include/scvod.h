@@ -1518,6 +1518,78 @@ int scvod_cloud_visibility_stats(scvod_ctx* ctx, int64_t* h_out10);
 /* bytes of device scratch the stage holds on this ctx (0 before the first call) */
 int64_t scvod_cloud_visibility_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- the objects of a batch vote on the seen-through verdict (opt-in: nothing runs unless it is called; csrc/scvod_objvis.hip) ----
+ * Reference analogue: none.  No program of the reference joins free-space evidence with its clusters; the rule and both sets of
+ * defaults are this project's convention, and the defaults are NOT from real data.
+ * scvod_batch_visibility answers per point: the half of a moving car that no neighbouring scan looks behind stays KEEP or UNTESTED, and
+ * a few strays of a wall come out SEEN_THROUGH.  This call joins the verdict bytes with the object table: per object of the table the
+ * last scvod_batch_objects left in the ctx's scratch (the state rules and SCVOD_ERR_STATE cases of scvod_batch_object_truth; a
+ * SCVOD_OBJ_NO_TRACK table is fine), over its members -- the input points d_member_src lists --
+ *   n_seen / n_keep / n_untested   members whose byte of d_verdict is 2 / 1 / anything else
+ *   sum_through .. sum_other       bytes 0..3 of d_votes summed over ALL members (0 without d_votes)
+ * With t = n_seen, a = n_keep (SCVOD_OBJVIS_POOL_PAIRS: t = sum_through, a = sum_agree) an object VOTES iff
+ *   n_points >= min_points && n_keep + n_seen >= min_tested
+ * and its verdict is SCVOD_VIS_SEEN_THROUGH iff
+ *   t >= min_through && (int64)t * vote_den >= (int64)vote_num * ((int64)t + a)
+ * and SCVOD_VIS_KEEP otherwise (how = 1).  With SCVOD_OBJVIS_WITH_TRACK an object whose record in d_objects has dynamic == 1 is
+ * SCVOD_VIS_SEEN_THROUGH with how = 2 whether or not it votes: voxel differencing speaks for car-typed clusters, free space for
+ * anything.  Every other object has verdict -1, how 0.  Integers only: host and device agree by construction, and every output is
+ * bit-identical from run to run.
+ *   d_verdict      one byte per INPUT point of the ctx's last batch, what scvod_batch_visibility wrote; any bytes are legal
+ *   d_votes        one uint32 per input point (that call's pair counters); may be NULL without SCVOD_OBJVIS_POOL_PAIRS
+ *   d_objects      the 64-byte records the last scvod_batch_objects wrote; read only with SCVOD_OBJVIS_WITH_TRACK, and only the
+ *                  `dynamic` byte of the table's objects (a SCVOD_OBJ_NO_TRACK table has 0 there)
+ *   d_records      [cap_records] scvod_object_visibility, one per object in table order, or NULL: no records.  Nothing is written at or
+ *                  behind cap_records; an overflow (d_records given, more objects than cap_records) is latched for the stats call and
+ *                  changes no byte of d_verdict_out
+ *   d_verdict_out  one byte per input point, or NULL: every member of an object with how != 0 gets the object's verdict, its UNTESTED
+ *                  members included -- the occluded half goes with the half that was seen --, every other input point d_verdict[i].
+ *                  d_verdict_out == d_verdict works in place.  The bytes gate scvod_map_accumulate_labelled as the per-point verdict does
+ * Stream-ordered (stream NULL = the stream of the ctx's last batch call); never synchronises with the host except to grow its scratch
+ * (32 bytes per SCVOD_OBJVIS_TILE input points and 8 counter words: a grow-only allocation of its own, NOT part of scvod_arena_bytes,
+ * not the table's scratch), so scvod_batch_visibility -> this call -> scvod_map_accumulate_labelled on one stream needs no host read.
+ * It launches and allocates nothing unless it is called and moves no other stage's state.  params NULL: the defaults.
+ * SCVOD_ERR_INVALID before a device is looked for and before anything is written: NULL ctx, NULL d_verdict, an unknown flag bit,
+ * reserved != 0, min_points < 1, min_tested < 1, vote_den outside 1 .. 1 << 20, vote_num outside 0 .. 1 << 20, POOL_PAIRS without
+ * d_votes, WITH_TRACK without d_objects, cap_records < 0, d_votes or d_records not 4-byte aligned, d_objects not 8-byte aligned, a
+ * d_verdict_out that overlaps d_verdict without being equal to it or overlaps d_votes, d_records (cap_records records) or d_objects
+ * (taken to be as long as d_records: cap_records records, at least one).
+ * How it runs: the sorted member list is cut into tiles of SCVOD_OBJVIS_TILE positions, whatever the objects' sizes; objects inside a
+ * tile are finished by its workgroup, an object that crosses a tile edge adds integer partial counts into the 8-word accumulator of the
+ * tile in which it begins, and a second launch decides it once and rewrites its pieces (csrc/scvod_objvis.hip). */
+#define SCVOD_OBJVIS_POOL_PAIRS 1 /* flags bit 0: the rule reads the members' pooled pair counters, not their verdict bytes */
+#define SCVOD_OBJVIS_WITH_TRACK 2 /* flags bit 1: an object whose table record has dynamic == 1 is SEEN_THROUGH whatever the vote */
+#define SCVOD_OBJVIS_TILE 2048    /* member-list positions per tile */
+typedef struct scvod_object_visibility_params { /* 32 bytes */
+    int32_t flags;
+    int32_t min_points;  /* >= 1: objects with fewer members do not vote                            */
+    int32_t min_tested;  /* >= 1: nor objects with fewer members whose byte is KEEP or SEEN_THROUGH */
+    int32_t min_through; /* any value                                                               */
+    int32_t vote_num;    /* 0 .. 1 << 20                                                            */
+    int32_t vote_den;    /* 1 .. 1 << 20                                                            */
+    int32_t reserved[2]; /* 0                                                                       */
+} scvod_object_visibility_params;
+/* flags 0, min_points 1, min_tested 1, min_through 2, vote 1 / 2.  This project's values, NOT from real data. */
+void scvod_object_visibility_params_default(scvod_object_visibility_params* p);
+typedef struct scvod_object_visibility { /* 48 bytes, one per object of the table, table order */
+    int32_t n_points;                                        /* == scvod_object::n_points                                         */
+    int32_t n_untested, n_keep, n_seen;                      /* members by verdict byte: 2 is seen, 1 keep, every other value untested */
+    int32_t sum_through, sum_agree, sum_occluded, sum_other; /* bytes 0..3 of d_votes summed over ALL members; 0 without d_votes   */
+    int32_t verdict;                                         /* -1 none, SCVOD_VIS_KEEP, SCVOD_VIS_SEEN_THROUGH                    */
+    int32_t how;                                             /* 0 no verdict, 1 voted, 2 forced by the table's dynamic flag        */
+    int32_t reserved[2];                                     /* 0                                                                  */
+} scvod_object_visibility;
+int scvod_batch_object_visibility(scvod_ctx* ctx, const uint8_t* d_verdict, const uint32_t* d_votes, const void* d_objects,
+                                  const scvod_object_visibility_params* params, void* d_records, int64_t cap_records,
+                                  uint8_t* d_verdict_out, void* stream);
+/* h_out8 = {objects of the table, objects with how == 1 (voted), objects with how == 2 (forced), objects with verdict SEEN_THROUGH,
+ * members moved to SEEN_THROUGH (input byte not 2, object's verdict 2), members moved to KEEP (input byte not 1, object's verdict 1),
+ * records written, 1 after an overflow} of the last call.  Synchronises that call's stream.  SCVOD_ERR_CAPACITY after an overflow,
+ * with the words filled; SCVOD_ERR_STATE before the first call. */
+int scvod_batch_object_visibility_stats(scvod_ctx* ctx, int64_t* h_out8);
+/* bytes of device scratch the stage holds on this ctx (0 before the first call) */
+int64_t scvod_batch_object_visibility_scratch_bytes(scvod_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
