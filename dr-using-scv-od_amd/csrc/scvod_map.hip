@@ -447,6 +447,8 @@ void scvod_map_destroy(scvod_map* m) {
     if (m->d_cls) hipFree(m->d_cls);
     if (m->q_counters) hipFree(m->q_counters);
     if (m->f_buf) hipFree(m->f_buf);
+    if (m->c_buf) hipFree(m->c_buf);
+    if (m->v_buf) hipFree(m->v_buf);
     delete m;
 }
 

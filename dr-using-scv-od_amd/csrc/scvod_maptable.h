@@ -46,6 +46,16 @@ struct scvod_map {
     long long f_points = 0;          // points of the last filter
     hipStream_t f_stream = nullptr;  // its stream
     bool f_ran = false;
+    // scvod_map_components / scvod_map_component_visibility: one grow-only block each, of their own (scvod_mapcomp.hip)
+    unsigned char* c_buf = nullptr;
+    size_t c_cap = 0;
+    long long c_records = 0;         // records of the last components call
+    hipStream_t c_stream = nullptr;  // its stream
+    bool c_ran = false;
+    unsigned char* v_buf = nullptr;
+    size_t v_cap = 0;
+    hipStream_t v_stream = nullptr;  // the stream of the last component vote
+    bool v_ran = false;
     std::string err;
 };
 

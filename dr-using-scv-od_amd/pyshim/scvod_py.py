@@ -204,6 +204,28 @@ OBJECT_VISIBILITY_DTYPE = np.dtype([("n_points", "<i4"), ("n_untested", "<i4"), 
 assert OBJECT_VISIBILITY_DTYPE.itemsize == 48
 
 
+class ComponentVisibilityParams(C.Structure):
+    """scvod_component_visibility_params (include/scvod.h), 32 bytes"""
+    _fields_ = [("flags", C.c_int32), ("min_cells", C.c_int32), ("max_cells", C.c_int32), ("min_tested", C.c_int32),
+                ("min_through", C.c_int32), ("vote_num", C.c_int32), ("vote_den", C.c_int32), ("reserved", C.c_int32)]
+
+
+CMPVIS_POOL_PAIRS = 1                                 # SCVOD_CMPVIS_POOL_PAIRS
+MAP_COMPONENTS_OUTPUTS = ("component", "table", "n")
+MAP_COMPONENTS_STATS = ("records", "nodes", "padding", "absent", "duplicates", "components", "written", "overflow")
+CMPVIS_OUTPUTS = ("records", "verdict")
+CMPVIS_STATS = ("components", "voted", "seen_through", "moved_to_seen_through", "moved_to_keep", "written", "beyond_cap", "overflow")
+# struct scvod_map_component: one connected component of the map's cells (scvod_map_components), 48 bytes
+MAP_COMPONENT_DTYPE = np.dtype([("key", "<u8"), ("n_records", "<i4"), ("first_record", "<i4"), ("cell_min", "<i4", 3),
+                                ("cell_max", "<i4", 3), ("reserved", "<i4", 2)])
+assert MAP_COMPONENT_DTYPE.itemsize == 48
+# struct scvod_component_visibility: one component's share of the vote (scvod_map_component_visibility), 64 bytes
+COMPONENT_VISIBILITY_DTYPE = np.dtype([("n_records", "<i4"), ("n_untested", "<i4"), ("n_keep", "<i4"), ("n_seen", "<i4"),
+                                       ("sum_through", "<i8"), ("sum_agree", "<i8"), ("sum_occluded", "<i8"), ("sum_empty", "<i8"),
+                                       ("verdict", "<i4"), ("how", "<i4"), ("reserved", "<i4", 2)])
+assert COMPONENT_VISIBILITY_DTYPE.itemsize == 64
+
+
 class SplitParams(C.Structure):
     """struct scvod_split_params (include/scvod.h)"""
     _fields_ = [("cell", C.c_float), ("max_rings", C.c_int32), ("base_stride", C.c_int32), ("query_stride", C.c_int32),
@@ -434,6 +456,12 @@ def load_lib():
         "scvod_batch_object_visibility": (C.c_int, [vp, vp, vp, vp, C.POINTER(ObjectVisibilityParams), vp, i64, vp, vp]),
         "scvod_batch_object_visibility_stats": (C.c_int, [vp, vp]),
         "scvod_batch_object_visibility_scratch_bytes": (i64, [vp]),
+        "scvod_map_components": (C.c_int, [vp, vp, i64, i32, vp, vp, i64, vp, vp]),
+        "scvod_map_components_stats": (C.c_int, [vp, vp]),
+        "scvod_map_components_scratch_bytes": (i64, [vp]),
+        "scvod_component_visibility_params_default": (None, [C.POINTER(ComponentVisibilityParams)]),
+        "scvod_map_component_visibility": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, C.POINTER(ComponentVisibilityParams), vp, i64, vp, vp]),
+        "scvod_map_component_visibility_stats": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # raises AttributeError if a declared symbol is not exported
@@ -478,6 +506,9 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_cloud_visibility_scratch_bytes",
                     "scvod_object_visibility_params_default", "scvod_batch_object_visibility", "scvod_batch_object_visibility_stats",
                     "scvod_batch_object_visibility_scratch_bytes",
+                    "scvod_map_components", "scvod_map_components_stats", "scvod_map_components_scratch_bytes",
+                    "scvod_component_visibility_params_default", "scvod_map_component_visibility",
+                    "scvod_map_component_visibility_stats",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
                     "scvod_map_split"]
 
@@ -653,6 +684,17 @@ def object_visibility_params_default(**kw):
     for k, v in kw.items():
         assert hasattr(p, k), k
         setattr(p, k, v)
+    return p
+
+
+def component_visibility_params_default(**kw):
+    """scvod_component_visibility_params with the library's defaults (flags 0, min_cells 1, max_cells 0 = no limit, min_tested 1,
+    min_through 2, vote 1 / 2: this project's values, not from real data), overridden by keyword"""
+    p = ComponentVisibilityParams()
+    load_lib().scvod_component_visibility_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert k in {f[0] for f in ComponentVisibilityParams._fields_} - {"reserved"}, k
+        setattr(p, k, int(v))
     return p
 
 
@@ -1933,6 +1975,81 @@ class StaticMap:
 
     def merge(self, d_records, stream=None):
         self._chk(self.lib.scvod_map_merge(self.h, C.c_void_p(d_records.data_ptr()), int(d_records.numel() // 2), C.c_void_p(stream or 0)))
+
+    # ---- connected components of the map's cells and their vote (include/scvod.h: scvod_map_components) ----
+    def components(self, records, connectivity=26, cap=None, want=MAP_COMPONENTS_OUTPUTS, stream=None):
+        """scvod_map_components of the list `records` (torch int64 [n, 2] on the map's device, as points / points_labelled / export hand
+        it out; only the keys are read): a dict of device tensors, one per name in `want` (MAP_COMPONENTS_OUTPUTS; "table" brings "n") --
+        component int32 [n] (-1: no node), table uint8 [cap, 48] (view as MAP_COMPONENT_DTYPE on the host; cap None: n, which holds
+        every table; the rows behind n are not initialised), n int64 [1].  Components are numbered ascending by their smallest cell
+        key.  Stream-ordered, no synchronisation; components_stats() tells what happened"""
+        import torch
+        want = tuple(want)
+        assert all(w in MAP_COMPONENTS_OUTPUTS for w in want), want
+        assert records.dtype == torch.int64 and records.is_contiguous() and (records.numel() == 0 or records.shape[-1] == 2)
+        n = int(records.numel() // 2)
+        cap = int(n if cap is None else cap)
+        dev = torch.device("cuda", self.device)
+        out = {}
+        if "component" in want:
+            out["component"] = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)[:n]
+        if "table" in want:
+            out["table"] = torch.empty((max(cap, 1), MAP_COMPONENT_DTYPE.itemsize), dtype=torch.uint8, device=dev)[:cap]
+        if "n" in want or "table" in want:
+            out["n"] = torch.empty((1,), dtype=torch.int64, device=dev)
+        self._chk(self.lib.scvod_map_components(
+            self.h, C.c_void_p(records.data_ptr()) if n > 0 else None, n, int(connectivity),
+            C.c_void_p(out["component"].data_ptr()) if "component" in out and n > 0 else None,
+            C.c_void_p(out["table"].data_ptr()) if "table" in out else None, cap if "table" in out else 0,
+            C.c_void_p(out["n"].data_ptr()) if "n" in out else None, C.c_void_p(stream or 0)))
+        return out
+
+    def components_stats(self):
+        """the MAP_COMPONENTS_STATS of the last components() as a dict (synchronises its stream); ScvodError with status -4 after a
+        table overflow"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_map_components_stats(self.h, o))
+        return dict(zip(MAP_COMPONENTS_STATS, (int(v) for v in o)))
+
+    def components_scratch_bytes(self):
+        return int(self.lib.scvod_map_components_scratch_bytes(self.h))
+
+    def component_visibility(self, comp, verdict, votes=None, params=None, cap_components=None, cap=None, want=CMPVIS_OUTPUTS, in_place=False,
+                             stream=None):
+        """scvod_map_component_visibility: `comp` the dict components() returned for the same list (its "component" and "n"), verdict
+        uint8 [n] and votes int16 [n, 4] as Ctx.cloud_visibility wrote them for the same points (votes None: no pooled sums).  A dict
+        of device tensors, one per name in `want` (CMPVIS_OUTPUTS): records uint8 [cap, 64] (view as COMPONENT_VISIBILITY_DTYPE on the
+        host; cap None: n), verdict uint8 [n] -- with in_place=True `verdict` itself, rewritten.  cap_components None: n (every
+        component votes).  Stream-ordered, no host read; component_visibility_stats() tells what happened"""
+        import torch
+        want = tuple(want)
+        assert all(w in CMPVIS_OUTPUTS for w in want), want
+        d_comp, d_n = comp["component"], comp["n"]
+        n = int(d_comp.numel())
+        assert d_comp.dtype == torch.int32 and d_comp.is_contiguous() and d_n.dtype == torch.int64
+        assert verdict.dtype == torch.uint8 and verdict.is_contiguous() and verdict.numel() == n
+        assert votes is None or (votes.is_contiguous() and votes.element_size() == 2 and votes.numel() == 4 * n)
+        cap = int(n if cap is None else cap)
+        cap_components = int(n if cap_components is None else cap_components)
+        out = {}
+        if "records" in want:
+            out["records"] = torch.empty((max(cap, 1), COMPONENT_VISIBILITY_DTYPE.itemsize), dtype=torch.uint8, device=verdict.device)[:cap]
+        if "verdict" in want:
+            out["verdict"] = verdict if in_place else torch.empty((max(n, 1),), dtype=torch.uint8, device=verdict.device)[:n]
+        self._chk(self.lib.scvod_map_component_visibility(
+            self.h, C.c_void_p(d_comp.data_ptr()) if n > 0 else None, n, C.c_void_p(d_n.data_ptr()), cap_components,
+            C.c_void_p(verdict.data_ptr()) if n > 0 else None, None if votes is None or n == 0 else C.c_void_p(votes.data_ptr()),
+            C.byref(params) if params is not None else None, C.c_void_p(out["records"].data_ptr()) if "records" in out else None,
+            cap if "records" in out else 0, C.c_void_p(out["verdict"].data_ptr()) if "verdict" in out and n > 0 else None,
+            C.c_void_p(stream or 0)))
+        return out
+
+    def component_visibility_stats(self):
+        """the CMPVIS_STATS of the last component_visibility() as a dict (synchronises its stream); ScvodError with status -4 after a
+        records overflow"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_map_component_visibility_stats(self.h, o))
+        return dict(zip(CMPVIS_STATS, (int(v) for v in o)))
 
     def points(self, stream=None):
         """(xyzi float32 [n, 4], records int64 [n, 2]) device tensors, same (unspecified) order"""

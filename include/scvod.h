@@ -1590,6 +1590,102 @@ int scvod_batch_object_visibility_stats(scvod_ctx* ctx, int64_t* h_out8);
 /* bytes of device scratch the stage holds on this ctx (0 before the first call) */
 int64_t scvod_batch_object_visibility_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- connected components of the map's cells, and their vote (opt-in: nothing runs or is allocated unless these are called;
+ *      csrc/scvod_mapcomp.hip) ----
+ * Reference analogue: none.  No program of the reference labels map cells; the conventions below are this project's (DESIGN.md
+ * section 2).
+ * NODES are the records of the caller's list: n 16-byte {key, val} records as scvod_map_points, scvod_map_points_labelled and
+ * scvod_map_export* hand them out; only the key is read.  Every output is aligned with that list.  A record whose key is ~0 (padding)
+ * or is not in the map is no node (component -1, counted).  Two records with the same key are the same cell.  A neighbouring cell is a
+ * node iff the LIST holds it: a list of scvod_map_points_labelled with a select table leaves cells out of the graph (ground, say).
+ * EDGES: two nodes are joined iff their cells differ by an offset in {-1, 0, 1}^3 \ {0} with |dx| + |dy| + |dz| <= 1, 2 or 3:
+ * connectivity 6, 18 or 26.  Cells outside [-2^20, 2^20) on an axis do not exist; no offset carries from one axis into the next.
+ *   d_component[i]  the index of record i's component, -1 for a record that is no node
+ *   d_table         [cap_table] scvod_map_component, one per component
+ *   d_n[0]          (device) the number of components
+ * Components are numbered ascending by the SMALLEST CELL KEY they hold, so the numbering depends on the set of cells alone: not on the
+ * order of the list, the table's capacity, the order of insertion or the run.  Every output is optional, but a table needs d_n.
+ * Nothing is written at or behind cap_table; more components than cap_table is an overflow, latched for the stats call, and
+ * d_component and d_n are complete all the same.  All reductions are integer: the outputs are bit-identical from run to run.
+ * Stream-ordered against accumulate, merge and clear; reads the map's table only; never synchronises with the host except to grow its
+ * scratch: 4 bytes per slot of the map, 64 bytes per record, rocprim's temporary storage of a sort of n pairs and 16 counter words, a
+ * grow-only allocation of the map's own that no other stage's scratch or counter shares.
+ * SCVOD_ERR_INVALID before a device is looked for: NULL map, n < 0 or n > 2^31 - 1, NULL records with n > 0, a connectivity other than
+ * 6 / 18 / 26, d_records or d_table or d_n not 8-byte, d_component not 4-byte aligned, cap_table < 0, a table without d_n, outputs that
+ * overlap the records or each other, a map of more than 2^30 slots.
+ * How it runs: every record finds its slot and leaves its list index there (lowest wins); every node probes the half neighbourhood
+ * (3 / 9 / 13 cells) and unites itself with the nodes it finds in a lock-free union-find over list indices (path halving, the larger
+ * root hooked under the smaller by compare-and-swap; no grid barrier, no waiting); a flatten pass; count, smallest key and box are
+ * reduced per root through an LDS table per workgroup; the roots are sorted by smallest key and the rank becomes the index. */
+typedef struct scvod_map_component { /* 48 bytes */
+    uint64_t key;                     /* smallest cell key of the component                */
+    int32_t n_records;                /* its records, duplicates included                  */
+    int32_t first_record;             /* lowest list index among them                      */
+    int32_t cell_min[3], cell_max[3]; /* signed cell coordinates, inclusive                */
+    int32_t reserved[2];              /* 0                                                 */
+} scvod_map_component;
+int scvod_map_components(scvod_map* map, const void* d_records, int64_t n, int32_t connectivity, int32_t* d_component, void* d_table,
+                         int64_t cap_table, int64_t* d_n, void* stream);
+/* h_out8 = {records, nodes, padding records, records whose key is absent, duplicate records, components, table records written,
+ * 1 after an overflow} of the last call.  Synchronises that call's stream.  SCVOD_ERR_CAPACITY after an overflow, with the words
+ * filled; SCVOD_ERR_STATE before the first call. */
+int scvod_map_components_stats(scvod_map* map, int64_t* h_out8);
+/* bytes of device scratch the labelling holds on this map (0 before the first call) */
+int64_t scvod_map_components_scratch_bytes(const scvod_map* map);
+
+/* The components vote on the seen-through verdict: the rule of scvod_batch_object_visibility, restated for components.  The rule and
+ * the defaults are this project's convention and NOT from real data.
+ *   d_component    [n] what scvod_map_components wrote for the same list; d_n (device) its component count
+ *   d_verdict      [n] one byte per record, what scvod_cloud_visibility_device wrote for the same points; any bytes are legal
+ *   d_votes        [n][4] uint16 {n_through, n_agree, n_occluded, n_empty} of that call, or NULL without SCVOD_CMPVIS_POOL_PAIRS
+ * Per component, over its members (the records with its index): n_seen / n_keep / n_untested = members whose byte is 2 / 1 / anything
+ * else; the four counters summed over ALL members in int64.  With t = n_seen, a = n_keep (SCVOD_CMPVIS_POOL_PAIRS: t = sum_through,
+ * a = sum_agree) a component VOTES iff
+ *   n_records >= min_cells && (max_cells == 0 || n_records <= max_cells) && n_keep + n_seen >= min_tested
+ * and its verdict is SCVOD_VIS_SEEN_THROUGH iff
+ *   t >= min_through && t * vote_den >= vote_num * (t + a)          (int64; the sums stay below 2^47, the products below 2^60)
+ * and SCVOD_VIS_KEEP otherwise (how = 1).  Every other component has verdict -1, how 0.
+ *   d_verdict_out  [n] or NULL: every member of a component that voted takes its verdict, UNTESTED members included; a record keeps
+ *                  its byte if its component is -1, did not vote, or has an index at or beyond cap_components.
+ *                  d_verdict_out == d_verdict works in place
+ *   d_records      [cap_records] scvod_component_visibility, one per component, or NULL.  Nothing is written at or behind cap_records;
+ *                  more components (below cap_components) than cap_records is an overflow, latched for the stats call
+ * d_n is read on the device: scvod_cloud_visibility_device -> scvod_map_components -> this call -> scvod_map_accumulate_labelled on one
+ * stream needs no host read.  Stream-ordered; never synchronises except to grow its scratch (48 bytes per component up to
+ * min(cap_components, n), 8 counter words: a grow-only allocation of the map's own).  params NULL: the defaults.
+ * SCVOD_ERR_INVALID before a device is looked for: NULL map, n < 0 or n > 2^31 - 1, NULL d_n, NULL d_component or d_verdict with n > 0,
+ * cap_components < 0, cap_records < 0, an unknown flag bit, reserved != 0, min_cells < 1, max_cells < 0, min_tested < 1, vote_den
+ * outside 1 .. 4096, vote_num outside 0 .. 4096, POOL_PAIRS without d_votes, d_component not 4-byte, d_n or d_votes or d_records not
+ * 8-byte aligned, a d_verdict_out that overlaps d_verdict without being equal to it or overlaps another argument. */
+#define SCVOD_CMPVIS_POOL_PAIRS 1 /* flags bit 0: the rule reads the members' pooled pair counters, not their verdict bytes */
+typedef struct scvod_component_visibility_params { /* 32 bytes */
+    int32_t flags;
+    int32_t min_cells;   /* >= 1: components with fewer records do not vote                             */
+    int32_t max_cells;   /* >= 0: nor components with more; 0: no upper limit                           */
+    int32_t min_tested;  /* >= 1: nor components with fewer members whose byte is KEEP or SEEN_THROUGH  */
+    int32_t min_through; /* any value                                                                   */
+    int32_t vote_num;    /* 0 .. 4096                                                                   */
+    int32_t vote_den;    /* 1 .. 4096                                                                   */
+    int32_t reserved;    /* 0                                                                           */
+} scvod_component_visibility_params;
+/* flags 0, min_cells 1, max_cells 0, min_tested 1, min_through 2, vote 1 / 2.  This project's values, NOT from real data. */
+void scvod_component_visibility_params_default(scvod_component_visibility_params* p);
+typedef struct scvod_component_visibility { /* 64 bytes, one per component, component order */
+    int32_t n_records;                                       /* members in the list                                           */
+    int32_t n_untested, n_keep, n_seen;                      /* members by verdict byte: 2 is seen, 1 keep, every other untested */
+    int64_t sum_through, sum_agree, sum_occluded, sum_empty; /* the four counters of d_votes over ALL members; 0 without d_votes */
+    int32_t verdict;                                         /* -1 none, SCVOD_VIS_KEEP, SCVOD_VIS_SEEN_THROUGH               */
+    int32_t how;                                             /* 0 no verdict, 1 voted                                         */
+    int32_t reserved[2];                                     /* 0                                                             */
+} scvod_component_visibility;
+int scvod_map_component_visibility(scvod_map* map, const int32_t* d_component, int64_t n, const int64_t* d_n, int64_t cap_components,
+                                   const uint8_t* d_verdict, const uint16_t* d_votes, const scvod_component_visibility_params* params,
+                                   void* d_records, int64_t cap_records, uint8_t* d_verdict_out, void* stream);
+/* h_out8 = {components (d_n), voted, SEEN_THROUGH, members moved to SEEN_THROUGH, members moved to KEEP, records written, components at
+ * or beyond cap_components, 1 after an overflow} of the last call.  Synchronises that call's stream.  SCVOD_ERR_CAPACITY after an
+ * overflow, with the words filled; SCVOD_ERR_STATE before the first call. */
+int scvod_map_component_visibility_stats(scvod_map* map, int64_t* h_out8);
+
 #ifdef __cplusplus
 }
 #endif
