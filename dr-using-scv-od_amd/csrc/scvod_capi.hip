@@ -3044,8 +3044,10 @@ static int read_counters(scvod_ctx* c, const unsigned long long* d_words, int n,
 
 static int nn_run(scvod_ctx* c, const float* d_map, int32_t n_map, const float* d_q, int32_t n_query, float radius,
                   int32_t* d_idx, float* d_sq, uint8_t* d_w, const float origin[3], int bounded, hipStream_t st) {
-    // grid: cell edge >= radius (so `within` is decided by the 27-cell probe); the origin only shifts the hash
-    const float cell = radius > 0.2f ? radius : 0.2f;
+    // grid: cell edge >= radius; the origin only shifts the hash.  The radius search answers from the 27 cells alone, which hold every
+    // point closer than 0.99 cell edges (launch_nn's h2) and no promise beyond: its cell is widened until radius^2 <= h2
+    float cell = radius > 0.2f ? radius : 0.2f;
+    if (bounded && radius * radius > (0.99f * cell) * (0.99f * cell)) cell = radius / 0.98f;
     const int32_t buckets = grid_buckets(n_map);
     const size_t nm = n_map ? n_map : 1, nq = n_query ? n_query : 1;
     const size_t work_ints = 3 * (size_t)buckets + nm + nq + 8 + (size_t)buckets / 1024 + 1;

@@ -1,10 +1,11 @@
 // scvod_k_nn_grid.inc -- uniform-grid correspondence search (A7).
 // Part of the kernels translation unit: included by scvod_kernels.hip (inside namespace scvod), never compiled on its own.
 // ---- uniform-grid correspondence search ------------------------------------------------------------
-// Map points are entered into the shared hash grid of scvod_grid.h (cell edge h >= radius); a query probes the 27 cells around it.
-// If the best candidate is within h it is the true nearest neighbour (anything outside the 27 cells is farther
-// than h); otherwise the query goes to the exact brute-force kernel.  Distances and tie-breaking (lowest map
-// index) are those of the brute-force kernel, so both paths return identical results.
+// Map points are entered into the shared hash grid of scvod_grid.h (cell edge h); a query probes the 27 cells around it.
+// If the best candidate is within 0.99 h it is the true nearest neighbour (anything outside the 27 cells is farther
+// than that; the 1 % covers the fp32 rounding of the cell coordinate, DESIGN.md A7); otherwise the query goes to the exact
+// brute-force kernel.  Distances and tie-breaking (lowest map index) are those of the brute-force kernel, so both paths return
+// identical results.  The radius search has no second kernel: its cell is chosen so that radius^2 <= (0.99 h)^2.
 
 // exclusive scan of `n` ints, three launches: per-block (1024) scans + block totals, scan of totals, add-back
 __global__ __launch_bounds__(1024) void k_scan_blocks(const int* in, int* out, int* block_tot, int n) {
@@ -43,17 +44,18 @@ __global__ __launch_bounds__(256) void k_nn_query(PointGrid g, float h2, const f
     float best = 0.f;
     int bi = -1;
     grid_probe27(g, map_xyz, 3, qx, qy, qz, best, bi);
-    if (bi >= 0 && best <= h2) {
-        nn_idx[q] = bi;
-        nn_sq[q] = best;
-        within[q] = best < r2 ? 1 : 0;
-    } else if (bounded) {
-        // radius search (pcl radiusSearch, evaluate.cpp:95,104): the cell edge is >= radius, so a neighbour inside the radius
-        // would have been among the candidates; accepted above whenever it is closer than 0.99 cell edges
+    if (bounded) {
+        // radius search (pcl radiusSearch, evaluate.cpp:95,104): the caller's cell has r2 <= h2 (nn_run), so every map point with
+        // d^2 < r2 is closer than 0.99 cell edges and therefore among the candidates: the best of them below r2 is the nearest
+        // point inside the radius, and none below r2 means none inside it
         const bool in = bi >= 0 && best < r2;
         nn_idx[q] = in ? bi : -1;
         nn_sq[q] = in ? best : __builtin_huge_valf();
         within[q] = in ? 1 : 0;
+    } else if (bi >= 0 && best <= h2) {
+        nn_idx[q] = bi;
+        nn_sq[q] = best;
+        within[q] = best < r2 ? 1 : 0;
     } else {
         todo[atomicAdd(n_todo, 1)] = q;  // exact answer needs the whole map
     }

@@ -552,22 +552,33 @@ int scvod_set_timing(scvod_ctx* ctx, int32_t enabled);
 /* ---- correspondence search (north_star "GICP correspondence search"; the reference's
  * real analogue is the kd-tree look-up of src/evaluate.cpp:79-145) ----------------------- */
 
+/* Range of the three searches below: they are exact while every map and query coordinate lies within 25 000 cell edges of the grid
+ * origin on each axis, |x - origin| <= 25000 * cell.  The cell edge is max(radius, 0.2f); scvod_nn_radius_search takes
+ * radius / 0.98f once radius exceeds 0.198.  The origin is the map's min corner in the two host forms and 0 in the device form, so
+ * a device-resident cloud searched with radius <= 0.2 may reach 5 km from the origin.  (The 27-cell probe allows the fp32 cell
+ * coordinate 1 % of a cell; its three roundings use up to 0.45 % per point at that range -- DESIGN.md, A7.)  Beyond the bound a
+ * neighbour may be missed.  Non-finite coordinates are unspecified: a NaN map point can poison a query's running best depending
+ * on the order inside a bucket. */
+
 /* For every query point: index of the nearest map point (ties: lowest index) and the
  * squared distance (fp32, ((dx*dx + dy*dy) + dz*dz)); h_within[q] = 1 if any map point
  * lies within `radius` (squared distance < radius^2: pcl radiusSearch non-empty, evaluate.cpp:95,104).  h_xyz arrays
- * are n x 3 floats. */
+ * are n x 3 floats.  Coordinates: finite, within 25 000 cell edges of the map's min corner (above). */
 int scvod_nn_search(scvod_ctx* ctx, const float* h_map_xyz, int32_t n_map,
                     const float* h_query_xyz, int32_t n_query, float radius,
                     int32_t* h_nn_idx, float* h_nn_sqdist, uint8_t* h_within);
 
 /* pcl::KdTreeFLANN::radiusSearch as src/evaluate.cpp:95,104 uses it (is anything inside the radius?): per query the
  * nearest map point with squared distance < radius^2 (FLANN keeps dist < r^2), or index -1 / distance +inf.  Unlike
- * scvod_nn_search it never looks beyond the radius, so queries far from the map cost one 27-cell probe. */
+ * scvod_nn_search it never looks beyond the radius, so queries far from the map cost one 27-cell probe: the cell edge is chosen so
+ * that radius^2 <= (0.99 cell)^2, and every map point inside the radius is among the 27 cells.  Coordinates: finite, within
+ * 25 000 cell edges of the map's min corner (above); the cell edge is max(radius, 0.2f), or radius / 0.98f above radius 0.198. */
 int scvod_nn_radius_search(scvod_ctx* ctx, const float* h_map_xyz, int32_t n_map, const float* h_query_xyz,
                            int32_t n_query, float radius, int32_t* h_nn_idx, float* h_nn_sqdist);
 
 /* The same search on arrays already resident in HBM (packed xyz, 12 B per point); asynchronous on `stream`
- * (NULL = the ctx's stream).  For sequence-scale evaluation without host round trips. */
+ * (NULL = the ctx's stream).  For sequence-scale evaluation without host round trips.  The grid origin is 0:
+ * coordinates are finite and |x| <= 25000 * max(radius, 0.2f) on every axis (above), 5 km for radius <= 0.2. */
 int scvod_nn_search_device(scvod_ctx* ctx, const float* d_map_xyz, int32_t n_map,
                            const float* d_query_xyz, int32_t n_query, float radius,
                            int32_t* d_nn_idx, float* d_nn_sqdist, uint8_t* d_within, void* stream);

@@ -832,7 +832,7 @@ def test_nn_search_parity(scvod, oracle):
 
 def test_nn_radius_search_parity(scvod, oracle):
     """The bounded path of the grid search (scvod_nn_radius_search): the nearest map point inside the radius or -1 / +inf, against the
-    brute-force oracle.  Radii >= 0.2: the cell edge is the radius."""
+    brute-force oracle.  Radii >= 0.2: the cell edge is radius / 0.98."""
     rng = np.random.default_rng(11)
     m = rng.uniform(-20, 20, (5000, 3)).astype(np.float32)
     q = np.concatenate([m[:500] + rng.normal(0, 0.05, (500, 3)).astype(np.float32),
