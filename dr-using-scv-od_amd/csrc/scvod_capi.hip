@@ -222,6 +222,12 @@ struct scvod_ctx {
     // accumulators) and 8 counter words of their own, allocated by the first call; not part of the arena or the table's scratch
     Scratch ov;  // stream / ran: the last call (scvod_batch_object_visibility_stats waits for it)
     unsigned long long* ov_counters = nullptr;
+    // the objects linked into tracks (scvod_object_tracks_device / scvod_batch_object_tracks, scvod_tracks.hip): a grow-only block (pose
+    // and successor tables, the per-object arrays, the scan's temporary storage) and 8 counter words of their own, allocated by the
+    // first call; not part of the arena or the table's scratch
+    Scratch trk;  // stream / ran: the last call (scvod_object_tracks_stats waits for it)
+    unsigned long long* trk_counters = nullptr;
+    std::vector<unsigned char> trk_host;  // the tables as built on the host (the upload is staged from a copy)
     // scan stacking (scvod_batch_stack_scans, scvod_stack.hip): the segment and tile tables, one grow-only block of their own allocated
     // by the first call; not part of the arena
     Scratch stk;
@@ -1567,6 +1573,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->ot_counters) hipFree(c->ot_counters);
     if (c->ov.buf) hipFree(c->ov.buf);
     if (c->ov_counters) hipFree(c->ov_counters);
+    if (c->trk.buf) hipFree(c->trk.buf);
+    if (c->trk_counters) hipFree(c->trk_counters);
     if (c->stk.buf) hipFree(c->stk.buf);
     if (c->vis.buf) hipFree(c->vis.buf);
     if (c->vis_counters) hipFree(c->vis_counters);
@@ -3718,6 +3726,144 @@ int scvod_batch_object_visibility_stats(scvod_ctx* c, int64_t* h_out8) {
 
 int64_t scvod_batch_object_visibility_scratch_bytes(scvod_ctx* c) {
     return c ? (int64_t)c->ov.cap + (c->ov_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+}
+
+// ---- the objects of a table linked into tracks (scvod_tracks.hip) ----
+// what both forms refuse before a device is touched; *p receives the parameters in force
+static int trk_check(scvod_ctx* c, const scvod_track_params* params, scvod_track_params* p, const void* d_objects, const void* d_links,
+                     int64_t cap_links, const void* d_tracks, int64_t cap_tracks, const void* d_track_objects, const void* d_n_tracks) {
+    if (params)
+        *p = *params;
+    else
+        scvod_track_params_default(p);
+    if (p->flags & ~(SCVOD_TRK_NO_GATE | SCVOD_TRK_ANY_CLASS)) return fail(c, SCVOD_ERR_INVALID, "unknown flag bit (flags %d)", p->flags);
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(c, SCVOD_ERR_INVALID, "scvod_track_params::reserved must be 0");
+    if (p->occupancy != p->occupancy) return fail(c, SCVOD_ERR_INVALID, "occupancy is NaN");
+    if (!(p->gate > 0.f) || !std::isfinite(p->gate)) return fail(c, SCVOD_ERR_INVALID, "gate %g: a positive finite number of metres", (double)p->gate);
+    if (!(p->size_ratio >= 1.f)) return fail(c, SCVOD_ERR_INVALID, "size_ratio %g below 1", (double)p->size_ratio);
+    if (p->min_points < 1 || p->min_length < 1)
+        return fail(c, SCVOD_ERR_INVALID, "min_points %d, min_length %d: both at least 1", p->min_points, p->min_length);
+    if (cap_links < 0 || cap_tracks < 0 || cap_links > 2147483647ll) return fail(c, SCVOD_ERR_INVALID, "cap_links %lld / cap_tracks %lld", (long long)cap_links, (long long)cap_tracks);
+    if (cap_links > 0 && !d_objects) return fail(c, SCVOD_ERR_INVALID, "NULL d_objects with cap_links %lld", (long long)cap_links);
+    if ((uintptr_t)d_objects & 7u) return fail(c, SCVOD_ERR_INVALID, "d_objects is not 8-byte aligned");
+    if (((uintptr_t)d_links & 3u) || ((uintptr_t)d_tracks & 3u) || ((uintptr_t)d_track_objects & 3u) || ((uintptr_t)d_n_tracks & 3u))
+        return fail(c, SCVOD_ERR_INVALID, "d_links, d_tracks, d_track_objects and d_n_tracks must be 4-byte aligned");
+    if (p->occupancy < 0.f) p->occupancy = c->params.occupancy;
+    return SCVOD_OK;
+}
+
+// the successor table of n_scans scans under scvod_visibility_viewers' rules -> next (negative: none)
+static int trk_next_table(scvod_ctx* c, const int32_t* h_next_scan, int n_scans, std::vector<int32_t>& next) {
+    std::vector<int32_t> begin, viewers;
+    if (vis_viewers(h_next_scan, n_scans, 0, 1, begin, viewers))
+        return fail(c, SCVOD_ERR_INVALID, "object tracks: the successor table names a scan outside the batch, a scan itself, one successor twice or a ring");
+    next.resize((size_t)n_scans);
+    for (int s = 0; s < n_scans; ++s) {
+        const int32_t v = h_next_scan ? h_next_scan[s] : (s + 1 < n_scans ? s + 1 : -1);
+        next[s] = v < 0 ? -1 : v;
+    }
+    return SCVOD_OK;
+}
+
+static int trk_run(scvod_ctx* c, TrkJob J, const std::vector<int32_t>& next, const float* h_poses, const int32_t* scan_cnt, hipStream_t st) {
+    const size_t B = (size_t)J.n_scans, b_T = align_up(sizeof(float) * 12 * B, 256), b_tab = b_T + sizeof(int32_t) * B;
+    c->trk_host.assign(b_tab > 0 ? b_tab : 1, 0);
+    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (size_t s = 0; s < B; ++s) scvod_pose_matrix(h_poses ? h_poses + 6 * s : zero, (float*)c->trk_host.data() + 12 * s);
+    if (B) memcpy(c->trk_host.data() + b_T, next.data(), sizeof(int32_t) * B);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = counter_block(c, &c->trk_counters, 8)) return rc;
+    if (int rc = scratch_reserve(c, c->trk, trk_work_bytes(J.cap, J.n_scans))) return rc;  // (waits for the call in flight before the block moves)
+    c->trk.stream = st;
+    c->trk.ran = true;
+    HIPCHK(c, hipMemsetAsync(c->trk_counters, 0, 8 * sizeof(unsigned long long), st));
+    if (B)
+        if (int rc = staged_upload(c, c->trk_host.data(), b_tab, c->trk.buf, st)) return rc;
+    J.counters = c->trk_counters;
+    const hipError_t e = launch_object_tracks(c->A, J, scan_cnt, c->trk.buf, st);
+    if (e != hipSuccess) return fail(c, SCVOD_ERR_HIP, "object tracks: %s", hipGetErrorString(e));
+    return SCVOD_OK;
+}
+
+static void trk_fill(TrkJob& J, const scvod_track_params& p, const void* d_objects, void* d_links, int64_t cap_links, void* d_tracks,
+                     int64_t cap_tracks, int32_t* d_track_objects, int32_t* d_n_tracks) {
+    J.objects = (const scvod_object*)d_objects;
+    J.cap = (long long)cap_links;
+    J.flags = p.flags;
+    J.min_points = p.min_points;
+    J.min_length = p.min_length;
+    J.occupancy = p.occupancy;
+    J.gate2 = p.gate * p.gate;
+    J.size_ratio = p.size_ratio;
+    J.out_links = (scvod_object_link*)d_links;
+    J.out_tracks = (scvod_track*)d_tracks;
+    J.cap_tracks = (long long)cap_tracks;
+    J.out_tobj = d_track_objects;
+    J.n_tracks = d_n_tracks;
+}
+
+int scvod_object_tracks_device(scvod_ctx* c, const void* d_objects, const int32_t* d_obj_offsets, int32_t n_scans, const int32_t* h_next_scan,
+                               const float* h_poses, const int32_t* d_cand_begin, const void* d_cand, const scvod_track_params* params,
+                               void* d_links, int64_t cap_links, void* d_tracks, int64_t cap_tracks, int32_t* d_track_objects,
+                               int32_t* d_n_tracks, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    scvod_track_params p;
+    if (int rc = trk_check(c, params, &p, d_objects, d_links, cap_links, d_tracks, cap_tracks, d_track_objects, d_n_tracks)) return rc;
+    if (n_scans < 0) return fail(c, SCVOD_ERR_INVALID, "n_scans below 0");
+    if (!d_obj_offsets || ((uintptr_t)d_obj_offsets & 3u)) return fail(c, SCVOD_ERR_INVALID, "d_obj_offsets is NULL or not 4-byte aligned");
+    if (d_cand && !d_cand_begin) return fail(c, SCVOD_ERR_INVALID, "d_cand without d_cand_begin");
+    if (((uintptr_t)d_cand & 7u) || ((uintptr_t)d_cand_begin & 3u)) return fail(c, SCVOD_ERR_INVALID, "d_cand must be 8-byte, d_cand_begin 4-byte aligned");
+    std::vector<int32_t> next;
+    if (int rc = trk_next_table(c, h_next_scan, n_scans, next)) return rc;
+    TrkJob J{};
+    trk_fill(J, p, d_objects, d_links, cap_links, d_tracks, cap_tracks, d_track_objects, d_n_tracks);
+    J.obj_off = d_obj_offsets;
+    J.n_scans = n_scans;
+    J.cand_begin = d_cand ? d_cand_begin : nullptr;
+    J.cand = (const int2*)d_cand;
+    return trk_run(c, J, next, h_poses, nullptr, stream ? (hipStream_t)stream : c->stream);
+}
+
+int scvod_batch_object_tracks(scvod_ctx* c, const void* d_objects, const float* h_poses, const scvod_track_params* params, void* d_links,
+                              int64_t cap_links, void* d_tracks, int64_t cap_tracks, int32_t* d_track_objects, int32_t* d_n_tracks,
+                              void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    scvod_track_params p;
+    if (int rc = trk_check(c, params, &p, d_objects, d_links, cap_links, d_tracks, cap_tracks, d_track_objects, d_n_tracks)) return rc;
+    if (!d_objects) return fail(c, SCVOD_ERR_INVALID, "NULL d_objects");
+    const long long* tab_stats = nullptr;
+    const uint64_t* key_out = nullptr;
+    const int32_t* begin = nullptr;
+    const char* why = "";
+    if (!c->obj_lists_serial) return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_tracks needs a scvod_batch_objects that asked for records or members");
+    if (!c->obj_lists_track) return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_tracks: the table was made with SCVOD_OBJ_NO_TRACK");
+    if (!c->track_valid) return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_tracks needs a current scvod_batch_track");
+    if (int rc = scvod__ctx_object_lists(c, "scvod_batch_object_tracks", &tab_stats, &key_out, &begin, &why)) return rc;
+    const int B = c->A.n_scans;
+    if ((int)c->up_next.size() != B) return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_tracks: the ctx holds no successor table of this batch");
+    std::vector<int32_t> next;
+    if (int rc = trk_next_table(c, c->up_next.data(), B, next)) return rc;
+    TrkJob J{};
+    trk_fill(J, p, d_objects, d_links, cap_links, d_tracks, cap_tracks, d_track_objects, d_n_tracks);
+    J.n_scans = B;
+    J.root_obj = c->obj_words;  // what the table left in its scratch, read only
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    return trk_run(c, J, next, h_poses, c->obj_scan_cnt, st);
+}
+
+int scvod_object_tracks_stats(scvod_ctx* c, int64_t* h_out8) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->trk.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_object_tracks_device / scvod_batch_object_tracks on this ctx yet");
+    if (int rc = read_counters(c, c->trk_counters, 8, c->trk.stream, h_out8)) return rc;
+    if (h_out8[7])
+        return fail(c, SCVOD_ERR_CAPACITY, "object tracks: %lld objects, %lld listed tracks, %lld track records written: a capacity was too small",
+                    (long long)h_out8[0], (long long)h_out8[1], (long long)h_out8[2]);
+    return SCVOD_OK;
+}
+
+int64_t scvod_object_tracks_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->trk.cap + (c->trk_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
 }
 
 void scvod_object_truth_params_default(scvod_object_truth_params* p) {

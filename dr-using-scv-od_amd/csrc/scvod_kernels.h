@@ -585,6 +585,39 @@ struct ObjVisJob {
 size_t objvis_work_bytes(long long total_pts);
 void launch_object_visibility(const Arena& A, ObjVisJob J, void* work, hipStream_t st);
 
+// the objects of a table linked into tracks (scvod_object_tracks_device / scvod_batch_object_tracks; scvod_tracks.hip).  work:
+// trk_work_bytes bytes; its first trk_tables_bytes hold the pose matrices [n_scans][12] and the successor table [n_scans], each rounded
+// up to 256 bytes, staged by the caller.  counters: the 8 words of scvod_object_tracks_stats, cleared by the caller on the stream
+enum { kTrkStObjects = 0, kTrkStFound, kTrkStWritten, kTrkStKind1, kTrkStKind2, kTrkStRefused, kTrkStLongest, kTrkStOverflow };
+struct TrkJob {
+    const scvod_object* objects;   // caller's records
+    const int32_t* obj_off;        // [n_scans + 1] caller's offsets (device); the batch form: made from the table's scan counts
+    int32_t n_scans;
+    long long cap;                 // records the caller vouches for (cap_links)
+    const int32_t* cand_begin;     // [objects + 1] and
+    const int2* cand;              //   (successor object, count): the caller's overlap candidates, or nullptr
+    const int32_t* root_obj;       // batch form: the table's root_obj; the candidates are the arena's remap_name pairs then
+    int32_t flags, min_points, min_length;
+    float occupancy, gate2, size_ratio;  // gate2 = gate * gate in fp32
+    scvod_object_link* out_links;  // caller's outputs, each may be nullptr
+    scvod_track* out_tracks;
+    long long cap_tracks;
+    int32_t* out_tobj;
+    int32_t* n_tracks;
+    unsigned long long* counters;
+    // filled by launch_object_tracks: slices of `work`
+    const float* T;
+    const int32_t* next;
+    float4* cw;                    // world centre, box diagonal
+    unsigned long long *slot, *prop_key, *chain, *val, *pre;
+    scvod_object_link* links;
+    int32_t *prop_b, *rank[2], *jump[2], *tobj, *heads;
+};
+int trk_rounds(int n_scans);  // pointer-jumping rounds: ceil(log2(max(n_scans, 2)))
+size_t trk_tables_bytes(int n_scans);
+size_t trk_work_bytes(long long cap, int n_scans);
+hipError_t launch_object_tracks(const Arena& A, TrkJob J, const int32_t* scan_cnt, void* work, hipStream_t st);
+
 // a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the shared one (grid_buckets, grid_work_ints)
 // over the base cloud with the caller's cell edge; work: sp_work_bytes bytes; stats: the 8 words of scvod_map_split_stats, written by
 // every launch.  The optional outputs of SpJob are nullptr when not asked for; mark == nullptr: a byte array inside `work`

@@ -204,6 +204,34 @@ OBJECT_VISIBILITY_DTYPE = np.dtype([("n_points", "<i4"), ("n_untested", "<i4"), 
 assert OBJECT_VISIBILITY_DTYPE.itemsize == 48
 
 
+class TrackParams(C.Structure):
+    """scvod_track_params (include/scvod.h), 32 bytes"""
+    _fields_ = [("flags", C.c_int32), ("occupancy", C.c_float), ("gate", C.c_float), ("size_ratio", C.c_float),
+                ("min_points", C.c_int32), ("min_length", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class TracksResult(C.Structure):
+    """scvod_tracks_result (include/scvod.h), 72 bytes"""
+    _fields_ = [("tracks", C.c_int64), ("moving_tracks", C.c_int64), ("moving_members", C.c_int64),
+                ("moving_members_dynamic", C.c_int64), ("still_tracks", C.c_int64), ("still_members", C.c_int64),
+                ("still_members_dynamic", C.c_int64), ("recall_along", C.c_double), ("false_alarm", C.c_double)]
+
+
+TRK_NO_GATE = 1                                       # SCVOD_TRK_NO_GATE
+TRK_ANY_CLASS = 2                                     # SCVOD_TRK_ANY_CLASS
+TRK_OUTPUTS = ("links", "tracks", "track_objects", "n_tracks")
+TRK_STATS = ("objects", "tracks", "written", "overlap_links", "gate_links", "refused", "longest", "overflow")
+# struct scvod_object_link: how one object of the table continues across scans (scvod_object_tracks_device), 32 bytes
+OBJECT_LINK_DTYPE = np.dtype([("track", "<i4"), ("rank", "<i4"), ("pred", "<i4"), ("succ", "<i4"), ("kind", "<i4"), ("weight", "<i4"),
+                              ("step", "<f4"), ("reserved", "<i4")])
+assert OBJECT_LINK_DTYPE.itemsize == 32
+# struct scvod_track: one listed track, 64 bytes
+TRACK_DTYPE = np.dtype([("first_object", "<i4"), ("last_object", "<i4"), ("length", "<i4"), ("first_scan", "<i4"), ("last_scan", "<i4"),
+                        ("n_dynamic", "<i4"), ("n_gate_links", "<i4"), ("object_begin", "<i4"), ("net", "<f4", 3), ("path", "<f4"),
+                        ("max_step", "<f4"), ("reserved", "<i4", 3)])
+assert TRACK_DTYPE.itemsize == 64
+
+
 class ComponentVisibilityParams(C.Structure):
     """scvod_component_visibility_params (include/scvod.h), 32 bytes"""
     _fields_ = [("flags", C.c_int32), ("min_cells", C.c_int32), ("max_cells", C.c_int32), ("min_tested", C.c_int32),
@@ -456,6 +484,12 @@ def load_lib():
         "scvod_batch_object_visibility": (C.c_int, [vp, vp, vp, vp, C.POINTER(ObjectVisibilityParams), vp, i64, vp, vp]),
         "scvod_batch_object_visibility_stats": (C.c_int, [vp, vp]),
         "scvod_batch_object_visibility_scratch_bytes": (i64, [vp]),
+        "scvod_track_params_default": (None, [C.POINTER(TrackParams)]),
+        "scvod_object_tracks_device": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(TrackParams), vp, i64, vp, i64, vp, vp, vp]),
+        "scvod_batch_object_tracks": (C.c_int, [vp, vp, vp, C.POINTER(TrackParams), vp, i64, vp, i64, vp, vp, vp]),
+        "scvod_object_tracks_stats": (C.c_int, [vp, vp]),
+        "scvod_object_tracks_scratch_bytes": (i64, [vp]),
+        "scvod_tracks_finish": (C.c_int, [vp, i64, C.c_double, C.POINTER(TracksResult)]),
         "scvod_map_components": (C.c_int, [vp, vp, i64, i32, vp, vp, i64, vp, vp]),
         "scvod_map_components_stats": (C.c_int, [vp, vp]),
         "scvod_map_components_scratch_bytes": (i64, [vp]),
@@ -506,7 +540,9 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_cloud_visibility_scratch_bytes",
                     "scvod_object_visibility_params_default", "scvod_batch_object_visibility", "scvod_batch_object_visibility_stats",
                     "scvod_batch_object_visibility_scratch_bytes",
-                    "scvod_map_components", "scvod_map_components_stats", "scvod_map_components_scratch_bytes",
+                    "scvod_track_params_default", "scvod_object_tracks_device", "scvod_batch_object_tracks", "scvod_object_tracks_stats",
+                    "scvod_object_tracks_scratch_bytes", "scvod_tracks_finish",
+                    "scvod_map_components","scvod_map_components_stats", "scvod_map_components_scratch_bytes",
                     "scvod_component_visibility_params_default", "scvod_map_component_visibility",
                     "scvod_map_component_visibility_stats",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
@@ -685,6 +721,28 @@ def object_visibility_params_default(**kw):
         assert hasattr(p, k), k
         setattr(p, k, v)
     return p
+
+
+def track_params_default(**kw):
+    """scvod_track_params with the defaults (flags 0, occupancy -1 = the ctx's, gate 2.0, size_ratio 1.5, min_points 10, min_length 2:
+    this project's values, not from real data and untuned), overridden by keyword"""
+    p = TrackParams()
+    load_lib().scvod_track_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert k in {f[0] for f in TrackParams._fields_} - {"reserved"}, k
+        setattr(p, k, v)
+    return p
+
+
+def tracks_finish(tracks, min_travel):
+    """TRACK_DTYPE records -> the dict of scvod_tracks_result: tracks, moving / still tracks, members and dynamic members, and the two
+    rates in percent (NaN for a zero denominator); a track moves iff |net| >= min_travel.  Host only"""
+    t = np.ascontiguousarray(tracks, TRACK_DTYPE).reshape(-1)
+    r = TracksResult()
+    rc = load_lib().scvod_tracks_finish(t.ctypes.data_as(C.c_void_p) if t.size else None, int(t.size), float(min_travel), C.byref(r))
+    if rc != 0:
+        raise RuntimeError(f"scvod_tracks_finish failed with status {rc}")
+    return {k: getattr(r, k) for k, _ in TracksResult._fields_}
 
 
 def component_visibility_params_default(**kw):
@@ -1661,6 +1719,76 @@ class Ctx:
     def batch_object_visibility_scratch_bytes(self):
         """device scratch of the stage on this ctx (not part of arena_bytes or batch_objects_scratch_bytes)"""
         return int(self.lib.scvod_batch_object_visibility_scratch_bytes(self.h))
+
+    # ---- the objects of a table linked into tracks (include/scvod.h: scvod_object_tracks_device) ----
+    @staticmethod
+    def _tracks_outputs(dev, cap_links, cap_tracks, want, guard):
+        """the output tensors of a tracks call: name -> uint8 / int32 device tensor with `guard` extra rows behind the capacity (filled
+        with 0xA5 bytes, for tests), and the capacity-sized views"""
+        import torch
+        want = TRK_OUTPUTS if want is None else tuple(want)
+        assert all(w in TRK_OUTPUTS for w in want), want
+        rows = {"links": (cap_links, OBJECT_LINK_DTYPE.itemsize), "tracks": (cap_tracks, TRACK_DTYPE.itemsize),
+                "track_objects": (cap_links, 4), "n_tracks": (1, 4)}
+        full = {w: torch.full((rows[w][0] + guard + 1, rows[w][1]), 0xA5, dtype=torch.uint8, device=dev) for w in want}
+        return full, {w: full[w][:rows[w][0]] for w in want}
+
+    def object_tracks_device(self, d_objects, d_obj_offsets, n_scans, next_scan=None, poses=None, d_cand_begin=None, d_cand=None,
+                             params=None, cap_links=None, cap_tracks=None, want=None, guard=0, stream=None, full=False):
+        """scvod_object_tracks_device on the caller's table: d_objects a contiguous device tensor of 64-byte OBJECT_DTYPE rows,
+        d_obj_offsets int32 [n_scans + 1] (device), next_scan / poses host arrays or None, d_cand_begin int32 [objects + 1] and d_cand
+        int32 [pairs, 2] device tensors or None.  cap_links None: the rows of d_objects; cap_tracks None: cap_links.  Returns a dict of
+        uint8 device tensors, one per name in `want` (TRK_OUTPUTS; None: all): links [cap_links, 32] (OBJECT_LINK_DTYPE), tracks
+        [cap_tracks, 64] (TRACK_DTYPE), track_objects [cap_links, 4] (int32), n_tracks [1, 4] (int32); the rows behind what was written
+        hold 0xA5 bytes.  full=True: (views, the tensors with their `guard` rows behind).  Stream-ordered"""
+        nbytes = d_objects.numel() * d_objects.element_size()
+        assert d_objects.is_contiguous() and nbytes % OBJECT_DTYPE.itemsize == 0
+        cap_links = nbytes // OBJECT_DTYPE.itemsize if cap_links is None else int(cap_links)
+        cap_tracks = cap_links if cap_tracks is None else int(cap_tracks)
+        nx = None if next_scan is None else np.ascontiguousarray(next_scan, np.int32)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert (nx is None or nx.shape[0] == n_scans) and (p is None or p.shape[0] == n_scans)
+        whole, out = self._tracks_outputs(d_objects.device, cap_links, cap_tracks, want, guard)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.scvod_object_tracks_device(
+            self.h, ptr(d_objects), ptr(d_obj_offsets), int(n_scans), None if nx is None else nx.ctypes.data_as(C.c_void_p),
+            None if p is None else p.ctypes.data_as(C.c_void_p), ptr(d_cand_begin), ptr(d_cand),
+            C.byref(params) if params is not None else None, ptr(whole.get("links")), cap_links, ptr(whole.get("tracks")), cap_tracks,
+            ptr(whole.get("track_objects")), ptr(whole.get("n_tracks")), C.c_void_p(stream or 0)))
+        return (out, whole) if full else out
+
+    def batch_object_tracks(self, d_objects, poses=None, params=None, cap_links=None, cap_tracks=None, want=None, guard=0, stream=None,
+                            full=False):
+        """scvod_batch_object_tracks: the same on the table the last batch_objects (with lists, with tracking) left; d_objects are the
+        records that call wrote; the successor table is the one the last batch_track was given.  Outputs as object_tracks_device"""
+        nbytes = d_objects.numel() * d_objects.element_size()
+        assert d_objects.is_contiguous() and nbytes % OBJECT_DTYPE.itemsize == 0
+        cap_links = nbytes // OBJECT_DTYPE.itemsize if cap_links is None else int(cap_links)
+        cap_tracks = cap_links if cap_tracks is None else int(cap_tracks)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == self._n_scans
+        whole, out = self._tracks_outputs(d_objects.device, cap_links, cap_tracks, want, guard)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.scvod_batch_object_tracks(
+            self.h, ptr(d_objects), None if p is None else p.ctypes.data_as(C.c_void_p), C.byref(params) if params is not None else None,
+            ptr(whole.get("links")), cap_links, ptr(whole.get("tracks")), cap_tracks, ptr(whole.get("track_objects")), ptr(whole.get("n_tracks")),
+            C.c_void_p(stream or 0)))
+        return (out, whole) if full else out
+
+    def object_tracks_stats(self):
+        """{objects, tracks, written, overlap_links, gate_links, refused, longest, overflow} of the last tracks call of either form;
+        synchronises its stream; raises after an overflow"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_object_tracks_stats(self.h, o))
+        return dict(zip(TRK_STATS, (int(v) for v in o)))
+
+    def object_tracks_scratch_bytes(self):
+        """device scratch of the stage on this ctx (not part of arena_bytes or batch_objects_scratch_bytes)"""
+        return int(self.lib.scvod_object_tracks_scratch_bytes(self.h))
 
     # ---- a cloud against every scan's range image (include/scvod.h: scvod_cloud_visibility_device) ----
     def cloud_visibility(self, d_xyzi, d_images, poses, params=None, flags=0, want=("votes", "verdict"), stream=None):

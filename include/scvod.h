@@ -1601,6 +1601,120 @@ int scvod_batch_object_visibility_stats(scvod_ctx* ctx, int64_t* h_out8);
 /* bytes of device scratch the stage holds on this ctx (0 before the first call) */
 int64_t scvod_batch_object_visibility_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- the objects of a batch linked into tracks (opt-in: nothing runs or is allocated unless it is called; csrc/scvod_tracks.hip) ----
+ * Reference analogue: Cluster::track_id (src/ssc.cpp:1266-1272, 1356, 1381, 1400) keeps an identity across scans, but its ids depend
+ * on unordered_map iteration order and by construction never follow a moving object (a dynamic cluster is one without an overlapping
+ * successor).  The rule below is this project's convention; gate and size_ratio are NOT from real data and
+ * untuned.  The object table says what every cluster of every scan is; this stage says which object of the successor scan is the same
+ * one.  Let A be an object of scan s and nx = next[s] >= 0:
+ *   world centre  cW(A) = scvod_pose_matrix(pose_s) applied to A.center: T0*x + T1*y + T2*z + T3 per row, left to right in fp32
+ *                 without contraction (the map kernel's expression)
+ *   overlap (kind 1)  among A's candidates (B, count) -- B an object of scan nx, count >= 0 -- those with A.cls == 2, B.cls == 2 and
+ *                 (float)count / (float)B.n_voxels >= occupancy; the largest count wins, ties to the smaller B.  This mirrors the
+ *                 inheritance of ssc.cpp:1378-1385, 1408, first order
+ *   gate (kind 2) only without a kind-1 proposal and without SCVOD_TRK_NO_GATE.  A needs cls == 2 (SCVOD_TRK_ANY_CLASS: any class)
+ *                 and n_points >= min_points; every object B of scan nx with B.cls == A.cls, B.n_points >= min_points,
+ *                 diag(A) <= size_ratio * diag(B), diag(B) <= size_ratio * diag(A) and d2 < gate * gate (the fp32 product) is
+ *                 considered; diag = sqrtf((ex*ex + ey*ey) + ez*ez) of the box extents, d2 = (dx*dx + dy*dy) + dz*dz of the world
+ *                 centres in fp32; the smallest d2 wins, ties to the smaller B; a NaN never qualifies
+ *   acceptance    B accepts one proposer: kind 1 before kind 2, then the larger count (kind 1) or the smaller d2 (kind 2), then the
+ *                 smaller A.  A refused proposer has no successor, makes no second proposal and is counted.  An accepted pair is a
+ *                 link; step(B) = sqrtf(d2(A, B)), correctly rounded, for either kind
+ *   tracks        the chains of links; a track is LISTED iff length >= min_length.  Tracks end at the batch's edge and at an external
+ *                 successor table: nothing is carried across batches or shards
+ * Every output is bit-identical from run to run and for any launch geometry. */
+#define SCVOD_TRK_NO_GATE 1   /* flags bit 0: overlap links only */
+#define SCVOD_TRK_ANY_CLASS 2 /* flags bit 1: the gate links objects of equal cls, not only cars */
+typedef struct scvod_track_params { /* 32 bytes */
+    int32_t flags;
+    float occupancy;     /* negative: the ctx's params.occupancy; NaN is refused                    */
+    float gate;          /* metres, > 0 and finite                                                   */
+    float size_ratio;    /* >= 1                                                                     */
+    int32_t min_points;  /* >= 1: smaller objects neither propose through the gate nor are proposed to */
+    int32_t min_length;  /* >= 1: shorter chains are not listed                                      */
+    int32_t reserved[2]; /* 0                                                                        */
+} scvod_track_params;
+/* flags 0, occupancy -1, gate 2.0f, size_ratio 1.5f, min_points 10, min_length 2.  This project's values, NOT from real data. */
+void scvod_track_params_default(scvod_track_params* p);
+typedef struct scvod_object_link { /* 32 bytes, one per object of the table, table order */
+    int32_t track;    /* index in the track table, -1 when the object's track is not listed          */
+    int32_t rank;     /* number of predecessors along accepted links                                  */
+    int32_t pred;     /* table index of the object of the scan before that this one continues, or -1  */
+    int32_t succ;     /* table index of the object that continues this one, or -1                     */
+    int32_t kind;     /* how pred was linked: 0 none, 1 overlap, 2 gate                               */
+    int32_t weight;   /* the overlap count for kind 1, else 0                                         */
+    float step;       /* world-frame centre distance to pred, 0 without one                           */
+    int32_t reserved; /* 0                                                                            */
+} scvod_object_link;
+typedef struct scvod_track { /* 64 bytes, one per listed track, ascending by first_object */
+    int32_t first_object, last_object; /* table indices of the members with rank 0 and rank length - 1                             */
+    int32_t length;                    /* members                                                                                   */
+    int32_t first_scan, last_scan;     /* scvod_object::scan of the two                                                             */
+    int32_t n_dynamic;                 /* members with dynamic == 1                                                                 */
+    int32_t n_gate_links;              /* members with kind == 2                                                                    */
+    int32_t object_begin;              /* first slot of its run in the track-object list: the member of rank r is at object_begin + r */
+    float net[3];                      /* cW(last) - cW(first), per component in fp32                                               */
+    float path;                        /* the members' step values summed in rank order, sequentially from 0.0f in fp32              */
+    float max_step;                    /* the largest step that is not NaN; 0 without one                                            */
+    int32_t reserved[3];               /* 0                                                                                         */
+} scvod_track;
+/* The device form works on the caller's tables, so it can be driven with crafted input.
+ *   d_objects        the 64-byte records scvod_batch_objects writes; read are scan, n_points, n_voxels, box_*, center, cls, dynamic
+ *   d_obj_offsets    [n_scans + 1] device array, what scvod_batch_objects writes; the true object count is d_obj_offsets[n_scans], read on
+ *                    the device
+ *   h_next_scan      [n_scans] or NULL (s + 1, none for the last scan), with the conventions and refusals of scvod_visibility_viewers: a
+ *                    negative entry ends the chain; two scans with one successor, a scan that names itself, a ring or an entry >= n_scans
+ *                    are refused
+ *   h_poses          [n_scans][6] or NULL: the zero pose for every scan; staged before the call returns
+ *   d_cand_begin     [objects + 1] and d_cand, int32 pairs (table index of a successor object, count): the overlap candidates of every
+ *                    object.  Both may be NULL: none.  A pair whose object is not of the successor scan or whose count is negative is
+ *                    skipped
+ *   d_links          [cap_links] scvod_object_link or NULL.  cap_links is also the number of records of d_objects (and of entries of
+ *                    d_cand_begin, less one) the caller vouches for: MORE OBJECTS THAN cap_links IS AN OVERFLOW, and then nothing is
+ *                    linked and nothing is written but d_n_tracks[0] = -1
+ *   d_tracks         [cap_tracks] scvod_track or NULL.  Nothing is written at or behind cap_tracks; more listed tracks than cap_tracks is
+ *                    an overflow (d_n_tracks[0] = -1; the links and the track-object list are complete all the same)
+ *   d_track_objects  [cap_links] int32 or NULL: the listed tracks' objects, track after track in rank order
+ *   d_n_tracks       [1] int32 (device) or NULL: the listed tracks, or -1 after an overflow
+ * Stream-ordered (stream NULL = the ctx's stream); never synchronises with the host except to grow its scratch (about 130 bytes per
+ * record of cap_links, 56 bytes per scan, rocprim's temporary storage of a scan, 8 counter words: a grow-only allocation of its own,
+ * NOT part of scvod_arena_bytes and no other stage's scratch).  It touches neither the arena nor any batch state.  params NULL: the
+ * defaults.  SCVOD_ERR_INVALID before a device is looked for: NULL ctx, an unknown flag bit, a reserved word that is not 0, an
+ * occupancy that is NaN, a gate that is <= 0 or not finite, size_ratio < 1 (or NaN), min_points < 1, min_length < 1, a refused successor
+ * table, n_scans < 0, cap_links or cap_tracks < 0 or cap_links > 2^31 - 1, NULL d_obj_offsets, NULL d_objects with cap_links > 0, d_cand
+ * without d_cand_begin, d_objects or d_cand not 8-byte aligned, any other pointer not 4-byte aligned. */
+int scvod_object_tracks_device(scvod_ctx* ctx, const void* d_objects, const int32_t* d_obj_offsets, int32_t n_scans,
+                               const int32_t* h_next_scan, const float* h_poses, const int32_t* d_cand_begin, const void* d_cand,
+                               const scvod_track_params* params, void* d_links, int64_t cap_links, void* d_tracks, int64_t cap_tracks,
+                               int32_t* d_track_objects, int32_t* d_n_tracks, void* stream);
+/* The same on the table the last scvod_batch_objects (with lists) left in the ctx's scratch: d_objects are the records that call wrote
+ * (cap_links of them).  The state rules are those of scvod_batch_object_shapes, and a CURRENT scvod_batch_track is needed besides: a
+ * SCVOD_OBJ_NO_TRACK table is SCVOD_ERR_STATE.  The successor table is the ctx's copy from that track call (SCVOD_ERR_INVALID when the
+ * rules above refuse it).  The candidates of object A are the first-order remap_name pairs of its root in the arena (what
+ * scvod_batch_fetch_track reports as pair_label / pair_count), each label mapped to the object of the successor scan with that name; a
+ * label that names no object of the table yields no candidate, and a successor that is an external table yields no candidates and no
+ * link.  The arena, the table's scratch and scvod_arena_bytes do not change.  Stream NULL = the stream of the ctx's last batch call. */
+int scvod_batch_object_tracks(scvod_ctx* ctx, const void* d_objects, const float* h_poses, const scvod_track_params* params, void* d_links,
+                              int64_t cap_links, void* d_tracks, int64_t cap_tracks, int32_t* d_track_objects, int32_t* d_n_tracks,
+                              void* stream);
+/* h_out8 = {objects, listed tracks found, track records written, kind-1 links, kind-2 links, proposals refused, longest listed track,
+ * 1 after an overflow} of the last call of either form.  After a cap_links overflow only words 0 and 7 are filled.  Synchronises that
+ * call's stream.  SCVOD_ERR_CAPACITY after an overflow, with the words filled; SCVOD_ERR_STATE before the first call. */
+int scvod_object_tracks_stats(scvod_ctx* ctx, int64_t* h_out8);
+/* bytes of device scratch the stage holds on this ctx (0 before the first call) */
+int64_t scvod_object_tracks_scratch_bytes(scvod_ctx* ctx);
+/* Host only, no device, evaluated in double.  A track is MOVING iff sqrt(net . net) >= min_travel, STILL otherwise.  The rates are in
+ * percent, NaN for a zero denominator.  SCVOD_ERR_INVALID for a NULL out, n < 0 or NULL tracks with n > 0. */
+typedef struct scvod_tracks_result { /* 72 bytes */
+    int64_t tracks;
+    int64_t moving_tracks, moving_members, moving_members_dynamic;
+    int64_t still_tracks, still_members, still_members_dynamic;
+    double recall_along; /* moving_members_dynamic / (moving_members - moving_tracks): the last member of a track has no successor
+                            and so can never be dynamic */
+    double false_alarm;  /* still_members_dynamic / still_members */
+} scvod_tracks_result;
+int scvod_tracks_finish(const scvod_track* tracks, int64_t n, double min_travel, scvod_tracks_result* out);
+
 /* ---- connected components of the map's cells, and their vote (opt-in: nothing runs or is allocated unless these are called;
  *      csrc/scvod_mapcomp.hip) ----
  * Reference analogue: none.  No program of the reference labels map cells; the conventions below are this project's (DESIGN.md
