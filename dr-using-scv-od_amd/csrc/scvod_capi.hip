@@ -228,6 +228,12 @@ struct scvod_ctx {
     Scratch trk;  // stream / ran: the last call (scvod_object_tracks_stats waits for it)
     unsigned long long* trk_counters = nullptr;
     std::vector<unsigned char> trk_host;  // the tables as built on the host (the upload is staged from a copy)
+    // the tracks' vote on the seen-through verdict (scvod_track_visibility_device, scvod_trackvis.hip): a grow-only block (pose
+    // matrices, the per-object and per-track arrays) and 8 counter words of their own, allocated by the first call; not part of the
+    // arena and no other stage's scratch
+    Scratch tv;  // stream / ran: the last call (scvod_track_visibility_stats waits for it)
+    unsigned long long* tv_counters = nullptr;
+    std::vector<float> tv_host;  // the pose matrices as built on the host
     // scan stacking (scvod_batch_stack_scans, scvod_stack.hip): the segment and tile tables, one grow-only block of their own allocated
     // by the first call; not part of the arena
     Scratch stk;
@@ -1575,6 +1581,8 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->ov_counters) hipFree(c->ov_counters);
     if (c->trk.buf) hipFree(c->trk.buf);
     if (c->trk_counters) hipFree(c->trk_counters);
+    if (c->tv.buf) hipFree(c->tv.buf);
+    if (c->tv_counters) hipFree(c->tv_counters);
     if (c->stk.buf) hipFree(c->stk.buf);
     if (c->vis.buf) hipFree(c->vis.buf);
     if (c->vis_counters) hipFree(c->vis_counters);
@@ -3864,6 +3872,112 @@ int scvod_object_tracks_stats(scvod_ctx* c, int64_t* h_out8) {
 
 int64_t scvod_object_tracks_scratch_bytes(scvod_ctx* c) {
     return c ? (int64_t)c->trk.cap + (c->trk_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+}
+
+// ---- the tracks of a table vote on the seen-through verdict (scvod_trackvis.hip) ----
+int scvod_track_visibility_device(scvod_ctx* c, const void* d_objects, const int32_t* d_obj_offsets, int32_t n_scans, const float* h_poses,
+                                  const void* d_links, int64_t cap_objects, const void* d_tracks, int64_t cap_tracks,
+                                  const int32_t* d_track_objects, const int32_t* d_n_tracks, const void* d_object_vis,
+                                  const int32_t* d_point_object, const uint8_t* d_verdict, uint8_t* d_verdict_out, int64_t n_points,
+                                  const scvod_track_visibility_params* params, void* d_track_votes, int64_t cap_track_votes,
+                                  void* d_object_votes, int64_t cap_object_votes, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    scvod_track_visibility_params p;
+    if (params)
+        p = *params;
+    else
+        scvod_track_visibility_params_default(&p);
+    if (p.flags & ~(SCVOD_TRKVIS_NO_DYNAMIC | SCVOD_TRKVIS_CLEAR)) return fail(c, SCVOD_ERR_INVALID, "unknown flag bit (flags %d)", p.flags);
+    if (p.reserved[0] != 0 || p.reserved[1] != 0) return fail(c, SCVOD_ERR_INVALID, "scvod_track_visibility_params::reserved must be 0");
+    if (p.window < 0) return fail(c, SCVOD_ERR_INVALID, "window %d below 0", p.window);
+    if (!(p.min_travel > 0.f) || !std::isfinite(p.min_travel))
+        return fail(c, SCVOD_ERR_INVALID, "min_travel %g: a positive finite number of metres", (double)p.min_travel);
+    if (p.min_length < 1 || p.min_moved < 1) return fail(c, SCVOD_ERR_INVALID, "min_length %d, min_moved %d: both at least 1", p.min_length, p.min_moved);
+    if (p.vote_den < 1 || p.vote_den > (1 << 20) || p.vote_num < 0 || p.vote_num > (1 << 20))
+        return fail(c, SCVOD_ERR_INVALID, "vote %d / %d: 0 <= vote_num <= 2^20, 1 <= vote_den <= 2^20", p.vote_num, p.vote_den);
+    if (n_scans < 0) return fail(c, SCVOD_ERR_INVALID, "n_scans below 0");
+    if (cap_objects < 0 || cap_objects > 2147483647ll || cap_tracks < 0 || cap_track_votes < 0 || cap_object_votes < 0 || n_points < 0)
+        return fail(c, SCVOD_ERR_INVALID, "cap_objects %lld, cap_tracks %lld, cap_track_votes %lld, cap_object_votes %lld, n_points %lld",
+                    (long long)cap_objects, (long long)cap_tracks, (long long)cap_track_votes, (long long)cap_object_votes, (long long)n_points);
+    if (!d_obj_offsets || !d_links || !d_tracks || !d_track_objects || !d_n_tracks)
+        return fail(c, SCVOD_ERR_INVALID, "NULL d_obj_offsets, d_links, d_tracks, d_track_objects or d_n_tracks");
+    if (cap_objects > 0 && !d_objects) return fail(c, SCVOD_ERR_INVALID, "NULL d_objects with cap_objects %lld", (long long)cap_objects);
+    if (d_verdict_out && !d_point_object) return fail(c, SCVOD_ERR_INVALID, "d_verdict_out without d_point_object");
+    if ((uintptr_t)d_objects & 7u) return fail(c, SCVOD_ERR_INVALID, "d_objects is not 8-byte aligned");
+    if (((uintptr_t)d_obj_offsets & 3u) || ((uintptr_t)d_links & 3u) || ((uintptr_t)d_tracks & 3u) || ((uintptr_t)d_track_objects & 3u) ||
+        ((uintptr_t)d_n_tracks & 3u) || ((uintptr_t)d_object_vis & 3u) || ((uintptr_t)d_point_object & 3u) || ((uintptr_t)d_track_votes & 3u) ||
+        ((uintptr_t)d_object_votes & 3u))
+        return fail(c, SCVOD_ERR_INVALID, "every pointer to records or int32 must be 4-byte aligned");
+    if (d_verdict_out && n_points > 0) {
+        const uintptr_t n = (uintptr_t)n_points, o0 = (uintptr_t)d_verdict_out, o1 = o0 + n;
+        const uintptr_t co = (uintptr_t)cap_objects, ct = (uintptr_t)cap_tracks;
+        auto hits = [&](const void* q, uintptr_t bytes) { return q && bytes > 0 && o0 < (uintptr_t)q + bytes && (uintptr_t)q < o1; };
+        if ((d_verdict_out != d_verdict && hits(d_verdict, n)) || hits(d_point_object, 4 * n) || hits(d_objects, sizeof(scvod_object) * co) ||
+            hits(d_obj_offsets, 4 * ((uintptr_t)n_scans + 1)) || hits(d_links, sizeof(scvod_object_link) * co) ||
+            hits(d_tracks, sizeof(scvod_track) * ct) || hits(d_track_objects, 4 * co) || hits(d_n_tracks, 4) ||
+            hits(d_object_vis, sizeof(scvod_object_visibility) * co) || hits(d_track_votes, sizeof(scvod_track_vote) * (uintptr_t)cap_track_votes) ||
+            hits(d_object_votes, sizeof(scvod_object_track_vote) * (uintptr_t)cap_object_votes))
+            return fail(c, SCVOD_ERR_INVALID, "d_verdict_out overlaps an input or a record buffer (only d_verdict_out == d_verdict works in place)");
+    }
+    const size_t B = (size_t)n_scans;
+    c->tv_host.assign(12 * B > 0 ? 12 * B : 1, 0.f);
+    const float zero[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (size_t s = 0; s < B; ++s) scvod_pose_matrix(h_poses ? h_poses + 6 * s : zero, c->tv_host.data() + 12 * s);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (int rc = counter_block(c, &c->tv_counters, 8)) return rc;
+    if (int rc = scratch_reserve(c, c->tv, tv_work_bytes(cap_objects, cap_tracks, n_scans))) return rc;  // (waits for the call in flight before the block moves)
+    c->tv.stream = st;
+    c->tv.ran = true;
+    HIPCHK(c, hipMemsetAsync(c->tv_counters, 0, 8 * sizeof(unsigned long long), st));
+    if (B)
+        if (int rc = staged_upload(c, c->tv_host.data(), sizeof(float) * 12 * B, c->tv.buf, st)) return rc;
+    TvJob J{};
+    J.objects = (const scvod_object*)d_objects;
+    J.obj_off = d_obj_offsets;
+    J.n_scans = n_scans;
+    J.cap = (long long)cap_objects;
+    J.links = (const scvod_object_link*)d_links;
+    J.tracks = (const scvod_track*)d_tracks;
+    J.cap_tracks = (long long)cap_tracks;
+    J.tobj = d_track_objects;
+    J.n_tracks = d_n_tracks;
+    J.ovis = (const scvod_object_visibility*)d_object_vis;
+    J.point_object = d_point_object;
+    J.verdict = d_verdict;
+    J.out = d_point_object ? d_verdict_out : nullptr;
+    J.n_points = (long long)n_points;
+    J.flags = p.flags;
+    J.window = p.window;
+    J.min_length = p.min_length;
+    J.min_moved = p.min_moved;
+    J.min_flagged = p.min_flagged;
+    J.vote_num = p.vote_num;
+    J.vote_den = p.vote_den;
+    J.travel2_min = p.min_travel * p.min_travel;
+    J.out_tracks = (scvod_track_vote*)d_track_votes;
+    J.cap_tvotes = (long long)cap_track_votes;
+    J.out_objs = (scvod_object_track_vote*)d_object_votes;
+    J.cap_ovotes = (long long)cap_object_votes;
+    J.counters = c->tv_counters;
+    const hipError_t e = launch_track_visibility(J, c->tv.buf, st);
+    if (e != hipSuccess) return fail(c, SCVOD_ERR_HIP, "track visibility: %s", hipGetErrorString(e));
+    return SCVOD_OK;
+}
+
+int scvod_track_visibility_stats(scvod_ctx* c, int64_t* h_out8) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->tv.ran) return fail(c, SCVOD_ERR_STATE, "no scvod_track_visibility_device on this ctx yet");
+    if (int rc = read_counters(c, c->tv_counters, 8, c->tv.stream, h_out8)) return rc;
+    if (h_out8[7] & 3)
+        return fail(c, SCVOD_ERR_CAPACITY, "track visibility: %lld objects, %lld listed tracks: a capacity was too small (latch bits %lld)",
+                    (long long)h_out8[0], (long long)h_out8[1], (long long)h_out8[7]);
+    return SCVOD_OK;
+}
+
+int64_t scvod_track_visibility_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->tv.cap + (c->tv_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
 }
 
 void scvod_object_truth_params_default(scvod_object_truth_params* p) {

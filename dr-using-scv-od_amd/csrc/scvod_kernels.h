@@ -618,6 +618,43 @@ size_t trk_tables_bytes(int n_scans);
 size_t trk_work_bytes(long long cap, int n_scans);
 hipError_t launch_object_tracks(const Arena& A, TrkJob J, const int32_t* scan_cnt, void* work, hipStream_t st);
 
+// the tracks of a table vote on the seen-through verdict (scvod_track_visibility_device; scvod_trackvis.hip).  work: tv_work_bytes
+// bytes; its first tv_tables_bytes hold the pose matrices [n_scans][12], staged by the caller.  counters: the 8 words of
+// scvod_track_visibility_stats, cleared by the caller on the stream
+enum { kTvStObjects = 0, kTvStTracks, kTvStVoted, kTvStMotion, kTvStCleared, kTvStToSeen, kTvStToKeep, kTvStLatch };
+struct TvJob {
+    const scvod_object* objects;          // caller's tables, read only
+    const int32_t* obj_off;               // [n_scans + 1]
+    int32_t n_scans;
+    long long cap;                        // records of objects / links / tobj the caller vouches for
+    const scvod_object_link* links;
+    const scvod_track* tracks;
+    long long cap_tracks;
+    const int32_t* tobj;
+    const int32_t* n_tracks;
+    const scvod_object_visibility* ovis;  // or nullptr
+    const int32_t* point_object;          // or nullptr (then out is nullptr too)
+    const uint8_t* verdict;               // or nullptr: every byte SCVOD_VIS_UNTESTED
+    uint8_t* out;                         // or nullptr: records only
+    long long n_points;
+    int32_t flags, window, min_length, min_moved, min_flagged, vote_num, vote_den;
+    float travel2_min;                    // min_travel * min_travel in fp32
+    scvod_track_vote* out_tracks;         // caller's records, each may be nullptr
+    long long cap_tvotes;
+    scvod_object_track_vote* out_objs;
+    long long cap_ovotes;
+    unsigned long long* counters;
+    // filled by launch_track_visibility: slices of `work`
+    const float* T;
+    float4* cw;                           // world centre
+    float* trav;                          // travel2
+    unsigned char *mf, *vb;               // bit 0 flagged, bit 1 moved; the verdict byte (0xFF none), slot `cap`: always none
+    int4* tdec;                           // per listed track: state, how, n_moved
+};
+size_t tv_tables_bytes(int n_scans);
+size_t tv_work_bytes(long long cap, long long cap_tracks, int n_scans);
+hipError_t launch_track_visibility(TvJob J, void* work, hipStream_t st);
+
 // a map split by nearest-neighbour hits (scvod_map_split_device; scvod_split.hip).  The grid is the shared one (grid_buckets, grid_work_ints)
 // over the base cloud with the caller's cell edge; work: sp_work_bytes bytes; stats: the 8 words of scvod_map_split_stats, written by
 // every launch.  The optional outputs of SpJob are nullptr when not asked for; mark == nullptr: a byte array inside `work`

@@ -232,6 +232,26 @@ TRACK_DTYPE = np.dtype([("first_object", "<i4"), ("last_object", "<i4"), ("lengt
 assert TRACK_DTYPE.itemsize == 64
 
 
+class TrackVisibilityParams(C.Structure):
+    """scvod_track_visibility_params (include/scvod.h), 40 bytes"""
+    _fields_ = [("flags", C.c_int32), ("window", C.c_int32), ("min_travel", C.c_float), ("min_length", C.c_int32),
+                ("min_moved", C.c_int32), ("min_flagged", C.c_int32), ("vote_num", C.c_int32), ("vote_den", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+TRKVIS_NO_DYNAMIC = 1                                 # SCVOD_TRKVIS_NO_DYNAMIC
+TRKVIS_CLEAR = 2                                      # SCVOD_TRKVIS_CLEAR
+TRKVIS_OUTPUTS = ("track_votes", "object_votes", "verdict")
+TRKVIS_STATS = ("objects", "tracks", "tracks_voted", "members_motion", "members_cleared", "to_seen_through", "to_keep", "latch")
+# struct scvod_track_vote: one per listed track (scvod_track_visibility_device), 32 bytes
+TRACK_VOTE_DTYPE = np.dtype([("length", "<i4"), ("n_flagged", "<i4"), ("n_moved", "<i4"), ("verdict", "<i4"), ("how", "<i4"),
+                             ("max_travel2", "<f4"), ("reserved", "<i4", 2)])
+assert TRACK_VOTE_DTYPE.itemsize == 32
+# struct scvod_object_track_vote: one per object of the table, 16 bytes
+OBJECT_TRACK_VOTE_DTYPE = np.dtype([("track", "<i4"), ("verdict", "<i4"), ("how", "<i4"), ("travel2", "<f4")])
+assert OBJECT_TRACK_VOTE_DTYPE.itemsize == 16
+
+
 class ComponentVisibilityParams(C.Structure):
     """scvod_component_visibility_params (include/scvod.h), 32 bytes"""
     _fields_ = [("flags", C.c_int32), ("min_cells", C.c_int32), ("max_cells", C.c_int32), ("min_tested", C.c_int32),
@@ -490,6 +510,11 @@ def load_lib():
         "scvod_object_tracks_stats": (C.c_int, [vp, vp]),
         "scvod_object_tracks_scratch_bytes": (i64, [vp]),
         "scvod_tracks_finish": (C.c_int, [vp, i64, C.c_double, C.POINTER(TracksResult)]),
+        "scvod_track_visibility_params_default": (None, [C.POINTER(TrackVisibilityParams)]),
+        "scvod_track_visibility_device": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64,
+                                                    C.POINTER(TrackVisibilityParams), vp, i64, vp, i64, vp]),
+        "scvod_track_visibility_stats": (C.c_int, [vp, vp]),
+        "scvod_track_visibility_scratch_bytes": (i64, [vp]),
         "scvod_map_components": (C.c_int, [vp, vp, i64, i32, vp, vp, i64, vp, vp]),
         "scvod_map_components_stats": (C.c_int, [vp, vp]),
         "scvod_map_components_scratch_bytes": (i64, [vp]),
@@ -542,6 +567,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_batch_object_visibility_scratch_bytes",
                     "scvod_track_params_default", "scvod_object_tracks_device", "scvod_batch_object_tracks", "scvod_object_tracks_stats",
                     "scvod_object_tracks_scratch_bytes", "scvod_tracks_finish",
+                    "scvod_track_visibility_params_default", "scvod_track_visibility_device", "scvod_track_visibility_stats",
+                    "scvod_track_visibility_scratch_bytes",
                     "scvod_map_components","scvod_map_components_stats", "scvod_map_components_scratch_bytes",
                     "scvod_component_visibility_params_default", "scvod_map_component_visibility",
                     "scvod_map_component_visibility_stats",
@@ -730,6 +757,17 @@ def track_params_default(**kw):
     load_lib().scvod_track_params_default(C.byref(p))
     for k, v in kw.items():
         assert k in {f[0] for f in TrackParams._fields_} - {"reserved"}, k
+        setattr(p, k, v)
+    return p
+
+
+def track_visibility_params_default(**kw):
+    """scvod_track_visibility_params with the defaults (flags 0, window 0, min_travel 2.0, min_length 2, min_moved 1, min_flagged 2,
+    vote 1 / 2: this project's values, not from real data and untuned), overridden by keyword"""
+    p = TrackVisibilityParams()
+    load_lib().scvod_track_visibility_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert k in {f[0] for f in TrackVisibilityParams._fields_} - {"reserved"}, k
         setattr(p, k, v)
     return p
 
@@ -1789,6 +1827,70 @@ class Ctx:
     def object_tracks_scratch_bytes(self):
         """device scratch of the stage on this ctx (not part of arena_bytes or batch_objects_scratch_bytes)"""
         return int(self.lib.scvod_object_tracks_scratch_bytes(self.h))
+
+    # ---- the tracks of a table vote on the seen-through verdict (include/scvod.h: scvod_track_visibility_device) ----
+    def track_visibility(self, d_objects, d_obj_offsets, n_scans, poses, trk, d_point_object, d_verdict, d_object_vis=None, params=None,
+                         cap_objects=None, cap_tracks=None, cap_track_votes=None, cap_object_votes=None, want=None, in_place=False,
+                         guard=0, stream=None, full=False):
+        """scvod_track_visibility_device.  d_objects: a contiguous device tensor of 64-byte OBJECT_DTYPE rows; d_obj_offsets int32
+        [n_scans + 1] (device); poses a host array [n_scans, 6] or None; trk: the dict object_tracks_device / batch_object_tracks
+        returned (links, tracks, track_objects, n_tracks); d_point_object int32 [n_points] and d_verdict uint8 [n_points] device
+        tensors, either may be None (no d_point_object: records only; no d_verdict: every byte UNTESTED; n_points is the length of the
+        one that is given); d_object_vis the records of batch_object_visibility or None.  cap_objects None: the rows of d_objects;
+        cap_tracks None: the rows of trk["tracks"]; cap_track_votes / cap_object_votes None: cap_tracks / cap_objects.  Returns a dict
+        of uint8 device tensors, one per name in `want` (TRKVIS_OUTPUTS; None: all that the inputs allow): track_votes
+        [cap_track_votes, 32] (TRACK_VOTE_DTYPE), object_votes [cap_object_votes, 16] (OBJECT_TRACK_VOTE_DTYPE), verdict [n_points]
+        (in_place=True: d_verdict itself).  Record rows behind what was written hold 0xA5 bytes, and with guard > 0 every output has
+        `guard` rows (verdict: 16 * guard bytes) of 0xA5 in front of it and behind it.  full=True: (views, the tensors with their guard
+        rows).  Stream-ordered"""
+        import torch
+        nbytes = d_objects.numel() * d_objects.element_size()
+        assert d_objects.is_contiguous() and nbytes % OBJECT_DTYPE.itemsize == 0
+        cap_objects = nbytes // OBJECT_DTYPE.itemsize if cap_objects is None else int(cap_objects)
+        cap_tracks = int(trk["tracks"].shape[0]) if cap_tracks is None else int(cap_tracks)
+        cap_tv = cap_tracks if cap_track_votes is None else int(cap_track_votes)
+        cap_ov = cap_objects if cap_object_votes is None else int(cap_object_votes)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == n_scans
+        n_points = int(d_point_object.numel()) if d_point_object is not None else (int(d_verdict.numel()) if d_verdict is not None else 0)
+        assert d_verdict is None or (d_verdict.dtype == torch.uint8 and d_verdict.numel() == n_points)
+        paint = d_point_object is not None
+        want = tuple(w for w in TRKVIS_OUTPUTS if paint or w != "verdict") if want is None else tuple(want)
+        assert all(w in TRKVIS_OUTPUTS for w in want) and (paint or "verdict" not in want) and not (in_place and d_verdict is None)
+        dev = d_objects.device
+        rows = {"track_votes": (cap_tv, TRACK_VOTE_DTYPE.itemsize), "object_votes": (cap_ov, OBJECT_TRACK_VOTE_DTYPE.itemsize)}
+        whole, out = {}, {}
+        for w in want:
+            if w == "verdict":
+                if in_place:
+                    whole[w] = out[w] = d_verdict
+                else:
+                    whole[w] = torch.full((n_points + 32 * guard,), 0xA5, dtype=torch.uint8, device=dev)
+                    out[w] = whole[w][16 * guard:16 * guard + n_points]
+            else:
+                whole[w] = torch.full((rows[w][0] + 2 * guard + 1, rows[w][1]), 0xA5, dtype=torch.uint8, device=dev)
+                out[w] = whole[w][guard:guard + rows[w][0]]
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.scvod_track_visibility_device(
+            self.h, ptr(d_objects), ptr(d_obj_offsets), int(n_scans), None if p is None else p.ctypes.data_as(C.c_void_p),
+            ptr(trk["links"]), cap_objects, ptr(trk["tracks"]), cap_tracks, ptr(trk["track_objects"]), ptr(trk["n_tracks"]),
+            ptr(d_object_vis), ptr(d_point_object), ptr(d_verdict), ptr(out.get("verdict")), n_points,
+            C.byref(params) if params is not None else None, ptr(out.get("track_votes")), cap_tv, ptr(out.get("object_votes")), cap_ov,
+            C.c_void_p(stream or 0)))
+        return (out, whole) if full else out
+
+    def track_visibility_stats(self):
+        """{objects, tracks, tracks_voted, members_motion, members_cleared, to_seen_through, to_keep, latch} of the last
+        track_visibility call; synchronises its stream; raises after a capacity overflow (latch bit 1 or 2)"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_track_visibility_stats(self.h, o))
+        return dict(zip(TRKVIS_STATS, (int(v) for v in o)))
+
+    def track_visibility_scratch_bytes(self):
+        """device scratch of the stage on this ctx (not part of arena_bytes and no other stage's scratch)"""
+        return int(self.lib.scvod_track_visibility_scratch_bytes(self.h))
 
     # ---- a cloud against every scan's range image (include/scvod.h: scvod_cloud_visibility_device) ----
     def cloud_visibility(self, d_xyzi, d_images, poses, params=None, flags=0, want=("votes", "verdict"), stream=None):

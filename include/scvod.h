@@ -1715,6 +1715,108 @@ typedef struct scvod_tracks_result { /* 72 bytes */
 } scvod_tracks_result;
 int scvod_tracks_finish(const scvod_track* tracks, int64_t n, double min_travel, scvod_tracks_result* out);
 
+/* ---- the tracks of a batch vote on the seen-through verdict (opt-in: nothing runs or is allocated unless it is called;
+ *      csrc/scvod_trackvis.hip) ----
+ * Reference analogue: none; the rule is this project's convention and its defaults are NOT from real data and
+ * untuned.  Every listed track decides, and every member object takes the decision: motion along the track is a cue of its own, the
+ * per-object flags pooled over the track are a vote, and an optional clear takes the stray flags of a still track back.  One
+ * streaming pass rewrites the per-point verdict bytes that gate scvod_map_accumulate_labelled.  Integers and one fixed fp32
+ * expression: host and device agree bit for bit, and every output is the same on every run and for any launch geometry.
+ *   cW(o)      the world centre of scvod_object_tracks_device: scvod_pose_matrix(pose of objects[o].scan) applied to center, as
+ *              T0*x + T1*y + T2*z + T3 per row, left to right in fp32 without contraction
+ *   d2(a, b)   (dx*dx + dy*dy) + dz*dz of cW(b) - cW(a) in fp32
+ * Let object o have t = links[o].track in [0, tracks), rank r = links[o].rank, L = tracks[t].length, ob = tracks[t].object_begin,
+ * L >= min_length, 0 <= r < L, and let tobj be the track-object list:
+ *   flagged(o)   objects[o].dynamic == 1 (not with SCVOD_TRKVIS_NO_DYNAMIC), or d_object_vis given and
+ *                d_object_vis[o].verdict == SCVOD_VIS_SEEN_THROUGH.  It needs no track: it is defined for every object of the table
+ *   travel2(o)   d2(cW(a), cW(b)) with a = tobj[ob + max(r - w, 0)], b = tobj[ob + min(r + w, L - 1)], w = window; window == 0: a
+ *                and b are the first and the last member, tobj[ob] and tobj[ob + L - 1]
+ *   moved(o)     travel2(o) >= min_travel * min_travel (the fp32 product).  A NaN never moves
+ * Per track, over its L list entries m = tobj[ob + k]: n_flagged and n_moved count flagged(m) and moved(m); max_travel2 is the largest
+ * travel2(m) that is not NaN.  The track VOTES THROUGH iff
+ *   n_flagged >= min_flagged && (int64)n_flagged * vote_den >= (int64)vote_num * L
+ * Verdict of a member, first match wins:
+ *   1. moved(o), and with window == 0 also n_moved >= min_moved:   SCVOD_VIS_SEEN_THROUGH, how 2.  With window > 0 this is per
+ *      member: a car that stops and goes keeps its parked phase
+ *   2. the track votes through:                                    SCVOD_VIS_SEEN_THROUGH, how 1
+ *   3. SCVOD_TRKVIS_CLEAR:                                         SCVOD_VIS_KEEP, how 3
+ *   4. otherwise no verdict (-1, how 0)
+ * An object without a listed track, or on a track below min_length (such a track is not walked: its record carries its length and
+ * zeros), has no verdict.
+ * Points: with o = d_point_object[i], d_verdict_out[i] = verdict(o) when o is an object of the table with a verdict, else d_verdict[i]
+ * (SCVOD_VIS_UNTESTED when d_verdict is NULL).  d_verdict_out == d_verdict works in place; d_verdict_out NULL or d_point_object NULL:
+ * records only.
+ * Nothing read from a table is used as an index unchecked.  The latch word of the stats call collects, as bits:
+ *   2  upstream overflow: d_n_tracks[0] < 0, d_obj_offsets[n_scans] (read on the device) negative or above cap_objects, more tracks than
+ *      cap_tracks.  No object gets a verdict, no record is written, d_verdict_out becomes a copy of d_verdict
+ *   8  a broken reference.  A track (of at least min_length) whose run [object_begin, object_begin + length) leaves [0, cap_objects) or
+ *      that lists an entry outside the table is REFUSED: its record carries its length, verdict -1 and zeros, and its objects get no
+ *      verdict and track -1.  An object whose links[o].track is outside [-1, tracks), or whose rank is outside [0, L) of a track that
+ *      gives a verdict, gets no verdict and track -1
+ *   4  a d_point_object[i] outside [-1, objects): treated as -1
+ *   1  record overflow: more listed tracks than cap_track_votes or more objects than cap_object_votes (each only when its buffer is
+ *      given).  Nothing is written at or behind the capacity, the records below it are complete, and NO byte of d_verdict_out changes
+ * Inputs: d_objects / d_obj_offsets / d_point_object are what scvod_batch_objects wrote; d_links, d_tracks, d_track_objects and
+ * d_n_tracks what scvod_object_tracks_device or scvod_batch_object_tracks wrote for the same d_objects (cap_objects records of
+ * d_objects, d_links, d_track_objects and d_object_vis, cap_tracks of d_tracks: what the caller vouches for); d_object_vis the records
+ * of scvod_batch_object_visibility or NULL; d_verdict any bytes, one per input point, or NULL; h_poses [n_scans][6] or NULL (the zero
+ * pose), staged before the call returns.  The stage works only on these tables: it touches neither the arena nor any batch state, and
+ * there are no state rules.
+ * Stream-ordered (stream NULL = the ctx's stream); never synchronises with the host except to grow its scratch (22 bytes per object of
+ * cap_objects -- world centre, travel2, the flag byte and the verdict byte --, 16 per track of cap_tracks, 48 per scan for the
+ * matrices, 8 counter words: a grow-only allocation of its own, NOT part of scvod_arena_bytes and no other stage's scratch).
+ * params NULL: the defaults.  SCVOD_ERR_INVALID before a device is looked for: NULL ctx; an unknown flag bit or a nonzero reserved
+ * word; window < 0; a min_travel that is not positive and finite; min_length < 1; min_moved < 1; vote_num outside 0 .. 1 << 20 or
+ * vote_den outside 1 .. 1 << 20; n_scans < 0; a negative capacity, cap_objects above 2^31 - 1 or a negative n_points; NULL
+ * d_obj_offsets, d_links, d_tracks, d_track_objects or d_n_tracks; NULL d_objects with cap_objects > 0; d_verdict_out without
+ * d_point_object; d_objects not 8-byte aligned, any other pointer to records or int32 not 4-byte aligned (the byte arrays may sit at
+ * any address); a d_verdict_out that overlaps any input or record buffer without being equal to d_verdict. */
+#define SCVOD_TRKVIS_NO_DYNAMIC 1 /* flags bit 0: the table's `dynamic` byte does not flag an object            */
+#define SCVOD_TRKVIS_CLEAR      2 /* flags bit 1: members of a track that voted and did not pass become KEEP     */
+typedef struct scvod_track_visibility_params { /* 40 bytes */
+    int32_t flags;
+    int32_t window;      /* >= 0.  0: whole-track motion (first against last member); w > 0: local motion over +-w ranks */
+    float   min_travel;  /* metres, > 0 and finite */
+    int32_t min_length;  /* >= 1: shorter listed tracks give no verdict */
+    int32_t min_moved;   /* >= 1, read with window == 0 only, see the rule */
+    int32_t min_flagged; /* any value */
+    int32_t vote_num;    /* 0 .. 1 << 20 */
+    int32_t vote_den;    /* 1 .. 1 << 20 */
+    int32_t reserved[2]; /* 0 */
+} scvod_track_visibility_params;
+/* flags 0, window 0, min_travel 2.0f, min_length 2, min_moved 1, min_flagged 2, vote 1 / 2.
+   This project's values, NOT from real data, untuned. */
+void scvod_track_visibility_params_default(scvod_track_visibility_params* p);
+typedef struct scvod_track_vote {        /* 32 bytes, one per listed track, track order */
+    int32_t length, n_flagged, n_moved;
+    int32_t verdict;                     /* -1 none, SCVOD_VIS_KEEP, SCVOD_VIS_SEEN_THROUGH: what members that did not move get */
+    int32_t how;                         /* 0 none, 1 voted through, 3 cleared */
+    float   max_travel2;                 /* largest travel2 of a member that is not NaN; 0 without one */
+    int32_t reserved[2];
+} scvod_track_vote;
+typedef struct scvod_object_track_vote { /* 16 bytes, one per object of the table, table order */
+    int32_t track;                       /* links[o].track, -1 when not listed or refused */
+    int32_t verdict;                     /* -1 none, SCVOD_VIS_KEEP, SCVOD_VIS_SEEN_THROUGH */
+    int32_t how;                         /* 0 none, 1 track vote, 2 motion, 3 cleared */
+    float   travel2;                     /* 0 without a verdict-giving track */
+} scvod_object_track_vote;
+int scvod_track_visibility_device(scvod_ctx* ctx,
+        const void* d_objects, const int32_t* d_obj_offsets, int32_t n_scans, const float* h_poses,
+        const void* d_links, int64_t cap_objects,           /* records of d_objects / d_links the caller vouches for */
+        const void* d_tracks, int64_t cap_tracks, const int32_t* d_track_objects, const int32_t* d_n_tracks,
+        const void* d_object_vis,                           /* scvod_object_visibility[cap_objects] or NULL */
+        const int32_t* d_point_object, const uint8_t* d_verdict, uint8_t* d_verdict_out, int64_t n_points,
+        const scvod_track_visibility_params* params,
+        void* d_track_votes, int64_t cap_track_votes, void* d_object_votes, int64_t cap_object_votes,
+        void* stream);
+/* h_out8 = {objects, listed tracks, tracks with how 1, members with how 2, members with how 3, points moved to SEEN_THROUGH (input
+ * byte not 2), points moved to KEEP (input byte not 1), latch bits} of the last call; after an upstream overflow words 0 and 1 are the
+ * counts as read and words 2 .. 6 are 0.  Synchronises that call's stream.  SCVOD_ERR_CAPACITY when latch bit 1 or 2 is set, with the
+ * words filled; SCVOD_ERR_STATE before the first call. */
+int     scvod_track_visibility_stats(scvod_ctx* ctx, int64_t* h_out8);
+/* bytes of device scratch the stage holds on this ctx (0 before the first call) */
+int64_t scvod_track_visibility_scratch_bytes(scvod_ctx* ctx);
+
 /* ---- connected components of the map's cells, and their vote (opt-in: nothing runs or is allocated unless these are called;
  *      csrc/scvod_mapcomp.hip) ----
  * Reference analogue: none.  No program of the reference labels map cells; the conventions below are this project's (DESIGN.md
