@@ -185,7 +185,13 @@ __global__ __launch_bounds__(1024) void k_vx_partition(DevParams P, Arena A) {
 // KT = uint32_t: hot path of a filtered batch -- (key - first key of the bucket) << idx_bits | apri index; a bucket spans
 // 2^vb_shift keys and a scan 2^idx_bits points, vb_shift + idx_bits <= 32 (checked on the host): half the LDS traffic, and
 // the compare-exchange is a full-rate v_min_u32 + v_max_u32.
-// LDS of one workgroup: padded keys + voxel starts + staged intensities (+ the scan's wave sums).  SCVOD_VOX_K32_LDS = 1: the key
+// COUNT = true (KT = uint32_t, MODE 0; launch_vx_tier picks it when the batch's buckets span 2^kVxCountShift keys): no network -- the bucket's
+// points are placed by key counting (vx_bucket_count below); only a bucket whose largest voxel exceeds kVxCountDense points is sorted.
+// Both forms write the same arrays, bit for bit: keys are unique, ascending (key, apri index) is one total order.
+// LDS of a COUNT workgroup: cnt[2^kVxCountShift] (a voxel's population, then start | population << 16) + lst[CAP + 4] (the keys listed by
+// voxel, 4 pad keys) (+ DESC: c_int[CAP] intensities in final order, c_vbeg[CAP] voxel starts) + the scan's wave sums; it is given the larger
+// of this and the network's need, which a dense bucket uses (vox_lds_bytes).
+// LDS of one network workgroup: padded keys + voxel starts + staged intensities (+ the scan's wave sums).  SCVOD_VOX_K32_LDS = 1: the key
 // area of the 4-byte keys is 4 bytes per slot, which lets a third (sixth, twelfth) workgroup of the 4096 (2048, 1024) tier onto a CU
 #ifndef SCVOD_VOX_K32_LDS
 #define SCVOD_VOX_K32_LDS 1
@@ -193,8 +199,42 @@ __global__ __launch_bounds__(1024) void k_vx_partition(DevParams P, Arena A) {
 constexpr size_t vox_key_bytes(int cap, size_t ksize) { return (((size_t)(cap + cap / 8) * (SCVOD_VOX_K32_LDS ? ksize : 8)) + 15) & ~(size_t)15; }
 // DESC = false (the lean form): no staged intensities; what is left of that area holds the <= 128 (chunk, wave) head counts
 constexpr size_t vox_aux_bytes(int cap, bool desc) { return desc ? (size_t)cap * 4 : ((size_t)(cap / 64) * 4 + 15) & ~(size_t)15; }
-constexpr size_t vox_lds_bytes(int cap, size_t ksize = 8, bool desc = true) {
-    return vox_key_bytes(cap, ksize) + (size_t)cap * 4 + vox_aux_bytes(cap, desc) + 128;
+// The counting form (32-bit keys, MODE 0): a bucket whose keys span 2^kVxCountShift voxels is ordered without a comparison network --
+// one LDS counter per voxel of the span gives every voxel's population, the prefix over the counters every voxel's start (the voxel's key
+// is the counter's index), and a point's place is its voxel's start + the number of smaller keys in the voxel's own segment.
+// SCVOD_VOX_COUNT = 0: network everywhere, 1: the tiers measured faster with it (profiles/voxel_counting_cost.md), 2: every tier that can
+#ifndef SCVOD_VOX_COUNT
+#define SCVOD_VOX_COUNT 1
+#endif
+constexpr int kVxCountShift = 12;     // the span the counters are sized for: semantickitti and parkinglot grids (os128_fine: 2^14, network)
+// a bucket whose largest voxel holds more points than this takes the network: the segment walks of a voxel of c points cost c^2 / 4 16-byte
+// reads, 16 k at c = 256 next to the 229 k accesses of the network on 4096 keys.  Measured (tools/voxel_dense_bench.py): one voxel of c
+// points per bucket crosses the network's time near c = 480, and a bucket that falls back pays 37 % more than the network alone; 256 leaves
+// room for several such voxels in one bucket, the criterion sees the largest only (profiles/voxel_counting_cost.md)
+#ifndef SCVOD_VOX_COUNT_DENSE
+#define SCVOD_VOX_COUNT_DENSE 256
+#endif
+constexpr int kVxCountDense = SCVOD_VOX_COUNT_DENSE;
+#ifndef SCVOD_VOX_COUNT_M
+#define SCVOD_VOX_COUNT_M 4  // workgroups per CU of the lean 2048 tier in the counting form (24.7 KB of LDS, 116 VGPRs; the network form runs eight)
+#endif
+#ifndef SCVOD_VOX_COUNT_L
+#define SCVOD_VOX_COUNT_L 2  // ... of the lean 4096 tier (35.2 KB of LDS, the network fallback's): two leave the kernel its 120 VGPRs; at three (80 VGPRs) it spills 40 and is 0.26 ms slower
+#endif
+// which tiers count, next to vx_bucket_padfree: the 256 and 1024 tiers cannot hold 16 KB of counters per workgroup at their 32 and 12 workgroups
+// per CU; the fused (DESC) form is tested but not timed, it counts with SCVOD_VOX_COUNT=2 only
+constexpr bool vx_bucket_counting(int cap, size_t ksize, int mode, bool desc) {
+    return ksize == 4 && mode == 0 && cap >= 2048 && (SCVOD_VOX_COUNT == 2 || (SCVOD_VOX_COUNT == 1 && !desc));
+}
+// workgroups per CU of the counting kernels: ONE place for the launch (launch_vx_tier) and for the kernels' amdgpu_waves_per_eu bound
+// (per CU x waves of a workgroup / 4 SIMDs).  The fused (DESC) form's LDS (40.1 / 64.2 KB) allows three / two
+constexpr int vx_count_per_cu(int cap, bool desc) { return cap >= 8192 ? 1 : cap >= 4096 ? (desc ? 2 : SCVOD_VOX_COUNT_L) : (desc ? 3 : SCVOD_VOX_COUNT_M); }
+// LDS of the counting form: counters + the bucket's keys listed by voxel (+ 4 pad keys) (+ DESC: staged intensities, voxel starts)
+constexpr size_t vox_count_bytes(int cap, bool desc) { return ((size_t)4 << kVxCountShift) + (size_t)(cap + 4) * 4 + (desc ? (size_t)cap * 8 : 0); }
+constexpr size_t vox_lds_bytes(int cap, size_t ksize = 8, bool desc = true, bool count = false) {
+    const size_t net = vox_key_bytes(cap, ksize) + (size_t)cap * 4 + vox_aux_bytes(cap, desc);
+    const size_t cnt = count ? vox_count_bytes(cap, desc) : 0;  // (a dense bucket takes the network in the same kernel)
+    return (net > cnt ? net : cnt) + 128;
 }
 // workgroups per CU of the lean 4096 tier with 32-bit keys (x2 for the 2048 tier): 35.2 KB of LDS each, four fit where the full form's
 // 51.3 KB allows three (profiles/lazy_voxel_descriptors_cost.md has both measured)
@@ -236,15 +276,149 @@ __device__ __forceinline__ void vx_descriptor(int n, F&& at, float& av_out, floa
     av_out = av;
     cov_out = cov / fn;
 }
+// The counting form of one bucket in LDS (see vx_bucket_counting above).  Returns false, having written nothing, when the bucket's largest
+// voxel exceeds kVxCountDense: the caller's network takes it.  Uniform over the workgroup.
+struct VxCountArgs {
+    const uint32_t* gkeys;   // the bucket's m keys, (voxel key relative to the bucket) << ib | apri index, in arbitrary order
+    int32_t* vox_pts;        // the outputs, all at the bucket's place (base + off)
+    int32_t* out_key;
+    int32_t* out_beg;
+    float* out_av;
+    float* out_cov;
+    const float* apri_int;   // the scan's
+    int32_t* nvox;
+    int32_t key0;
+    int m, off, ib;
+};
+template <int CAP, int THREADS, bool DESC, bool PV>
+__device__ __forceinline__ bool vx_bucket_count(const VxCountArgs& ca
+#ifdef SCVOD_PROFILE
+                                             , unsigned long long& t_prev
+#endif
+) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int SPAN = 1 << kVxCountShift;
+    constexpr int IT = CAP / THREADS;    // keys per thread
+    constexpr int CPT = SPAN / THREADS;  // consecutive counters per thread in the prefix
+    static_assert(CPT % 4 == 0 && IT % 2 == 0 && CAP <= 8192, "16-byte counter reads; start (13 bits) and count (14) share a word");
+    uint32_t* cnt = (uint32_t*)smem;                                 // [SPAN] population, then start | population << 16
+    uint32_t* lst = cnt + SPAN;                                      // [CAP + 4] the keys listed by voxel, in arrival order
+    float* c_int = (float*)(lst + CAP + 4);                          // [CAP] (DESC) intensities in final order
+    int* c_vbeg = (int*)(c_int + CAP);                               // [CAP] (DESC) voxel starts
+    int* c_wsum = (int*)(smem + vox_count_bytes(CAP, DESC));
+    const int m = ca.m, ib = ca.ib;
+    const uint32_t imask = (1u << ib) - 1u;
+    for (int i = threadIdx.x; i < SPAN / 4; i += THREADS) ((uint4*)cnt)[i] = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t key[IT];
+#pragma unroll
+    for (int it = 0; it < IT; ++it)  // all of a thread's key loads in flight together (coalesced); m > 0
+        key[it] = ca.gkeys[min(it * THREADS + (int)threadIdx.x, m - 1)];
+    __syncthreads();
+    if (PV) PROF_MARK(3, 0);
+    // arrival number of every key in its voxel (arbitrary order), two 16-bit numbers per register
+    uint32_t arr[IT / 2];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        uint32_t a = 0u;
+        if (it * THREADS + (int)threadIdx.x < m) a = atomicAdd(&cnt[key[it] >> ib], 1u);
+        if (it & 1)
+            arr[it / 2] |= a << 16;
+        else
+            arr[it / 2] = a;
+    }
+    __syncthreads();
+    if (PV) PROF_MARK(3, 1);
+    // population of the thread's CPT consecutive voxels; they are read again after the prefix, not held
+    const uint4* my_cnt = (const uint4*)cnt + threadIdx.x * (CPT / 4);
+    uint32_t sum = 0, nz = 0, mx = 0;
+#pragma unroll
+    for (int q = 0; q < CPT / 4; ++q) {
+        const uint4 x = my_cnt[q];
+        sum += x.x + x.y + x.z + x.w;
+        nz += (x.x ? 1u : 0u) + (x.y ? 1u : 0u) + (x.z ? 1u : 0u) + (x.w ? 1u : 0u);
+        mx = max(max(mx, max(x.x, x.y)), max(x.z, x.w));
+    }
+    if (__syncthreads_or(mx > (uint32_t)kVxCountDense)) return false;
+    int tot;
+    const int ex = block_excl_scan<THREADS>((int)(sum | (nz << 16)), tot, c_wsum);  // (points <= 8192, voxels <= 4096: no carry)
+    const int nv = tot >> 16;
+    int start = ex & 0xffff, v = ex >> 16;
+    int32_t vkey = ca.key0 + (int32_t)threadIdx.x * CPT;  // the voxel's key is the counter's index: no key is read for it
+    auto voxel = [&](uint32_t& n) {
+        if (n) {
+            ca.out_key[v] = vkey;
+            ca.out_beg[v] = ca.off + start;
+            if constexpr (DESC) c_vbeg[v] = start;
+            const int first = start;
+            start += (int)n;
+            n = (uint32_t)first | (n << 16);
+            ++v;
+        }
+        ++vkey;
+    };
+#pragma unroll
+    for (int q = 0; q < CPT / 4; ++q) {
+        uint4 x = my_cnt[q];
+        voxel(x.x);
+        voxel(x.y);
+        voxel(x.z);
+        voxel(x.w);
+        ((uint4*)cnt)[threadIdx.x * (CPT / 4) + q] = x;
+    }
+    if (threadIdx.x < 4) lst[m + (int)threadIdx.x] = 0xffffffffu;  // (the walks below read whole 16-byte groups)
+    if (threadIdx.x == 0) *ca.nvox = nv;
+    __syncthreads();
+    if (PV) PROF_MARK(3, 2);
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        if (it * THREADS + (int)threadIdx.x < m)
+            lst[(cnt[key[it] >> ib] & 0xffffu) + ((arr[it / 2] >> ((it & 1) * 16)) & 0xffffu)] = key[it];
+    }
+    __syncthreads();
+    if (PV) PROF_MARK(3, 3);
+    // by position: neighbouring lanes stand in the same voxel, their walks are equally long and their reads broadcast.  Keys are
+    // unique and ascend with the voxel, so place = keys below mine in [start rounded down to 4, end of my voxel's segment)
+    for (int p = threadIdx.x; p < m; p += THREADS) {
+        const uint32_t k = lst[p];
+        const uint32_t sc = cnt[k >> ib];
+        const int end = (int)(sc & 0xffffu) + (int)(sc >> 16);
+        int place = (int)(sc & 0xfffcu);
+        for (int q = place; q < end; q += 4) {
+            const uint4 x = *(const uint4*)(lst + q);
+            place += (int)(x.x < k) + (int)(x.y < k) + (int)(x.z < k) + (int)(x.w < k);
+        }
+        ca.vox_pts[place] = (int32_t)(k & imask);
+        if constexpr (DESC) c_int[place] = ca.apri_int[k & imask];
+    }
+    if constexpr (DESC) {
+        __syncthreads();
+        if (PV) PROF_MARK(3, 4);
+        // per voxel: sequential fp32 mean, then population variance accumulated as float += double, in list order
+        for (int u = threadIdx.x; u < nv; u += THREADS) {
+            const int j0 = c_vbeg[u];
+            const int j1 = (u + 1 < nv) ? c_vbeg[u + 1] : m;
+            float av, cov;
+            vx_descriptor<1>(j1 - j0, [&](int j) { return c_int[j0 + j]; }, av, cov);
+            ca.out_cov[u] = cov;
+            ca.out_av[u] = av;
+        }
+    } else {
+        if (PV) PROF_MARK(3, 4);
+    }
+    __syncthreads();  // LDS is reused by the next item
+    if (PV) PROF_MARK(3, 5);
+    return true;
+}
 // which tiers run the pad-free network (scvod_sortnet.h): those measured faster with it (profiles/padfree_sort_cost.md);
 // the 256 and 1024 tiers are slower, they keep the padded network.  SCVOD_VOX_PADFREE=0: none, 2: all
 constexpr bool vx_bucket_padfree(int cap) { return SCVOD_VOX_PADFREE == 2 || (SCVOD_VOX_PADFREE == 1 && cap >= 2048); }
 // DESC = false (MODE 0 only): the lean form of a batch whose descriptors are computed on demand (k_vx_descriptors) -- no intensity
 // staging, no per-voxel sums, no tmp_vox_av / tmp_vox_cov
-template <int CAP, int THREADS, int C_LO, int C_HI, int LGE, int MODE = 0, typename KT = unsigned long long, bool DESC = true>
+// COUNT: the kernel of a batch whose buckets span 2^kVxCountShift keys (chosen at the launch, launch_vx_tier): buckets count, dense ones sort
+template <int CAP, int THREADS, int C_LO, int C_HI, int LGE, int MODE = 0, typename KT = unsigned long long, bool DESC = true, bool COUNT = false>
 __global__ __launch_bounds__(THREADS)
 #if SCVOD_VOX_K32_LDS
-__attribute__((amdgpu_waves_per_eu((sizeof(KT) == 4 && CAP <= 4096 && CAP >= 2048) ? (DESC ? 6 : 2 * SCVOD_VOX_LEAN_MORE) : 1, 8)))
+__attribute__((amdgpu_waves_per_eu((sizeof(KT) == 4 && CAP <= 4096 && CAP >= 2048) ? (COUNT ? vx_count_per_cu(CAP, DESC) * (THREADS / 64) / 4 : DESC ? 6 : 2 * SCVOD_VOX_LEAN_MORE) : 1, 8)))
 #endif
 void k_vx_bucket(DevParams P, Arena A) {
     static_assert(DESC || MODE == 0, "the lean form is makeHashCloud's");
@@ -284,6 +458,30 @@ void k_vx_bucket(DevParams P, Arena A) {
     const uint32_t imask = (1u << A.vx_idx_bits) - 1u;
     auto k_major = [&](KT k) -> uint32_t { return K32 ? (uint32_t)k >> A.vx_idx_bits : key_major((unsigned long long)k); };
     auto k_idx = [&](KT k) -> uint32_t { return K32 ? (uint32_t)k & imask : key_idx((unsigned long long)k); };
+    if constexpr (COUNT) {
+        static_assert(vx_bucket_counting(CAP, sizeof(KT), MODE, DESC), "a tier that counts");
+        if (in_lds) {
+            VxCountArgs ca;
+            ca.gkeys = (const uint32_t*)gkeys;
+            ca.vox_pts = A.vox_pts + (size_t)base + off;
+            ca.out_key = A.tmp_vox_key + (size_t)base + off;
+            ca.out_beg = A.tmp_vox_begin + (size_t)base + off;
+            ca.out_av = DESC ? A.tmp_vox_av + (size_t)base + off : nullptr;
+            ca.out_cov = DESC ? A.tmp_vox_cov + (size_t)base + off : nullptr;
+            ca.apri_int = DESC ? A.apri_int + (size_t)base : nullptr;
+            ca.nvox = A.vb_nvox + s * kMaxBuckets + b;
+            ca.key0 = (int32_t)(((int64_t)b << P.vb_shift) - P.key_off);  // the key of the bucket's first voxel (as vox_key_of forms it)
+            ca.m = m;
+            ca.off = off;
+            ca.ib = A.vx_idx_bits;
+#ifdef SCVOD_PROFILE
+            if (vx_bucket_count<CAP, THREADS, DESC, PV>(ca, t_prev)) continue;
+#else
+            if (vx_bucket_count<CAP, THREADS, DESC, PV>(ca)) continue;
+#endif
+            // (a dense bucket: the network below reads its keys again, nothing has been written yet)
+        }
+    }
     if (in_lds) {
         int np2 = 1 << LGE;
         while (np2 < m) np2 <<= 1;

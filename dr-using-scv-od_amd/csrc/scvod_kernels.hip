@@ -444,6 +444,27 @@ constexpr size_t sort_lds_bytes(int cap) { return (size_t)(cap + cap / 8) * 8; }
 constexpr int kVoxCapS = 1024, kVoxThreadsS = 64;
 constexpr int kVoxCapL = 8192, kVoxThreadsL = 512;
 
+// one tier of the voxel stage (MODE 0).  A tier that counts (vx_bucket_counting) runs the counting kernel when the batch's buckets span
+// the 2^kVxCountShift keys its counters are sized for, with that form's LDS and workgroups per CU; everything else runs the network kernel
+template <int CAP, int THREADS, int C_LO, int C_HI, int LGE, typename KT, bool DESC>
+static void launch_vx_tier(const DevParams& P, const Arena& A, hipStream_t st, int per_cu_network) {
+    if constexpr (vx_bucket_counting(CAP, sizeof(KT), 0, DESC)) {
+        if (P.vb_shift == kVxCountShift) {
+            constexpr size_t lds = vox_lds_bytes(CAP, sizeof(KT), DESC, true);
+            constexpr int per_cu_counting = vx_count_per_cu(CAP, DESC);
+            static_assert(per_cu_counting > 0 && per_cu_counting * lds <= 160 * 1024, "workgroups per CU of a counting tier");
+            if (CAP >= 4096)
+                hipFuncSetAttribute((const void*)k_vx_bucket<CAP, THREADS, C_LO, C_HI, LGE, 0, KT, DESC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL((k_vx_bucket<CAP, THREADS, C_LO, C_HI, LGE, 0, KT, DESC, true>), dim3(kPersistCUs * per_cu_counting), dim3(THREADS), lds, st, P, A);
+            return;
+        }
+    }
+    constexpr size_t lds = vox_lds_bytes(CAP, sizeof(KT), DESC);
+    if (CAP >= 4096)
+        hipFuncSetAttribute((const void*)k_vx_bucket<CAP, THREADS, C_LO, C_HI, LGE, 0, KT, DESC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((k_vx_bucket<CAP, THREADS, C_LO, C_HI, LGE, 0, KT, DESC, false>), dim3(kPersistCUs * per_cu_network), dim3(THREADS), lds, st, P, A);
+}
+
 void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_patchwork, int apply_filter,
                     int do_voxels, TimerHook th, void* tu, int lean_voxels, int lean_emit) {
     const int B = A.n_scans;
@@ -588,30 +609,23 @@ void launch_process(const DevParams& P, const Arena& A, hipStream_t st, int do_p
             using KT = decltype(kt);
             constexpr size_t KS = sizeof(KT);
             constexpr bool DESC = decltype(desc)::value;
-            // workgroups per CU of the 4096 tier (x2 for the 2048 tier): what the LDS of each form allows, both measured
+            // workgroups per CU of the 4096 tier (x2 for the 2048 tier): what the LDS of each form allows, both measured; the counting
+            // kernels' own: vx_count_per_cu (profiles/voxel_counting_cost.md)
             constexpr int kMore = (KS == 4 && SCVOD_VOX_K32_LDS) ? (DESC ? 3 : SCVOD_VOX_LEAN_MORE) : 2;
-            hipFuncSetAttribute((const void*)k_vx_bucket<kVoxCapL, kVoxThreadsL * kTSv, kClassL, 63, kLGEv, 0, KT, DESC>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vox_lds_bytes(kVoxCapL, KS, DESC));
-            hipFuncSetAttribute((const void*)k_vx_bucket<4096, 256 * kTSv, kClassM2, kClassL - 1, kLGEv, 0, KT, DESC>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)vox_lds_bytes(4096, KS, DESC));
             TH_BEGIN("vx_bucket_8192");
-            hipLaunchKernelGGL((k_vx_bucket<kVoxCapL, kVoxThreadsL * kTSv, kClassL, 63, kLGEv, 0, KT, DESC>), dim3(kPersistCUs), dim3(kVoxThreadsL * kTSv),
-                               vox_lds_bytes(kVoxCapL, KS, DESC), st, P, A);
+            launch_vx_tier<kVoxCapL, kVoxThreadsL * kTSv, kClassL, 63, kLGEv, KT, DESC>(P, A, st, 1);
             TH_END("vx_bucket_8192");
             TH_BEGIN("vx_bucket_4096");
-            hipLaunchKernelGGL((k_vx_bucket<4096, 256 * kTSv, kClassM2, kClassL - 1, kLGEv, 0, KT, DESC>), dim3(kPersistCUs * kMore), dim3(256 * kTSv),
-                               vox_lds_bytes(4096, KS, DESC), st, P, A);
+            launch_vx_tier<4096, 256 * kTSv, kClassM2, kClassL - 1, kLGEv, KT, DESC>(P, A, st, kMore);
             TH_END("vx_bucket_4096");
             TH_BEGIN("vx_bucket_2048");
-            hipLaunchKernelGGL((k_vx_bucket<2048, 128 * kTSv, kClassM, kClassM2 - 1, kLGEv, 0, KT, DESC>), dim3(kPersistCUs * kMore * 2), dim3(128 * kTSv),
-                               vox_lds_bytes(2048, KS, DESC), st, P, A);
+            launch_vx_tier<2048, 128 * kTSv, kClassM, kClassM2 - 1, kLGEv, KT, DESC>(P, A, st, kMore * 2);
             TH_END("vx_bucket_2048");
             TH_BEGIN("vx_bucket_1024");
-            hipLaunchKernelGGL((k_vx_bucket<kVoxCapS, kVoxThreadsS * kTSv, kClassXS, kClassM - 1, kLGEv, 0, KT, DESC>), dim3(kPersistCUs * (DESC ? 8 : SCVOD_VOX_LEAN_S)),
-                               dim3(kVoxThreadsS * kTSv), vox_lds_bytes(kVoxCapS, KS, DESC), st, P, A);  // (fused form: twelve per CU measured slower than eight; lean form: twelve faster, sixteen no better)
+            launch_vx_tier<kVoxCapS, kVoxThreadsS * kTSv, kClassXS, kClassM - 1, kLGEv, KT, DESC>(P, A, st, DESC ? 8 : SCVOD_VOX_LEAN_S);  // (fused form: twelve per CU measured slower than eight; lean form: twelve faster, sixteen no better)
             TH_END("vx_bucket_1024");
             TH_BEGIN("vx_bucket_256");
-            hipLaunchKernelGGL((k_vx_bucket<256, 64, 0, kClassXS - 1, 3, 0, KT, DESC>), dim3(kPersistCUs * 32), dim3(64), vox_lds_bytes(256, KS, DESC), st, P, A);
+            launch_vx_tier<256, 64, 0, kClassXS - 1, 3, KT, DESC>(P, A, st, 32);
             TH_END("vx_bucket_256");
         };
         if (A.vx_k32) {

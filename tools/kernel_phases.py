@@ -18,7 +18,11 @@ KERNELS = [
                               "exact path: rounds", "exact path: number of rounds"]),
     ("k_pw_sort<4096> (per scan)", ["load keys", "bitonic sort", "gather + write sorted points"]),
     ("k_pw_sort<8192> (per scan)", ["load keys", "bitonic sort", "gather + write sorted points"]),
-    ("k_vx_bucket<4096> (per scan)", ["load keys", "bitonic sort", "heads + voxel starts", "stage intensities", "per-voxel sums", "final writes"]),
+    # (network form | counting form: a bucket of a 2^12-key span counts, see vx_bucket_count; a build with -DSCVOD_VOX_COUNT=0 never does.
+    #  A bucket above kVxCountDense has clocked its key load and its count into the first two rows before it falls back to the network, which
+    #  then clocks its own load and sort into the same rows: for scans with such buckets these two rows mix both forms.  Synthetic scans have none)
+    ("k_vx_bucket<4096> (per scan)", ["load keys | + clear counters", "bitonic sort | count (LDS atomics)", "heads + voxel starts | prefix + voxel starts",
+                                      "stage intensities | list keys by voxel", "per-voxel sums | rank in the voxel + point writes", "final writes | per-voxel sums"]),
     ("k_cc_scan generic variant, inside 'neighbour search + unions' (per scan)",
      ["opener triples + regular bits", "spill, plane starts, init", "windows: plan", "windows: load", "windows: search in LDS", "windows: write-out",
       "(from 'extra runs, canonical names') extra runs", "(from 'extra runs, canonical names') rest of the affected-components block",
