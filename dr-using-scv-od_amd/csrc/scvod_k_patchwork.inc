@@ -117,6 +117,13 @@ __device__ __forceinline__ void order_range(const int32_t* off, int c_lo, int c_
 // which tiers run the pad-free network (scvod_sortnet.h): those measured faster with it (profiles/padfree_sort_cost.md);
 // the 256 tier is slower and the 1024 tier within noise, they keep the padded network.  SCVOD_SORT_PADFREE=0: none, 2: all
 constexpr bool pw_sort_padfree(int cap) { return SCVOD_SORT_PADFREE == 2 || (SCVOD_SORT_PADFREE == 1 && cap >= 2048); }
+// which tiers merge their register runs by merge path (scvod_mergepath.h) instead of running the network's later stages: those
+// measured faster with it (profiles/merge_sort_cost.md): the 4096 and 8192 tiers; the 2048 tier's gain is within the noise of one
+// kernel's figure, it keeps the network.  Only tiers with one 16-key window per thread that run the pad-free start can; the 16 384
+// tier and the tiers below 2048 are not candidates.  SCVOD_SORT_MERGE=0: none, 2: the 2048 tier too
+constexpr bool pw_sort_merge(int cap) {
+    return pw_sort_padfree(cap) && cap >= 2048 && cap <= 8192 && (SCVOD_SORT_MERGE == 2 || (SCVOD_SORT_MERGE == 1 && cap >= 4096));
+}
 
 // (the pad-free network carries a predicated and an unpredicated form of every pass: the register budget is held to the
 //  four waves per SIMD that the launches below put on a CU -- what the padded network reached on its own; the few values
@@ -130,6 +137,7 @@ void k_pw_sort(DevParams P, Arena A) {
     order_range(A.order_off, C_LO, C_HI, lo, hi);
     constexpr int PK = (CAP == 4096) ? 1 : 2;  // (profiling build: the two large tiers are clocked)
     constexpr bool PADFREE = pw_sort_padfree(CAP);
+    constexpr bool MERGE = pw_sort_merge(CAP) && LGE == 4 && (THREADS << LGE) == CAP;  // one window of 16 outputs per thread
     PROF_BEGIN();
     for (int w = lo + blockIdx.x; w < hi; w += gridDim.x) {
         const int4 item = A.order[w];
@@ -159,7 +167,10 @@ void k_pw_sort(DevParams P, Arena A) {
                             }
                         }
                         if (CAP >= 4096) PROF_MARK(PK, 0);
-                        padfree_sort_regs<THREADS, true, LGE>(tmp, keys, np2, nlive, (unsigned long long)kKeyPad);
+                        if constexpr (MERGE)
+                            mergepath_sort_regs<THREADS, true, LGE, SCVOD_SORT_MERGE_RUN>(tmp, keys, np2, nlive, (unsigned long long)kKeyPad);
+                        else
+                            padfree_sort_regs<THREADS, true, LGE>(tmp, keys, np2, nlive, (unsigned long long)kKeyPad);
                     } else {
 #pragma unroll
                         for (int it = 0; it < IT; ++it) {
@@ -176,7 +187,9 @@ void k_pw_sort(DevParams P, Arena A) {
                 for (int j = threadIdx.x; j < nfill; j += THREADS) keys[sort_slot<true>(j)] = (j < n) ? gk[j] : kKeyPad;
                 __syncthreads();
                 if (CAP >= 4096) PROF_MARK(PK, 0);
-                if constexpr (PADFREE)
+                if constexpr (MERGE)
+                    mergepath_sort<THREADS, true, LGE, SCVOD_SORT_MERGE_RUN>(keys, np2, nlive, (unsigned long long)kKeyPad);
+                else if constexpr (PADFREE)
                     padfree_sort<THREADS, true, LGE>(keys, np2, nlive, (unsigned long long)kKeyPad);
                 else
                     block_bitonic_sort_pow2<THREADS, true, LGE>(keys, np2);

@@ -27,6 +27,7 @@
 #include "scvod_boxgrid.h"
 #include "scvod_grid.h"
 #include "scvod_sortnet.h"
+#include "scvod_mergepath.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace scvod {
@@ -409,6 +410,66 @@ __device__ __forceinline__ void padfree_sort_regs(T (&e)[1 << LGE], T* a, int np
     if ((int)threadIdx.x < (nlive >> LGE)) sortnet::run_store<LGE, PAD>(e, a, (int)threadIdx.x, CxAsc{});
     __syncthreads();
     padfree_merge_stages<THREADS, PAD, LGE>(a, np2, nlive, padv);
+}
+
+// ---- merge-path form of the large Patchwork tiers (scvod_mergepath.h) ------------------------------
+// Same runs in registers and same LDS layout; the network's stages run only up to runs of SCVOD_SORT_MERGE_RUN keys
+// (16: none of them), then every level merges pairs of runs by merge path, in place through registers: a thread owns
+// 16 consecutive outputs, finds its split by binary search, merges serially, barrier, stores, barrier.  n log n
+// comparisons instead of the network's n log^2 n.  One window per thread: THREADS << LGE covers the tier.
+#ifndef SCVOD_SORT_MERGE
+#define SCVOD_SORT_MERGE 1  // Patchwork sort tiers: 1 = merge path where it measured faster (pw_sort_merge), 0 = network in every tier, 2 = merge path in the 2048 tier too
+#endif
+#ifndef SCVOD_SORT_MERGE_RUN
+#define SCVOD_SORT_MERGE_RUN 16  // run length at which the network hands over to the merge levels: a power of two, 16 .. 1024
+#endif
+static_assert(SCVOD_SORT_MERGE_RUN >= 16 && SCVOD_SORT_MERGE_RUN <= 1024 && (SCVOD_SORT_MERGE_RUN & (SCVOD_SORT_MERGE_RUN - 1)) == 0,
+              "SCVOD_SORT_MERGE_RUN");
+
+template <int THREADS, bool PAD, int LGE, int RUN, typename T>
+__device__ __forceinline__ void mergepath_levels(T* a, int np2, int nlive, T padv) {
+    static_assert(RUN >= (1 << LGE), "the merge levels start from whole register runs");
+    if constexpr (RUN > (1 << LGE)) {  // the network's stages k = 2^(LGE+1) .. RUN
+        sortnet::for_each_pass<LGE>(np2 < RUN ? np2 : RUN, [&](int r, int lt, bool mirror) {
+            if (!mirror)
+                padfree_pass<THREADS, PAD, LGE, false>(a, np2, nlive, r, padv);
+            else if (lt == 1)
+                padfree_pass<THREADS, PAD, 1, true>(a, np2, nlive, r, padv);
+            else if (lt == 2)
+                padfree_pass<THREADS, PAD, 2, true>(a, np2, nlive, r, padv);
+            else if (lt == 3 || LGE == 3)
+                padfree_pass<THREADS, PAD, 3, true>(a, np2, nlive, r, padv);
+            else if constexpr (LGE >= 4)
+                padfree_pass<THREADS, PAD, 4, true>(a, np2, nlive, r, padv);
+        });
+    }
+    for (int L = RUN; L < nlive; L <<= 1) {
+        T out[1 << LGE];
+        const bool mine = mergepath::merge_window<LGE, PAD, T>(a, (int)threadIdx.x, L, nlive, out, ~(T)0);
+        __syncthreads();
+        if (mine) mergepath::store_window<LGE, PAD, T>(a, (int)threadIdx.x, out);
+        __syncthreads();
+    }
+}
+
+// staged start and register start, as padfree_sort / padfree_sort_regs
+template <int THREADS, bool PAD, int LGE, int RUN, typename T>
+__device__ __forceinline__ void mergepath_sort(T* a, int np2, int nlive, T padv) {
+    constexpr int E = 1 << LGE;
+    for (int g = threadIdx.x; g < (nlive >> LGE); g += THREADS) {
+        T e[E];
+#pragma unroll
+        for (int m = 0; m < E; ++m) e[m] = a[sort_slot<PAD>((g << LGE) + m)];
+        sortnet::run_store<LGE, PAD>(e, a, g, CxAsc{});
+    }
+    __syncthreads();
+    mergepath_levels<THREADS, PAD, LGE, RUN>(a, np2, nlive, padv);
+}
+template <int THREADS, bool PAD, int LGE, int RUN, typename T>
+__device__ __forceinline__ void mergepath_sort_regs(T (&e)[1 << LGE], T* a, int np2, int nlive, T padv) {
+    if ((int)threadIdx.x < (nlive >> LGE)) sortnet::run_store<LGE, PAD>(e, a, (int)threadIdx.x, CxAsc{});
+    __syncthreads();
+    mergepath_levels<THREADS, PAD, LGE, RUN>(a, np2, nlive, padv);
 }
 
 #include "scvod_k_patchwork.inc"  // Patchwork: classify / scatter / sort tiers / plane fit / arrange / ordered emission with the fused curved-voxel binning (A1-A4)
