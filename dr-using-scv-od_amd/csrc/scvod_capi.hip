@@ -222,6 +222,15 @@ struct scvod_ctx {
     // accumulators) and 8 counter words of their own, allocated by the first call; not part of the arena or the table's scratch
     Scratch ov;  // stream / ran: the last call (scvod_batch_object_visibility_stats waits for it)
     unsigned long long* ov_counters = nullptr;
+    // the ESF descriptor (scvod_esf_device / scvod_batch_object_esf, scvod_objesf.hip): a grow-only block (the workgroups' sample
+    // bytes; for the batch form the gathered members and the objects' classes) and 16 counter words of their own, allocated by the
+    // first call; not part of the arena or the table's scratch
+    Scratch esf;  // stream / ran: the last call (scvod_esf_stats waits for it)
+    unsigned long long* esf_counters = nullptr;
+    int esf_blocks = 0;  // two workgroups per CU of the device
+    hipEvent_t esf_ev = nullptr;  // orders a call behind the last one on another stream: they share the counters and the block
+    uint64_t types_serial = 0;        // counts the scvod_batch_cluster_types calls of this ctx
+    uint64_t obj_lists_types_serial = 0;  // ... at the table call whose lists the scratch holds (the class mask reads the class bytes)
     // the objects linked into tracks (scvod_object_tracks_device / scvod_batch_object_tracks, scvod_tracks.hip): a grow-only block (pose
     // and successor tables, the per-object arrays, the scan's temporary storage) and 8 counter words of their own, allocated by the
     // first call; not part of the arena or the table's scratch
@@ -1577,6 +1586,9 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->in_counters) hipFree(c->in_counters);
     if (c->ot.buf) hipFree(c->ot.buf);
     if (c->ot_counters) hipFree(c->ot_counters);
+    if (c->esf.buf) hipFree(c->esf.buf);
+    if (c->esf_counters) hipFree(c->esf_counters);
+    if (c->esf_ev) hipEventDestroy(c->esf_ev);
     if (c->ov.buf) hipFree(c->ov.buf);
     if (c->ov_counters) hipFree(c->ov_counters);
     if (c->trk.buf) hipFree(c->trk.buf);
@@ -1858,6 +1870,7 @@ int scvod_batch_cluster_types(scvod_ctx* c, void* stream, int32_t sync) {
     // the boxes and the type rules are evaluated by the clustering kernel itself (same workgroup, boxes in LDS): nothing to launch,
     // unless the region growing is on (scvod_k_rgrow.inc)
     c->rg_done = false;
+    ++c->types_serial;
     if (c->rg_on) {
         if (int rc = merge_check(c)) return rc;
         int rc = ensure_rgrow(c, 1);
@@ -2785,6 +2798,7 @@ int scvod_batch_objects(scvod_ctx* c, int32_t flags, void* d_objects, int64_t ca
     c->obj_ran = true;
     if (lists) {  // (a count-only call leaves the lists of an earlier call as they are)
         c->obj_lists_serial = c->cluster_serial;
+        c->obj_lists_types_serial = c->types_serial;
         c->obj_lists_track = use_track;
     }
     return SCVOD_OK;
@@ -3646,6 +3660,148 @@ int scvod__ctx_object_lists(scvod_ctx* c, const char* who, const long long** tab
 
 int64_t scvod_batch_object_truth_scratch_bytes(scvod_ctx* c) {
     return c ? (int64_t)c->ot.cap + (c->ot_counters ? (int64_t)sizeof(unsigned long long) * 8 : 0) : 0;
+}
+
+// ---- the ESF descriptor of grouped points and of the table's objects (scvod_objesf.hip) ----
+void scvod_esf_params_default(scvod_esf_params* p) {
+    if (!p) return;
+    p->samples = 20000;  // pcl::ESFEstimation's sample count
+    p->seed = 0u;
+    p->min_points = 3;
+    p->cls_mask = 0xFFFFFFFFu;
+    for (int k = 0; k < 4; ++k) p->reserved[k] = 0;
+}
+
+// arguments of both forms, before any device is looked for
+static int esf_check(scvod_ctx* c, const scvod_esf_params* params, const void* d_records, const float* d_sig640, int64_t cap,
+                     scvod_esf_params* p) {
+    if (!d_records || cap < 0) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (((uintptr_t)d_records & 3) || ((uintptr_t)d_sig640 & 3)) return fail(c, SCVOD_ERR_INVALID, "d_records and d_sig640 must be 4-byte aligned");
+    if (params)
+        *p = *params;
+    else
+        scvod_esf_params_default(p);
+    if (p->samples < 1 || p->samples > 65536) return fail(c, SCVOD_ERR_INVALID, "ESF: %d samples (1..65536)", p->samples);
+    if (p->min_points < 3) return fail(c, SCVOD_ERR_INVALID, "ESF: min_points %d (at least 3)", p->min_points);
+    return SCVOD_OK;
+}
+
+// the stage's counters and its block: [pts_bytes: gathered members][cls_bytes: classes][the workgroups' sample bytes]
+static int esf_reserve(scvod_ctx* c, const scvod_esf_params& p, size_t pts_bytes, size_t cls_bytes) {
+    if (!c->esf_blocks) {
+        int cus = 0;
+        HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        c->esf_blocks = 2 * (cus > 0 ? cus : 1);
+    }
+    if (int rc = counter_block(c, &c->esf_counters, 16)) return rc;
+    return scratch_reserve(c, c->esf, pts_bytes + cls_bytes + esf_work_bytes(c->esf_blocks, p.samples));
+}
+
+// the calls of a ctx share the counters and the block: one on another stream than the last waits for it on the device
+static int esf_order(scvod_ctx* c, hipStream_t st) {
+    if (!c->esf.ran || c->esf.stream == st) return SCVOD_OK;
+    if (!c->esf_ev) HIPCHK(c, hipEventCreateWithFlags(&c->esf_ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->esf_ev, c->esf.stream));
+    HIPCHK(c, hipStreamWaitEvent(st, c->esf_ev, 0));
+    return SCVOD_OK;
+}
+
+static void esf_job(scvod_ctx* c, const scvod_esf_params& p, void* d_records, float* d_sig640, int64_t cap, size_t bytes_off, EsfJob* J) {
+    J->samples = p.samples;
+    J->min_points = p.min_points;
+    J->seed = p.seed;
+    J->out = (ObjEsf*)d_records;
+    J->sig = d_sig640;
+    J->cap = (long long)cap;
+    J->sample_bytes = (uint8_t*)c->esf.buf + bytes_off;
+    J->counters = c->esf_counters;
+    J->blocks = c->esf_blocks;
+}
+
+int scvod_esf_device(scvod_ctx* c, const float* d_xyzi, const int32_t* d_begin, int64_t n_objects, const scvod_esf_params* params,
+                     void* d_records, float* d_sig640, int64_t cap, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (n_objects < 0 || (n_objects > 0 && (!d_xyzi || !d_begin))) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (((uintptr_t)d_xyzi & 15) || ((uintptr_t)d_begin & 3)) return fail(c, SCVOD_ERR_INVALID, "d_xyzi must be 16-byte and d_begin 4-byte aligned");
+    scvod_esf_params p;
+    if (int rc = esf_check(c, params, d_records, d_sig640, cap, &p)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (int rc = esf_reserve(c, p, 0, 0)) return rc;
+    if (int rc = esf_order(c, st)) return rc;
+    EsfJob J{};
+    J.pts = (const float4*)d_xyzi;
+    J.begin = d_begin;
+    J.n_host = (long long)n_objects;
+    J.cls_mask = 0xFFFFFFFFu;
+    esf_job(c, p, d_records, d_sig640, cap, 0, &J);
+    launch_esf(J, st);
+    HIPCHK(c, hipGetLastError());
+    c->esf.stream = st;
+    c->esf.ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_batch_object_esf(scvod_ctx* c, const scvod_esf_params* params, void* d_records, float* d_sig640, int64_t cap, void* stream) {
+    if (!c) return SCVOD_ERR_INVALID;
+    scvod_esf_params p;
+    if (int rc = esf_check(c, params, d_records, d_sig640, cap, &p)) return rc;
+    if (!c->obj_lists_serial) return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_esf needs a scvod_batch_objects that asked for records or members");
+    if (int rc = export_check(c, c->obj_lists_track, "scvod_batch_object_esf")) return rc;
+    if (c->obj_lists_serial != c->cluster_serial)
+        return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_esf: the last object table belongs to an earlier clustering: call scvod_batch_objects again");
+    if (c->obj_lists_types_serial != c->types_serial)  // (cls_mask selects by the class bytes: they must be those the table's records show)
+        return fail(c, SCVOD_ERR_STATE, "scvod_batch_object_esf: scvod_batch_cluster_types ran since the last object table: call scvod_batch_objects again");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : (c->last_stream ? c->last_stream : c->stream);
+    const size_t N = (size_t)(c->cap_pts > 0 ? c->cap_pts : 1);
+    const size_t M = (size_t)(c->A.total_pts > 0 ? c->A.total_pts : 1);  // (the members are points of this batch)
+    const size_t pts_bytes = M * sizeof(float4), cls_bytes = align_up(M, 256);
+    if (int rc = esf_reserve(c, p, pts_bytes, cls_bytes)) return rc;
+    if (int rc = esf_order(c, st)) return rc;
+    float4* pts = (float4*)c->esf.buf;
+    uint8_t* cls = (uint8_t*)c->esf.buf + pts_bytes;
+    const uint64_t* key_out = c->obj_keys + N;  // what the table left in the scratch; none of its caller's buffers
+    const int32_t* begin = c->obj_words + 2 * N;
+    launch_esf_gather(c->A, key_out, begin, c->obj_stats, c->rg_done ? c->rg.cls : c->A.pt_type, pts, cls, st);
+    EsfJob J{};
+    J.pts = pts;
+    J.begin = begin;
+    J.n_dev = c->obj_stats;
+    J.obj_cls = cls;
+    J.cls_mask = p.cls_mask;
+    esf_job(c, p, d_records, d_sig640, cap, pts_bytes + cls_bytes, &J);
+    launch_esf(J, st);
+    HIPCHK(c, hipGetLastError());
+    c->esf.stream = st;
+    c->esf.ran = true;
+    return SCVOD_OK;
+}
+
+int scvod_esf_stats(scvod_ctx* c, int64_t* h_out8) {
+    if (!c) return SCVOD_ERR_INVALID;
+    if (!h_out8) return fail(c, SCVOD_ERR_INVALID, "bad arguments");
+    if (!c->esf.ran) return fail(c, SCVOD_ERR_STATE, "no ESF call on this ctx yet");
+    if (int rc = read_counters(c, c->esf_counters, 8, c->esf.stream, h_out8)) return rc;
+    h_out8[7] = 0;
+    if (h_out8[3]) return fail(c, SCVOD_ERR_CAPACITY, "%lld objects, the ESF buffer holds %lld", (long long)h_out8[1], (long long)h_out8[0]);
+    return SCVOD_OK;
+}
+
+int64_t scvod_esf_scratch_bytes(scvod_ctx* c) {
+    return c ? (int64_t)c->esf.cap + (c->esf_counters ? (int64_t)sizeof(unsigned long long) * 16 : 0) : 0;
+}
+
+void scvod_esf_fold10(const float* sig640, float* out10) {
+    if (!sig640 || !out10) return;
+    for (int j = 0; j < 10; ++j) out10[j] = esf_fold(sig640, j);
+}
+
+// SSC::getFeature21 (ssc.cpp:788-795): the 11-value row, then the ten folded ESF values
+void scvod_feature_row21(const scvod_object* o, const scvod_object_shape* shape, const scvod_object_esf* esf, double* out21) {
+    if (!o || !esf || !out21) return;
+    scvod_feature_row(o, shape, out21);
+    for (int k = 0; k < 10; ++k) out21[11 + k] = (double)esf->fold10[k];
 }
 
 // ---- the objects of the table vote on the seen-through verdict (scvod_objvis.hip) ----

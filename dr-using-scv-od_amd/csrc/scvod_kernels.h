@@ -435,6 +435,30 @@ struct ShapeJob {
     FeatureParams K;
 };
 void launch_object_shapes(const Arena& A, const ShapeJob& J, hipStream_t st);
+// ESF descriptor of grouped points (scvod_esf_device / scvod_batch_object_esf; scvod_objesf.hip).  The batch form first gathers the
+// table's members and the objects' classes into the stage's scratch (launch_esf_gather), so the kernel reads one layout.
+constexpr int kEsfCachePts = 3584;      // points of an object kept in LDS (SCVOD_ESF_CACHE_POINTS): two workgroups fit a CU
+struct EsfJob {
+    const float4* pts;                  // xyzi records
+    const int32_t* begin;               // [objects + 1]
+    long long n_host;                   // objects, when n_dev is nullptr
+    const long long* n_dev;             // the table's stats ([1]: its objects) or nullptr
+    const uint8_t* obj_cls;             // [objects] or nullptr: no mask
+    uint32_t cls_mask;
+    int32_t samples, min_points;
+    uint32_t seed;
+    ObjEsf* out;                        // [cap] caller's
+    float* sig;                         // [cap][640] caller's, or nullptr
+    long long cap;
+    uint8_t* sample_bytes;              // [blocks][samples] per workgroup: what sweep 1 leaves for sweep 2
+    unsigned long long* counters;       // [8] scvod_esf_stats; [8] the next object to take
+    int32_t blocks;
+};
+size_t esf_work_bytes(int blocks, int samples);
+void launch_esf(const EsfJob& J, hipStream_t st);
+// the batch form's gather: member slot p of the table -> pts_out[p] (the point obj_load reads), object o -> cls_out[o]
+void launch_esf_gather(const Arena& A, const uint64_t* key_out, const int32_t* begin, const long long* tab_stats, const uint8_t* cls,
+                       float4* pts_out, uint8_t* cls_out, hipStream_t st);
 
 typedef void (*TimerHook)(void* user, const char* name, int begin);
 

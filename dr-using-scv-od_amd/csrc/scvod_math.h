@@ -1204,5 +1204,176 @@ SCVOD_HD void shape_finish(const float cov6[6], int n_points, const FeatureParam
     r.flags = fl;
 }
 
+// ---- the ESF descriptor of one cluster (SSC::getDescriptorByEnsembleShape, ssc.cpp:760-786; pcl::ESFEstimation of PCL 1.8's
+// features/impl/esf.hpp in structure).  The reference's numbers do not repeat (rand() seeded with time(0), an uninitialised fold
+// array), so this is the project's convention: a counter-based sampler, invalid samples skipped, integer
+// histograms.  fp32 throughout, in the written order, no contraction.  The kernel (scvod_objesf.hip) and the CPU helper
+// (tests/helpers/object_esf_ref.cpp) both call these. -------------------------------------------------------------------------------
+constexpr int kEsfGrid = 64;          // voxels per axis of the occupancy grid
+constexpr int kEsfBins = 64;          // bins per histogram
+constexpr int kEsfHists = 10;         // A3 in / out / mix, D3 in / out / mix, D2 in / out / mix, ratio
+constexpr int kEsfSig = kEsfHists * kEsfBins;
+constexpr int kEsfIn = 0, kEsfOut = 1, kEsfMix = 2;  // class of a line or a triangle; the order of scvod_object_esf::lines
+constexpr int kEsfFlagNoSample = 1, kEsfFlagFewPoints = 2, kEsfFlagExtent = 4, kEsfFlagMasked = 8;
+struct ObjEsf {  // the layout of scvod_object_esf (64 bytes)
+    float fold10[10];
+    int32_t n_valid, n_points, flags;
+    uint32_t lines[3];
+};
+// T[b] = (float)cos((b - 0.5) * pi / 126), b = 1 .. 63 (T[0] is never read): the angle bin of a cosine x is the number of b with
+// x <= T[b], so no inverse trigonometric function runs anywhere (tests/test_capi_object_esf.py checks the literals)
+#define SCVOD_ESF_COS_TABLE                                                                                                  \
+    {2.0f, 0.999922276f, 0.999300718f, 0.998057902f, 0.99619472f, 0.993712187f, 0.99061197f, 0.986895978f,                 \
+     0.982566476f, 0.977626145f, 0.972078145f, 0.965925813f, 0.959173083f, 0.951824069f, 0.943883359f,                      \
+     0.935355842f, 0.926246941f, 0.916562259f, 0.906307817f, 0.895489931f, 0.884115398f, 0.87219125f,                       \
+     0.859724939f, 0.846724212f, 0.833197117f, 0.819152057f, 0.804597795f, 0.789543331f, 0.773998082f,                      \
+     0.757971704f, 0.741474152f, 0.724515676f, 0.707106769f, 0.689258337f, 0.670981407f, 0.652287424f,                      \
+     0.63318789f, 0.613694787f, 0.593820214f, 0.57357645f, 0.552976131f, 0.532032073f, 0.510757267f,                        \
+     0.489165008f, 0.467268616f, 0.44508177f, 0.42261827f, 0.399892032f, 0.376917213f, 0.353708059f,                        \
+     0.330279052f, 0.306644738f, 0.282819808f, 0.258819044f, 0.234657407f, 0.210349888f, 0.185911611f,                      \
+     0.16135776f, 0.13670361f, 0.111964479f, 0.0871557444f, 0.0622928292f, 0.0373911932f, 0.0124663142f}
+
+SCVOD_HD uint32_t esf_mix(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x7feb352du;
+    h ^= h >> 15;
+    h *= 0x846ca68bu;
+    h ^= h >> 16;
+    return h;
+}
+// index j (0, 1, 2) of sample k in an object of n points: a function of (seed, k, n) alone
+SCVOD_HD int esf_draw(uint32_t seed, uint32_t k, int j, int n) {
+    const uint32_t h = esf_mix(seed + 0x9E3779B9u * (3u * k + (uint32_t)j + 1u));
+    return (int)(((uint64_t)h * (uint64_t)(uint32_t)n) >> 32);
+}
+SCVOD_HD float esf_dist2(float ax, float ay, float az, float bx, float by, float bz) {
+    const float dx = ax - bx, dy = ay - by, dz = az - bz;
+    return dx * dx + dy * dy + dz * dz;
+}
+// the voxel of a scaled coordinate (the points lie in [-32, 32]); a coordinate that is no number lands in voxel 0
+SCVOD_HD int esf_voxel(float v) {
+    float f = v < 0.f ? floor_f(v) + 32.0f : ceil_f(v) + 31.0f;
+    if (!(f >= 0.f)) f = 0.f;
+    if (f > 63.0f) f = 63.0f;
+    return (int)f;
+}
+SCVOD_HD bool esf_grid_test(const uint32_t* grid, int x, int y, int z) {
+    const int i = (z * kEsfGrid + y) * kEsfGrid + x;
+    return (grid[i >> 5] >> (i & 31)) & 1u;
+}
+// the line from voxel A to voxel B: m + 1 voxels, `in` of them set.  Returns the class; *cnt and *in the two counts
+SCVOD_HD int esf_line(const uint32_t* grid, const int A[3], const int B[3], int* cnt, int* in) {
+    const int dx = B[0] - A[0], dy = B[1] - A[1], dz = B[2] - A[2];
+    const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy, az = dz < 0 ? -dz : dz;
+    const int sx = dx < 0 ? -1 : 1, sy = dy < 0 ? -1 : 1, sz = dz < 0 ? -1 : 1;
+    int m = ax > ay ? ax : ay;
+    if (az > m) m = az;
+    // step t visits A_i + s_i * ((2 |d_i| t + m) / (2m)); the quotient and the remainder are carried from step to step (2 |d_i| <= 2m:
+    // the quotient grows by at most one), so no division runs
+    const int m2 = 2 * m;
+    int x = A[0], y = A[1], z = A[2], ex = m, ey = m, ez = m, n_in = 0;
+    for (int t = 0;;) {
+        n_in += esf_grid_test(grid, x, y, z) ? 1 : 0;
+        if (++t > m) break;
+        ex += 2 * ax;
+        ey += 2 * ay;
+        ez += 2 * az;
+        if (ex >= m2) ex -= m2, x += sx;
+        if (ey >= m2) ey -= m2, y += sy;
+        if (ez >= m2) ez -= m2, z += sz;
+    }
+    *cnt = m + 1;
+    *in = n_in;
+    return n_in >= m ? kEsfIn : (n_in <= 7 ? kEsfOut : kEsfMix);
+}
+SCVOD_HD int esf_triangle_class(int sum_in, int sum_cnt) { return sum_in <= 21 ? kEsfOut : (sum_cnt - sum_in < 4 ? kEsfIn : kEsfMix); }
+// angle bin of the corner between two edges of lengths l1, l2 with scalar product dot.  T: SCVOD_ESF_COS_TABLE (descending, so the
+// count of b with x <= T[b] is found by bisection)
+SCVOD_HD int esf_angle_bin(const float* T, float dot, float l1, float l2) {
+    float x = fabs_f(dot) / (l1 * l2);
+    if (x > 1.0f) x = 1.0f;
+    int n = 0;
+    for (int step = 32; step; step >>= 1)
+        if (x <= T[n + step]) n += step;
+    return n;
+}
+SCVOD_HD int esf_bin63(float v) { return (int)floor_f(v * 63.0f + 0.5f); }
+SCVOD_HD int esf_bin_of(float d, float d_max) { return esf_bin63(d / d_max); }
+
+struct EsfSample {      // what a sample yields before its lines are traced
+    int i[3];
+    float a, b, c;      // edge lengths 12, 13, 23
+    float heron;
+    bool valid;
+};
+// P(i, xyz): the scaled point i of the object
+template <class P>
+SCVOD_HD EsfSample esf_sample(uint32_t seed, uint32_t k, int n, const P& pt, float u[3][3]) {
+    EsfSample s;
+    for (int j = 0; j < 3; ++j) s.i[j] = esf_draw(seed, k, j, n);
+    s.valid = s.i[0] != s.i[1] && s.i[0] != s.i[2] && s.i[1] != s.i[2];
+    s.a = s.b = s.c = s.heron = 0.f;
+    if (!s.valid) return s;
+    for (int j = 0; j < 3; ++j) pt(s.i[j], u[j]);
+    s.a = sqrt_f(esf_dist2(u[0][0], u[0][1], u[0][2], u[1][0], u[1][1], u[1][2]));
+    s.b = sqrt_f(esf_dist2(u[0][0], u[0][1], u[0][2], u[2][0], u[2][1], u[2][2]));
+    s.c = sqrt_f(esf_dist2(u[1][0], u[1][1], u[1][2], u[2][0], u[2][1], u[2][2]));
+    const float h = (s.a + s.b + s.c) * 0.5f;
+    s.heron = ((h * (h - s.a)) * (h - s.b)) * (h - s.c);
+    s.valid = s.heron > 0.001f;
+    return s;
+}
+// the three corner bins of a valid sample: corner 1 (edges a, b), corner 2 (a, c), corner 3 (b, c)
+SCVOD_HD void esf_corner_bins(const float* T, float u[3][3], const EsfSample& s, int bins[3]) {
+    float e12[3], e13[3], e23[3];
+    for (int a = 0; a < 3; ++a) {
+        e12[a] = u[1][a] - u[0][a];
+        e13[a] = u[2][a] - u[0][a];
+        e23[a] = u[2][a] - u[1][a];
+    }
+    bins[0] = esf_angle_bin(T, e12[0] * e13[0] + e12[1] * e13[1] + e12[2] * e13[2], s.a, s.b);
+    bins[1] = esf_angle_bin(T, e12[0] * e23[0] + e12[1] * e23[1] + e12[2] * e23[2], s.a, s.c);
+    bins[2] = esf_angle_bin(T, e13[0] * e23[0] + e13[1] * e23[1] + e13[2] * e23[2], s.b, s.c);
+}
+// the lines 12, 13, 23 of a sample: class per line, the triangle's class, the ratio bin of a MIX line (else -1)
+struct EsfLines {
+    int cls[3], ratio_bin[3], tri;
+};
+SCVOD_HD EsfLines esf_trace(const uint32_t* grid, float u[3][3]) {
+    int v[3][3];
+    for (int j = 0; j < 3; ++j)
+        for (int a = 0; a < 3; ++a) v[j][a] = esf_voxel(u[j][a]);
+    EsfLines L;
+    int sum_in = 0, sum_cnt = 0;
+    const int from[3] = {0, 0, 1}, to[3] = {1, 2, 2};
+    for (int l = 0; l < 3; ++l) {
+        int cnt, in;
+        L.cls[l] = esf_line(grid, v[from[l]], v[to[l]], &cnt, &in);
+        L.ratio_bin[l] = L.cls[l] == kEsfMix ? esf_bin63((float)in / (float)cnt) : -1;
+        sum_in += in;
+        sum_cnt += cnt;
+    }
+    L.tri = esf_triangle_class(sum_in, sum_cnt);
+    return L;
+}
+// histogram rows of the signature
+SCVOD_HD int esf_row_a3(int tri) { return tri; }
+SCVOD_HD int esf_row_d3(int tri) { return 3 + tri; }
+SCVOD_HD int esf_row_d2(int line) { return 6 + line; }
+constexpr int kEsfRowRatio = 9;
+// one entry of the unnormalised signature from its counter
+SCVOD_HD float esf_sig_value(int i, int count) {
+    const float w[kEsfHists] = {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 1.0f, 1.0f, 2.0f, 2.0f, 2.0f};
+    const int h = i / kEsfBins;
+    const float value = h < 3 ? (float)count / 3.0f : (float)count;
+    return value * w[h];
+}
+// fold10[j] of a normalised signature: ssc.cpp:774-776 from a zeroed array
+SCVOD_HD float esf_fold(const float* sig, int j) {
+    double s = 0.0;
+    for (int i = j; i < kEsfSig; i += 10) s += (double)sig[i];
+    return (float)s;
+}
+
 }  // namespace scvod
 #endif  // SCVOD_MATH_H_

@@ -67,6 +67,21 @@ class FeatureParams(C.Structure):
                                           "kAnisotropyMax", "kEigenEntropyMax", "kChangeOfCurvatureMax")]
 
 
+# struct scvod_object_esf (include/scvod.h): the ESF descriptor of one object, 64 bytes
+OBJECT_ESF_DTYPE = np.dtype([("fold10", "f4", 10), ("n_valid", "i4"), ("n_points", "i4"), ("flags", "i4"), ("lines", "u4", 3)])
+ESF_SIG = 640
+ESF_CACHE_POINTS = 3584  # SCVOD_ESF_CACHE_POINTS
+
+
+class ObjectEsf(C.Structure):
+    _fields_ = [("fold10", C.c_float * 10), ("n_valid", C.c_int32), ("n_points", C.c_int32), ("flags", C.c_int32), ("lines", C.c_uint32 * 3)]
+
+
+class EsfParams(C.Structure):
+    """struct scvod_esf_params (include/scvod.h)"""
+    _fields_ = [("samples", C.c_int32), ("seed", C.c_uint32), ("min_points", C.c_int32), ("cls_mask", C.c_uint32), ("reserved", C.c_int32 * 4)]
+
+
 class EvalParams(C.Structure):
     """struct scvod_eval_params (include/scvod.h)"""
     _fields_ = [("voxelsize", C.c_double), ("n_dynamic_classes", C.c_int32), ("dynamic_classes", C.c_uint16 * 16)]
@@ -445,6 +460,13 @@ def load_lib():
         "scvod_batch_object_shapes_stats": (C.c_int, [vp, vp]),
         "scvod_feature_row": (None, [vp, vp, vp]),
         "scvod_compare_feature": (f32, [vp, vp]),
+        "scvod_esf_params_default": (None, [C.POINTER(EsfParams)]),
+        "scvod_esf_device": (C.c_int, [vp, vp, vp, i64, C.POINTER(EsfParams), vp, vp, i64, vp]),
+        "scvod_batch_object_esf": (C.c_int, [vp, C.POINTER(EsfParams), vp, vp, i64, vp]),
+        "scvod_esf_stats": (C.c_int, [vp, vp]),
+        "scvod_esf_scratch_bytes": (i64, [vp]),
+        "scvod_esf_fold10": (None, [vp, vp]),
+        "scvod_feature_row21": (None, [vp, vp, vp, vp]),
         "scvod_batch_timings": (C.c_int, [vp, vp, vp, i32]),
         "scvod_set_timing": (C.c_int, [vp, i32]),
         "scvod_nn_search": (C.c_int, [vp, vp, i32, vp, i32, f32, vp, vp, vp]),
@@ -573,7 +595,9 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_component_visibility_params_default", "scvod_map_component_visibility",
                     "scvod_map_component_visibility_stats",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
-                    "scvod_map_split"]
+                    "scvod_map_split",
+                    "scvod_esf_params_default", "scvod_esf_device", "scvod_batch_object_esf", "scvod_esf_stats", "scvod_esf_scratch_bytes",
+                    "scvod_esf_fold10", "scvod_feature_row21"]
 
 
 def eval_params_default(voxelsize=None, dynamic_classes=None):
@@ -843,6 +867,35 @@ def feature_row(obj, shape=None):
     out = np.zeros(11, np.float64)
     load_lib().scvod_feature_row(o.ctypes.data_as(C.c_void_p), sh.ctypes.data_as(C.c_void_p) if sh is not None else None,
                                  out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def esf_params_default(**kw):
+    """scvod_esf_params with the defaults (20000 samples, seed 0, min_points 3, every class), fields overridden by keyword"""
+    p = EsfParams()
+    load_lib().scvod_esf_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, int(v))
+    return p
+
+
+def esf_fold10(sig640):
+    """fold10 of one normalised 640-value signature (float32 [10]).  Host only"""
+    sig = np.ascontiguousarray(sig640, np.float32)
+    assert sig.size == ESF_SIG
+    out = np.zeros(10, np.float32)
+    load_lib().scvod_esf_fold10(sig.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def feature_row21(obj, shape, esf):
+    """SSC::getFeature21: feature_row(obj, shape) and the fold10 of one OBJECT_ESF_DTYPE record.  Host only"""
+    o = np.ascontiguousarray(obj, OBJECT_DTYPE).reshape(1)
+    sh = np.ascontiguousarray(shape, OBJECT_SHAPE_DTYPE).reshape(1) if shape is not None else None
+    e = np.ascontiguousarray(esf, OBJECT_ESF_DTYPE).reshape(1)
+    out = np.zeros(21, np.float64)
+    load_lib().scvod_feature_row21(o.ctypes.data_as(C.c_void_p), sh.ctypes.data_as(C.c_void_p) if sh is not None else None,
+                                   e.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
     return out
 
 
@@ -1368,6 +1421,45 @@ class Ctx:
         out = np.zeros(4, np.int64)
         self._chk(self.lib.scvod_batch_object_shapes_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return dict(written=int(out[0]), objects=int(out[1]), not_finite=int(out[2]), overflow=bool(out[3]))
+
+    # ---- the ESF descriptor (include/scvod.h: scvod_esf_device, scvod_batch_object_esf) ----
+    @staticmethod
+    def _esf_buffers(d_records, d_sig640):
+        nbytes = d_records.numel() * d_records.element_size()
+        assert d_records.is_contiguous() and nbytes % OBJECT_ESF_DTYPE.itemsize == 0
+        cap = nbytes // OBJECT_ESF_DTYPE.itemsize
+        if d_sig640 is not None:
+            assert d_sig640.is_contiguous() and d_sig640.element_size() == 4 and d_sig640.numel() >= cap * ESF_SIG
+        return cap, C.c_void_p(d_sig640.data_ptr()) if d_sig640 is not None else None
+
+    def esf_device(self, d_xyzi, d_begin, d_records, d_sig640=None, params=None, stream=None):
+        """one OBJECT_ESF_DTYPE record per run [d_begin[o], d_begin[o + 1]) of d_xyzi (float32 [n, 4] and int32 [objects + 1] torch
+        device tensors) into d_records (a contiguous device tensor of 64-byte rows) and, optionally, the normalised signatures
+        into d_sig640 (float32 [cap, 640]).  params: an EsfParams (None: the defaults).  Asynchronous on `stream`"""
+        assert d_xyzi.is_contiguous() and d_xyzi.element_size() == 4 and d_begin.is_contiguous() and d_begin.element_size() == 4
+        cap, sig = self._esf_buffers(d_records, d_sig640)
+        self._chk(self.lib.scvod_esf_device(self.h, C.c_void_p(d_xyzi.data_ptr()), C.c_void_p(d_begin.data_ptr()), d_begin.numel() - 1,
+                                            C.byref(params) if params is not None else None, C.c_void_p(d_records.data_ptr()), sig, cap,
+                                            C.c_void_p(stream or 0)))
+
+    def batch_object_esf(self, d_records, d_sig640=None, params=None, stream=None):
+        """the same for every object of the last batch_objects that asked for more than the counts, in table order; params.cls_mask
+        selects by class.  Asynchronous on `stream`"""
+        cap, sig = self._esf_buffers(d_records, d_sig640)
+        self._chk(self.lib.scvod_batch_object_esf(self.h, C.byref(params) if params is not None else None, C.c_void_p(d_records.data_ptr()),
+                                                  sig, cap, C.c_void_p(stream or 0)))
+
+    def esf_stats(self):
+        """{written, objects, flagged, overflow, valid_samples, masked, uncached} of the last ESF call; synchronises its stream;
+        raises after an overflow"""
+        out = np.zeros(8, np.int64)
+        self._chk(self.lib.scvod_esf_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return dict(written=int(out[0]), objects=int(out[1]), flagged=int(out[2]), overflow=bool(out[3]), valid_samples=int(out[4]),
+                    masked=int(out[5]), uncached=int(out[6]))
+
+    def esf_scratch_bytes(self):
+        """device scratch of the ESF stage on this ctx (not part of arena_bytes or any other stage's scratch)"""
+        return int(self.lib.scvod_esf_scratch_bytes(self.h))
 
     # ---- the truth label of the table's objects (include/scvod.h: scvod_batch_object_truth) ----
     def batch_object_truth(self, d_gt_label, params=None, cap=None, stream=None):

@@ -978,6 +978,80 @@ void scvod_feature_row(const scvod_object* object, const scvod_object_shape* sha
  * 0.2, 0.2, 0.2, 0.2, 0.6, 0.2, 0.0 of ssc.cpp:900-909 (column 10 is not read). */
 float scvod_compare_feature(const double* a, const double* b);
 
+/* ---- the ESF descriptor of an object, on the device (opt-in: nothing runs or is allocated unless it is called) ----------------------
+ * Reference analogue: SSC::getDescriptorByEnsembleShape (src/ssc.cpp:760-786: pcl::ESFEstimation's 640-bin signature folded to ten
+ * values) and SSC::getFeature21 (ssc.cpp:788-795: the 11-value row and those ten).  Parity is unpinned by construction: PCL seeds
+ * rand() with time(0), so the reference's numbers do not repeat, and ssc.cpp:773 folds into an uninitialised array.  The convention
+ * here keeps the structure of PCL 1.8's features/impl/esf.hpp with a counter-based sampler (the esf_* functions
+ * of csrc/scvod_math.h are the definition).  All fp32, in the written order, no contraction:
+ *   extent     c = the centroid by the sequential sums of scvod_object::center; q = p - c; r = sqrt(max(qx*qx + qy*qy + qz*qz));
+ *              u = q * (32.0f / r).  r zero or not finite: flags bit 2
+ *   voxels     of a coordinate v: v < 0 ? floor(v) + 32 : ceil(v) + 31, clamped to 0..63; every point sets the 3x3x3 voxels around
+ *              its own in a 64^3 occupancy grid
+ *   sampler    sample k draws i_j = mulhi32(mix(seed + 0x9E3779B9 * (3k + j + 1)), n), j = 0, 1, 2, with mix the 32-bit finaliser
+ *              h ^= h>>16; h *= 0x7feb352d; h ^= h>>15; h *= 0x846ca68b; h ^= h>>16: a function of (seed, k, n) alone, so an object's
+ *              descriptor does not depend on the batch around it.  An invalid sample is skipped, never redrawn
+ *   valid      the indices differ pairwise and, with a, b, c the distances 12, 13, 23 and s = (a+b+c)*0.5f,
+ *              ((s*(s-a))*(s-b))*(s-c) > 0.001f
+ *   lines      12, 13, 23 between the voxels A, B of the two points: with d = B - A and m = max |d_i|, t = 0..m visits
+ *              A_i + sgn(d_i) * ((2|d_i| t + m) / (2m)) (integers); count = m + 1, in = the visited voxels that are set.  IN iff
+ *              in >= count - 1, else OUT iff in <= 7, else MIX with ratio (float)in / (float)count
+ *   triangle   OUT iff sum(in) <= 21, else IN iff sum(count) - sum(in) < 4, else MIX
+ *   bins       ten histograms of 64 integer counters: A3 in/out/mix (three corner bins per sample, by triangle class; the bin of
+ *              x = min(1, |dot| / (len1*len2)) is the number of b in 1..63 with x <= (float)cos((b - 0.5) pi / 126)), D3 in/out/mix
+ *              (sqrt(sqrt(heron)) / max_d3), D2 in/out/mix (a, b, c by their own line's class, / max_d2), ratio (MIX lines); a
+ *              value v in [0, 1] falls into bin (int)floor(v * 63.0f + 0.5f); the maxima are those of the object's valid samples
+ *   signature  sig[h*64 + b] = value * w[h], value = (float)count / 3.0f for the A3 rows, else (float)count,
+ *              w = {.5, .5, .5, .5, .5, 1, 1, 2, 2, 2}; total = the sequential sum over i = 0..639; sig[i] /= total
+ *   fold10     fold10[j] = (float) of the double sum of sig[i] over ascending i with i % 10 == j
+ * Every number is the same bits on the device, in the CPU helper of the tests and from run to run.  64 bytes: */
+typedef struct scvod_object_esf {
+    float fold10[10];   /* the ten values getDescriptorByEnsembleShape returns                                                    */
+    int32_t n_valid;    /* samples that passed the validity tests                                                                */
+    int32_t n_points;
+    int32_t flags;      /* bit 0: no valid sample; bit 1: fewer than min_points points; bit 2: zero or non-finite extent; bit 3:
+                           left out by cls_mask.  A flagged record has fold10 and its signature all zero, never NaN              */
+    uint32_t lines[3];  /* lines of the valid samples that were IN / OUT / MIX                                                    */
+} scvod_object_esf;
+typedef struct scvod_esf_params {
+    int32_t samples;     /* point triples drawn per object, 1 .. 65536 (PCL: 20000)                                              */
+    uint32_t seed;
+    int32_t min_points;  /* objects of fewer points are flagged, not computed; at least 3                                        */
+    uint32_t cls_mask;   /* bit c selects the objects with cls == c; read by scvod_batch_object_esf only                         */
+    int32_t reserved[4]; /* 0                                                                                                    */
+} scvod_esf_params;
+/* 20000, 0, 3, 0xFFFFFFFF */
+void scvod_esf_params_default(scvod_esf_params* p);
+/* One record per object of a cloud the caller groups: d_xyzi holds 16-byte xyzi records on the device, d_begin [n_objects + 1] int32
+ * on the device; object o is the run [d_begin[o], d_begin[o + 1]) in the given order (an empty run is an object of no points).
+ * params NULL = the defaults.  d_records [cap] scvod_object_esf; d_sig640 NULL or float [cap][640], the normalised signatures.
+ * Stream-ordered (stream NULL = the ctx's stream), never synchronises; reads the inputs and writes the two buffers and scratch of
+ * its own (scvod_esf_scratch_bytes; scvod_arena_bytes and every other stage's scratch stay as they are).  Argument errors
+ * (SCVOD_ERR_INVALID: a NULL ctx, d_records, or d_xyzi / d_begin with n_objects > 0; n_objects or cap negative; samples outside
+ * 1..65536; min_points < 3; misaligned pointers) are reported before a device is looked for.  Nothing is written at or behind cap;
+ * the overflow is latched until the next call.  The ESF calls of a ctx share its counters and scratch: a call on another stream
+ * than the ctx's last ESF call waits for that call on the device (an event, no host synchronisation), so they never overlap. */
+int scvod_esf_device(scvod_ctx* ctx, const float* d_xyzi, const int32_t* d_begin, int64_t n_objects, const scvod_esf_params* params,
+                     void* d_records, float* d_sig640, int64_t cap, void* stream);
+/* The same on the table the last scvod_batch_objects left in its scratch: the members of an object in ascending apri index, gathered
+ * as scvod_batch_object_shapes gathers them; cls_mask selects by scvod_object::cls (the others get flags bit 3).  State rules and
+ * error codes are exactly those of scvod_batch_object_shapes (stream NULL = the stream of the ctx's last batch call); a
+ * SCVOD_OBJ_NO_TRACK table is fine.  One rule more, because the mask reads the class bytes: SCVOD_ERR_STATE when
+ * scvod_batch_cluster_types ran since that table call (its records may show other classes): call scvod_batch_objects again. */
+int scvod_batch_object_esf(scvod_ctx* ctx, const scvod_esf_params* params, void* d_records, float* d_sig640, int64_t cap, void* stream);
+/* h_out8 = {records written, objects, written records with flags != 0, 1 when the objects outgrew cap, valid samples summed over
+ * the written records, objects left out by cls_mask, objects whose points did not fit the on-chip cache (SCVOD_ESF_CACHE_POINTS),
+ * 0} of the last ESF call.  Synchronises that call's stream.  SCVOD_ERR_CAPACITY after an overflow, SCVOD_ERR_STATE before the
+ * first call. */
+int scvod_esf_stats(scvod_ctx* ctx, int64_t* h_out8);
+#define SCVOD_ESF_CACHE_POINTS 3584 /* objects of up to this many points are sampled from on-chip memory */
+/* bytes of device scratch the ESF stage holds on this ctx (0 before the first call) */
+int64_t scvod_esf_scratch_bytes(scvod_ctx* ctx);
+/* Host only.  fold10 of a normalised 640-value signature, as the record holds it. */
+void scvod_esf_fold10(const float* sig640, float* out10);
+/* Host only.  SSC::getFeature21: columns 0-10 are scvod_feature_row(object, shape), columns 11-20 esf->fold10 as doubles. */
+void scvod_feature_row21(const scvod_object* object, const scvod_object_shape* shape, const scvod_object_esf* esf, double* out21);
+
 /* ---- evaluation against labelled truth, on the device (opt-in: nothing runs or is allocated unless it is called) ------------------
  * Reference analogue: tool/analysis.py:124-194 -- the counters behind the published PR / RR / F1 table -- and the colour classes of the
  * map viewer (src/evaluate.cpp:79-145).  A ground-truth point is an INLIER when its nearest estimate point (squared distance
