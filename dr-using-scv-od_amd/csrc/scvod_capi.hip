@@ -17,6 +17,7 @@
 #include <algorithm>
 #include "scvod_kernels.h"
 #include "scvod_chain.h"
+extern "C" void scvod__register_free(void* state);  // scvod_register.hip
 
 using namespace scvod;
 
@@ -229,6 +230,9 @@ struct scvod_ctx {
     unsigned long long* esf_counters = nullptr;
     int esf_blocks = 0;  // two workgroups per CU of the device
     hipEvent_t esf_ev = nullptr;  // orders a call behind the last one on another stream: they share the counters and the block
+    // the pose refinement against a cloud (scvod_register_device, scvod_register.hip): the state of that unit (its grow-only block, the
+    // staged poses and offsets), made by the first call; not part of the arena
+    void* reg_state = nullptr;
     uint64_t types_serial = 0;        // counts the scvod_batch_cluster_types calls of this ctx
     uint64_t obj_lists_types_serial = 0;  // ... at the table call whose lists the scratch holds (the class mask reads the class bytes)
     // the objects linked into tracks (scvod_object_tracks_device / scvod_batch_object_tracks, scvod_tracks.hip): a grow-only block (pose
@@ -1391,6 +1395,13 @@ extern "C" int scvod__ctx_view(scvod_ctx* c, Arena* arena, int* device, int* tra
 // the three index lists of the batch, written before anything queued on `stream` behind this call reads them (k_map_mark_lists)
 extern "C" int scvod__ctx_ensure_lists(scvod_ctx* c, void* stream) { return ensure_lists(c, (hipStream_t)stream); }
 extern "C" void* scvod__ctx_stream(scvod_ctx* c, void* stream) { return stream ? stream : (void*)(c->last_stream ? c->last_stream : c->stream); }
+// scvod_register.hip: where its state hangs on the ctx, the ctx's device and own stream, and its error text
+extern "C" void** scvod__ctx_register_slot(scvod_ctx* c, int* device, void** own_stream) {
+    *device = c->device;
+    *own_stream = (void*)c->stream;
+    return &c->reg_state;
+}
+extern "C" int scvod__ctx_fail(scvod_ctx* c, int code, const char* msg) { return fail(c, code, "%s", msg); }
 
 extern "C" {
 
@@ -1589,6 +1600,7 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->esf.buf) hipFree(c->esf.buf);
     if (c->esf_counters) hipFree(c->esf_counters);
     if (c->esf_ev) hipEventDestroy(c->esf_ev);
+    scvod__register_free(c->reg_state);
     if (c->ov.buf) hipFree(c->ov.buf);
     if (c->ov_counters) hipFree(c->ov_counters);
     if (c->trk.buf) hipFree(c->trk.buf);

@@ -449,6 +449,7 @@ void scvod_map_destroy(scvod_map* m) {
     if (m->f_buf) hipFree(m->f_buf);
     if (m->c_buf) hipFree(m->c_buf);
     if (m->v_buf) hipFree(m->v_buf);
+    scvod__register_free(m->reg_state);
     delete m;
 }
 

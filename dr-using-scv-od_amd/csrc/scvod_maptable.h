@@ -56,6 +56,8 @@ struct scvod_map {
     size_t v_cap = 0;
     hipStream_t v_stream = nullptr;  // the stream of the last component vote
     bool v_ran = false;
+    // scvod_map_register: the state of scvod_register.hip (its grow-only block, the staged poses and offsets), made by the first call
+    void* reg_state = nullptr;
     std::string err;
 };
 
@@ -216,6 +218,9 @@ extern "C" int scvod__ctx_types_valid(scvod_ctx* c);
 extern "C" int scvod__ctx_view(scvod_ctx* ctx, scvod::Arena* arena, int* device, int* track_valid, int* batch_valid, int* n_scans,
                                int* max_scan_pts, int* batch_mode, int* num_min_pts);
 extern "C" void* scvod__ctx_stream(scvod_ctx* ctx, void* stream);
+extern "C" void** scvod__ctx_register_slot(scvod_ctx* ctx, int* device, void** own_stream);
+extern "C" int scvod__ctx_fail(scvod_ctx* ctx, int code, const char* msg);
+extern "C" void scvod__register_free(void* state);  // scvod_register.hip: frees what a reg_state slot holds (NULL: nothing)
 extern "C" int scvod__ctx_ensure_lists(scvod_ctx* ctx, void* stream);  // ground_idx / nonground_idx / rejected_src of a lean batch, before their reader
 extern "C" int scvod__ctx_object_lists(scvod_ctx* ctx, const char* who, const long long** tab_stats, const uint64_t** key_out, const int32_t** begin,
                                        const char** err);

@@ -1375,5 +1375,204 @@ SCVOD_HD float esf_fold(const float* sig, int j) {
     return (float)s;
 }
 
+// ---- pose refinement (scvod_register.hip): one Gauss-Newton step, defined once.  Not from the reference. ----
+// The running pose T of a scan is a row-major 3x4 in fp64.  A source point is moved with the fp32 rounding of T (reg_move, the map
+// kernels' expression), its correspondence q is the target's nearest point, and the step minimises the residual over a RIGHT
+// perturbation T <- T * exp(xi), xi = (omega, v): the Jacobian lives in the sensor frame and is bounded by max_range wherever the
+// world origin is.  Every term of the normal equations is an fp64 expression of the fp32 inputs in the order written below, scaled
+// by 2^20, rounded to nearest (ties to even) and summed as int64: integer sums do not depend on the order of the points.
+//
+// The scale.  With |p| <= max_range <= 256 = 2^8 and a unit normal, every entry of J is at most 2^8 in size and |r| <= 2^8 (r is
+// bounded by the distance gate, max_dist <= 256): every product J_i * J_j, J_i * r, r * r is at most 2^16, scaled 2^36, and its
+// rounding adds at most 1/2.  A point contributes at most three rows and a scan at most 2^24 points: |sum| <= 3 * 2^24 * (2^36 + 1)
+// < 2^62 < 2^63.  The rounding error of a term is 2^-21; over n terms of either sign the sum is off by about 2^-21 * sqrt(n) of n
+// units, far below the fp32 rounding of the inputs.  2^36 < 2^51 is also what reg_fix's rounding trick needs.
+// Words of a scan's sums: the 21 upper-triangle entries of J^T J row by row, the 6 of J^T r, sum r^2, the correspondences, and the
+// five skip counters {NaN, range, label, no correspondence, normal}.
+constexpr int kRegWords = 40;  // per scan (34 used)
+constexpr int kRegB = 21, kRegR2 = 27, kRegCorr = 28, kRegSkip = 29, kRegUsed = 34, kRegTerms = 28;
+constexpr double kRegScale = 1048576.0, kRegInvScale = 1.0 / 1048576.0;  // 2^20
+constexpr double kRegNormalEps = 1e-6;  // a target normal shorter than this (or not finite) gives no row
+constexpr int kRegGo = 0, kRegConverged = 1, kRegDegenerate = 2;  // SCVOD_REG_MAX_ITERATIONS / CONVERGED / DEGENERATE
+
+// x * 2^20 rounded to nearest, ties to even, for |x| < 2^31: y + 1.5 * 2^52 lies in [2^52, 2^53), where the 52 stored mantissa bits
+// ARE the integer y + 2^51 after the addition's own rounding.  One fp64 addition and two integer operations, no conversion.
+SCVOD_HD long long reg_fix(double x) {
+    const double y = x * kRegScale;
+    return (long long)(d2u(y + 6755399441055744.0) & 0xfffffffffffffull) - (1ll << 51);
+}
+// the fp32 rounding of the running pose, and a point moved by it
+SCVOD_HD void reg_pose32(const double* T, float* Tf) {
+    for (int i = 0; i < 12; ++i) Tf[i] = (float)T[i];
+}
+SCVOD_HD void reg_move(const float* T, float x, float y, float z, float* w) {
+    w[0] = T[0] * x + T[1] * y + T[2] * z + T[3];
+    w[1] = T[4] * x + T[5] * y + T[6] * z + T[7];
+    w[2] = T[8] * x + T[9] * y + T[10] * z + T[11];
+}
+// 0: the point takes part; 1: a NaN coordinate; 2: sensor-frame range beyond max_range (range2 = max_range * max_range in fp32)
+SCVOD_HD int reg_gate(float x, float y, float z, float range2) {
+    if (x != x || y != y || z != z) return 1;
+    return ((x * x + y * y) + z * z > range2) ? 2 : 0;
+}
+// one row (J, r) into the 28 term sums
+SCVOD_HD void reg_row(const double* J, double r, long long* acc) {
+    int k = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 6; ++i) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = i; j < 6; ++j) acc[k++] += reg_fix(J[i] * J[j]);
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 6; ++i) acc[kRegB + i] += reg_fix(J[i] * r);
+    acc[kRegR2] += reg_fix(r * r);
+}
+// the sensor-frame residual r = p - R^T (q - t): dq = q - t, u = R^T dq summed left to right, r = p - u
+SCVOD_HD void reg_residual(const double* T, const float* p, const float* q, double* r) {
+    const double d0 = (double)q[0] - T[3], d1 = (double)q[1] - T[7], d2 = (double)q[2] - T[11];
+    r[0] = (double)p[0] - ((T[0] * d0 + T[4] * d1) + T[8] * d2);
+    r[1] = (double)p[1] - ((T[1] * d0 + T[5] * d1) + T[9] * d2);
+    r[2] = (double)p[2] - ((T[2] * d0 + T[6] * d1) + T[10] * d2);
+}
+// point-to-point: three rows, J = [ -[p]x , I ]
+SCVOD_HD void reg_point_terms(const double* T, const float* p, const float* q, long long* acc) {
+    double r[3];
+    reg_residual(T, p, q, r);
+    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+    const double J0[6] = {0.0, z, -y, 1.0, 0.0, 0.0}, J1[6] = {-z, 0.0, x, 0.0, 1.0, 0.0}, J2[6] = {y, -x, 0.0, 0.0, 0.0, 1.0};
+    reg_row(J0, r[0], acc);
+    reg_row(J1, r[1], acc);
+    reg_row(J2, r[2], acc);
+}
+// point-to-plane: one row.  nu = n / sqrt(n . n) in fp64, n_l = R^T nu, e = n_l . r, J = [ (p x n_l)^T , n_l^T ].  false: the normal is
+// not finite or shorter than kRegNormalEps, and nothing was added
+SCVOD_HD bool reg_plane_terms(const double* T, const float* p, const float* q, const float* n, long long* acc) {
+    const double a = (double)n[0], b = (double)n[1], c = (double)n[2];
+    const double nn = (a * a + b * b) + c * c;
+    if (!(nn >= kRegNormalEps * kRegNormalEps) || !finite_d(nn)) return false;
+    const double len = sqrt_d(nn);
+    const double u0 = a / len, u1 = b / len, u2 = c / len;
+    const double l0 = (T[0] * u0 + T[4] * u1) + T[8] * u2, l1 = (T[1] * u0 + T[5] * u1) + T[9] * u2, l2 = (T[2] * u0 + T[6] * u1) + T[10] * u2;
+    double r[3];
+    reg_residual(T, p, q, r);
+    const double e = (l0 * r[0] + l1 * r[1]) + l2 * r[2];
+    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+    const double J[6] = {y * l2 - z * l1, z * l0 - x * l2, x * l1 - y * l0, l0, l1, l2};
+    reg_row(J, e, acc);
+    return true;
+}
+// The solve and the update of one scan from its sums (kRegUsed words); T is updated in place unless the scan is degenerate.
+//   H = sums / 2^20, g = -J^T r; H_ii += lambda * H_ii; LDL^T in place, a pivot that is not above pivot_eps * max_i H_ii is DEGENERATE,
+//   as are fewer than min_corr correspondences and a step that is not finite.  Sums run over k ascending, one subtraction per term.
+//   Update: the unit quaternion of (1, omega / 2) (a Cayley step: first-order correct, fixed point xi = 0, + - * / sqrt only), dR its
+//   rotation matrix, R <- R dR, t <- R v + t.  dR is orthonormal to a few ulp of fp64 by construction, so over max_iterations <= 64
+//   steps the product leaves the orthonormality of the initial matrix (an fp32 one, about 1e-7) by at most 64 * a few 1e-16: nothing
+//   is re-orthonormalised.
+// Returns kRegGo, kRegConverged (|omega| < eps_rot and |v| < eps_trans, after the update) or kRegDegenerate.
+SCVOD_HD int reg_solve_update(const long long* s, long long min_corr, double lambda, double pivot_eps, double eps_rot, double eps_trans, double* T,
+                              double* omega_norm, double* v_norm) {
+    *omega_norm = 0.0;
+    *v_norm = 0.0;
+    if (s[kRegCorr] < min_corr) return kRegDegenerate;
+    double H[6][6], x[6];
+    int k = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 6; ++i) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = i; j < 6; ++j) {
+            H[i][j] = (double)s[k] * kRegInvScale;
+            H[j][i] = H[i][j];
+            ++k;
+        }
+    }
+    double top = 0.0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 6; ++i) {
+        x[i] = -((double)s[kRegB + i] * kRegInvScale);
+        H[i][i] = H[i][i] + lambda * H[i][i];
+        if (H[i][i] > top) top = H[i][i];
+    }
+    const double floor_pivot = pivot_eps * top;
+    // LDL^T in place: d_j on the diagonal, L below it
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 6; ++j) {
+        double d = H[j][j];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int m = 0; m < j; ++m) d = d - (H[j][m] * H[j][m]) * H[m][m];
+        if (!(d > floor_pivot)) return kRegDegenerate;
+        H[j][j] = d;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int i = j + 1; i < 6; ++i) {
+            double a = H[i][j];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int m = 0; m < j; ++m) a = a - (H[i][m] * H[j][m]) * H[m][m];
+            H[i][j] = a / d;
+        }
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 6; ++i) {  // L z = g
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int m = 0; m < i; ++m) x[i] = x[i] - H[i][m] * x[m];
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 6; ++i) x[i] = x[i] / H[i][i];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 5; i >= 0; --i) {  // L^T xi = y
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int m = i + 1; m < 6; ++m) x[i] = x[i] - H[m][i] * x[m];
+    }
+    const double on = sqrt_d((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), vn = sqrt_d((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
+    if (!finite_d(on) || !finite_d(vn)) return kRegDegenerate;
+    const double hx = 0.5 * x[0], hy = 0.5 * x[1], hz = 0.5 * x[2];
+    const double qn = sqrt_d(1.0 + ((hx * hx + hy * hy) + hz * hz));
+    const double qw = 1.0 / qn, qx = hx / qn, qy = hy / qn, qz = hz / qn;
+    const double D[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qz * qw),       2.0 * (qx * qz + qy * qw),
+                         2.0 * (qx * qy + qz * qw),       1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qx * qw),
+                         2.0 * (qx * qz - qy * qw),       2.0 * (qy * qz + qx * qw),       1.0 - 2.0 * (qx * qx + qy * qy)};
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 3; ++i) {
+        const double a = T[4 * i], b = T[4 * i + 1], c = T[4 * i + 2];
+        T[4 * i + 3] = ((a * x[3] + b * x[4]) + c * x[5]) + T[4 * i + 3];
+        T[4 * i] = (a * D[0] + b * D[3]) + c * D[6];
+        T[4 * i + 1] = (a * D[1] + b * D[4]) + c * D[7];
+        T[4 * i + 2] = (a * D[2] + b * D[5]) + c * D[8];
+    }
+    *omega_norm = on;
+    *v_norm = vn;
+    return (on < eps_rot && vn < eps_trans) ? kRegConverged : kRegGo;
+}
+
 }  // namespace scvod
 #endif  // SCVOD_MATH_H_

@@ -300,6 +300,21 @@ SPLIT_MISS, SPLIT_HIT, SPLIT_GATED = 0, 1, 2
 SPLIT_STATS = ("n_hit", "n_miss", "n_gated", "pass1_queries", "ring_queries", "exhaustive_queries")
 
 
+class RegisterParams(C.Structure):
+    """scvod_register_params (64 bytes); use256 points at host bytes the caller keeps alive for the call (register_params_default does)"""
+    _fields_ = [("max_iterations", C.c_int32), ("min_corr", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32),
+                ("max_dist", C.c_float), ("max_range", C.c_float), ("eps_rot", C.c_double), ("eps_trans", C.c_double),
+                ("lam", C.c_double), ("pivot_eps", C.c_double), ("use256", C.c_void_p)]
+
+
+REG_POINT, REG_PLANE = 0, 1
+REG_MAX_ITERATIONS, REG_CONVERGED, REG_DEGENERATE = 0, 1, 2
+REGISTER_RECORD_DTYPE = np.dtype([("status", "i4"), ("iterations", "i4"), ("n_corr", "i8"), ("sum_r2", "f8"), ("last_omega", "f8"),
+                                  ("last_v", "f8"), ("skip_nan", "i4"), ("skip_range", "i4"), ("skip_label", "i4"), ("skip_no_corr", "i4"),
+                                  ("skip_normal", "i4"), ("reserved", "i4")])
+REGISTER_STATS = ("scans", "converged", "max_iterations", "degenerate", "correspondences", "iterations", "skipped", "points")
+
+
 class ScanResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_points", "n_ground", "n_nonground", "n_dropped", "n_apri", "n_rejected",
                                           "n_voxels", "n_patches")] + \
@@ -543,6 +558,15 @@ def load_lib():
         "scvod_component_visibility_params_default": (None, [C.POINTER(ComponentVisibilityParams)]),
         "scvod_map_component_visibility": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, C.POINTER(ComponentVisibilityParams), vp, i64, vp, vp]),
         "scvod_map_component_visibility_stats": (C.c_int, [vp, vp]),
+        "scvod_register_params_default": (None, [C.POINTER(RegisterParams)]),
+        "scvod_register_check": (C.c_int, [C.POINTER(RegisterParams), f32, i32, vp]),
+        "scvod_map_register": (C.c_int, [vp, vp, vp, i32, vp, vp, C.POINTER(RegisterParams), vp, vp, vp, vp]),
+        "scvod_batch_map_register": (C.c_int, [vp, vp, vp, vp, C.POINTER(RegisterParams), vp, vp, vp, vp]),
+        "scvod_map_register_stats": (C.c_int, [vp, vp]),
+        "scvod_map_register_scratch_bytes": (i64, [vp]),
+        "scvod_register_device": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, i32, C.POINTER(RegisterParams), vp, vp, vp]),
+        "scvod_register_stats": (C.c_int, [vp, vp]),
+        "scvod_register_scratch_bytes": (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # raises AttributeError if a declared symbol is not exported
@@ -596,8 +620,52 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_map_component_visibility_stats",
                     "scvod_split_params_default", "scvod_map_split_device", "scvod_map_split_stats", "scvod_map_split_scratch_bytes",
                     "scvod_map_split",
+                    "scvod_register_params_default", "scvod_register_check", "scvod_map_register", "scvod_batch_map_register",
+                    "scvod_map_register_stats", "scvod_map_register_scratch_bytes", "scvod_register_device", "scvod_register_stats",
+                    "scvod_register_scratch_bytes",
                     "scvod_esf_params_default", "scvod_esf_device", "scvod_batch_object_esf", "scvod_esf_stats", "scvod_esf_scratch_bytes",
                     "scvod_esf_fold10", "scvod_feature_row21"]
+
+
+def register_params_default(use256=None, **kw):
+    """scvod_register_params with this project's (untuned) defaults, overridden by keyword (lam: the struct's lambda).  use256: None
+    (every label), a [256] array, or the labels that take part; the bytes stay alive with the returned struct"""
+    p = RegisterParams()
+    load_lib().scvod_register_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    if use256 is not None:
+        a = np.asarray(use256)
+        if a.shape != (256,):
+            a = np.zeros(256, np.uint8)
+            a[np.asarray(use256, np.int64).reshape(-1)] = 1
+        p._use_bytes = np.ascontiguousarray(a != 0, np.uint8)
+        p.use256 = p._use_bytes.ctypes.data
+    return p
+
+
+def register_check(params=None, leaf=0.0, has_normals=False, d_src_xyzi=0):
+    """scvod_register_check: the status (0 or SCVOD_ERR_INVALID) the register calls would return before touching a device"""
+    return int(load_lib().scvod_register_check(C.byref(params) if params is not None else None, float(leaf), int(bool(has_normals)),
+                                               C.c_void_p(int(d_src_xyzi))))
+
+
+def register_result(d_pose_out, d_records):
+    """the outputs of a register call on the host (synchronises): dict(matrices float64 [n_scans, 3, 4], poses float32 [n_scans, 6] =
+    {x, y, z, roll, pitch, yaw} of the matrices narrowed to float (scvod_pose_from_matrix: NOT a bit-exact round trip), records
+    REGISTER_RECORD_DTYPE [n_scans])"""
+    M = d_pose_out.cpu().numpy().reshape(-1, 3, 4)
+    rec = d_records.cpu().numpy().view(np.uint8).reshape(-1)[:64 * len(M)].view(REGISTER_RECORD_DTYPE)
+    poses = np.stack([pose_from_matrix(m.astype(np.float32)) for m in M]) if len(M) else np.zeros((0, 6), np.float32)
+    return dict(matrices=M, poses=poses, records=rec)
+
+
+def _register_outputs(n_scans, device):
+    import torch
+    dev = torch.device("cuda", device)
+    return (torch.empty((max(n_scans, 1), 12), dtype=torch.float64, device=dev)[:n_scans],
+            torch.empty((max(n_scans, 1) * 64,), dtype=torch.uint8, device=dev)[:64 * n_scans])
 
 
 def eval_params_default(voxelsize=None, dynamic_classes=None):
@@ -1517,6 +1585,34 @@ class Ctx:
                                                   C.c_void_p(stream) if stream else None))
         return idx[:nq], sq[:nq], w[:nq]
 
+    # ---- refining scan poses against a cloud (include/scvod.h: scvod_register_device) ----
+    def register_device(self, d_src_xyzi, scan_offsets, d_tgt_xyz, poses=None, labels=None, d_tgt_normals=None, params=None, stream=None):
+        """torch CUDA tensors in: the source [n, 4] float32, the target [m, 3] float32 and (plane mode) its normals [m, 3]; labels uint8
+        [n] or None.  (d_pose_out float64 [n_scans, 12], d_records uint8 [n_scans * 64]) on the device, stream-ordered;
+        register_result brings them to the host"""
+        off = np.ascontiguousarray(scan_offsets, np.int32)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == len(off) - 1
+        pose, rec = _register_outputs(len(off) - 1, self.device)
+        n_tgt = int(d_tgt_xyz.shape[0])
+        self._chk(self.lib.scvod_register_device(self.h, C.c_void_p(d_src_xyzi.data_ptr()), off.ctypes.data_as(C.c_void_p), len(off) - 1,
+                                                 None if p is None else p.ctypes.data_as(C.c_void_p),
+                                                 None if labels is None else C.c_void_p(labels.data_ptr()),
+                                                 C.c_void_p(d_tgt_xyz.data_ptr()) if n_tgt else None,
+                                                 None if d_tgt_normals is None else C.c_void_p(d_tgt_normals.data_ptr()), n_tgt,
+                                                 C.byref(params) if params is not None else None, C.c_void_p(pose.data_ptr()),
+                                                 C.c_void_p(rec.data_ptr()), C.c_void_p(stream) if stream else None))
+        return pose, rec
+
+    def register_stats(self):
+        """REGISTER_STATS of the last register_device call on this ctx (synchronises its stream)"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_register_stats(self.h, o))
+        return dict(zip(REGISTER_STATS, (int(v) for v in o)))
+
+    def register_scratch_bytes(self):
+        return int(self.lib.scvod_register_scratch_bytes(self.h))
+
     # ---- evaluation against labelled truth on the device (include/scvod.h: scvod_evaluate_device ...) ----
     @staticmethod
     def _xyz(t):
@@ -2196,6 +2292,43 @@ class StaticMap:
 
     def query_scratch_bytes(self):
         return int(self.lib.scvod_map_query_scratch_bytes(self.h))
+
+    # ---- refining scan poses against the map (include/scvod.h: scvod_map_register) ----
+    def register(self, d_xyzi, scan_offsets, poses=None, labels=None, params=None, select=None, stream=None):
+        """scvod_map_register of the caller's cloud (torch float32 [n, 4]; labels: torch uint8 [n] or None): (d_pose_out float64
+        [n_scans, 12], d_records uint8 [n_scans * 64]) on the device, stream-ordered; register_result brings them to the host"""
+        off = np.ascontiguousarray(scan_offsets, np.int32)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p is None or p.shape[0] == len(off) - 1
+        pose, rec = _register_outputs(len(off) - 1, self.device)
+        k, pk = self._table256(select)
+        self._chk(self.lib.scvod_map_register(self.h, C.c_void_p(d_xyzi.data_ptr()), off.ctypes.data_as(C.c_void_p), len(off) - 1,
+                                              None if p is None else p.ctypes.data_as(C.c_void_p),
+                                              None if labels is None else C.c_void_p(labels.data_ptr()),
+                                              C.byref(params) if params is not None else None, pk, C.c_void_p(pose.data_ptr()),
+                                              C.c_void_p(rec.data_ptr()), C.c_void_p(stream or 0)))
+        return pose, rec
+
+    def register_batch(self, ctx, poses, labels=None, params=None, select=None, stream=None):
+        """scvod_batch_map_register: the same for the input cloud of the ctx's last batch (labels: typically ctx's point labels)"""
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        assert p.shape[0] == ctx._n_scans
+        pose, rec = _register_outputs(ctx._n_scans, self.device)
+        k, pk = self._table256(select)
+        self._chk(self.lib.scvod_batch_map_register(ctx.h, self.h, p.ctypes.data_as(C.c_void_p),
+                                                    None if labels is None else C.c_void_p(labels.data_ptr()),
+                                                    C.byref(params) if params is not None else None, pk, C.c_void_p(pose.data_ptr()),
+                                                    C.c_void_p(rec.data_ptr()), C.c_void_p(stream or 0)))
+        return pose, rec
+
+    def register_stats(self):
+        """REGISTER_STATS of the last register call on this map (synchronises its stream)"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_map_register_stats(self.h, o))
+        return dict(zip(REGISTER_STATS, (int(v) for v in o)))
+
+    def register_scratch_bytes(self):
+        return int(self.lib.scvod_map_register_scratch_bytes(self.h))
 
     # ---- cleaning scans against the map (include/scvod.h: scvod_map_filter) ----
     def _filter_outputs(self, n, n_scans, want, payload, votes_cap):

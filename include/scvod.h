@@ -1987,6 +1987,104 @@ int scvod_map_component_visibility(scvod_map* map, const int32_t* d_component, i
  * overflow, with the words filled; SCVOD_ERR_STATE before the first call. */
 int scvod_map_component_visibility_stats(scvod_map* map, int64_t* h_out8);
 
+/* ---- refining scan poses against the static map or a cloud (opt-in: nothing runs or is allocated unless these are called;
+ *      csrc/scvod_register.hip) ----
+ * Reference analogue: none (its src/gicp.cpp concatenates PCD files).  The definition is this project's.
+ * Every other stage takes the caller's poses as exact; this one improves them by Gauss-Newton on nearest-point correspondences, all
+ * iterations enqueued on the stream without a host read in between.  The step is defined once, in csrc/scvod_math.h (reg_*):
+ *   T_s        the running pose of scan s, a row-major 3x4 in fp64 on the device (d_pose_out); initially the fp32 matrix
+ *              scvod_pose_matrix(h_poses + 6 s) widened (h_poses NULL: the zero pose), so iteration 0 sees the points scvod_map_query sees
+ *   moving     a source point p (packed float4 in the sensor frame; w is not read) goes to T0*x + T1*y + T2*z + T3 per row, left to
+ *              right in fp32, with the fp32 rounding of T_s
+ *   skipped    and counted, each in its own counter: a NaN coordinate; (x*x + y*y) + z*z > max_range * max_range in fp32; a label
+ *              byte whose use256 entry is 0; no correspondence; (plane mode) a target normal that is not finite or shorter than 1e-6
+ *   q          the target's nearest point under the target's own rule (below) at squared fp32 distance d < max_dist * max_dist
+ *   residual   for the right perturbation T <- T * exp(xi), xi = (omega, v).  SCVOD_REG_POINT: three rows r = p - R^T (q - t),
+ *              J = [ -[p]x , I ].  SCVOD_REG_PLANE: one row e = n_l . r with n_l = R^T (n / |n|), J = [ (p x n_l)^T , n_l^T ]
+ *   sums       per scan the 21 + 6 + 1 entries of J^T J (upper triangle), J^T r and sum r^2: every term in fp64 from the fp32 inputs,
+ *              times 2^20, rounded to nearest and added as int64 -- the sums do not depend on the order of the points, the launch
+ *              geometry or the run.  No sum can overflow with max_range <= 256, max_dist <= 256 and at most 2^24 points per scan;
+ *              a larger or infinite max_range is accepted and leaves that bound to the caller (points * range^2 < 2^41)
+ *   solve      fp64: H = sums / 2^20, H_ii += lambda * H_ii, LDL^T.  DEGENERATE (the pose is kept) with fewer than min_corr
+ *              correspondences, a pivot not above pivot_eps * max H_ii, or a step that is not finite
+ *   update     the unit quaternion of (1, omega / 2) as a rotation dR (a Cayley step): R <- R dR, t <- R v + t; only + - * / sqrt
+ *   CONVERGED  |omega| < eps_rot and |v| < eps_trans for the step just applied.  A converged or degenerate scan is latched in its
+ *              record: later iterations return at once for it and its pose does not change again
+ * The rotation stays as orthonormal as the initial fp32 matrix is (about 1e-7): each dR is orthonormal to a few ulp of fp64.
+ * Device and host agree bit for bit (tests/helpers/register_ref.cpp runs the same functions on the CPU).
+ * scvod_pose_from_matrix turns a refined matrix (narrowed to float) into the {x, y, z, roll, pitch, yaw} the other calls take; that
+ * round trip goes through fp32 Euler angles and is NOT bit-exact. */
+#define SCVOD_REG_POINT 0 /* mode: point-to-point */
+#define SCVOD_REG_PLANE 1 /* mode: point-to-plane (a cloud target with normals only) */
+#define SCVOD_REG_MAX_ITERATIONS 0 /* status: max_iterations ran without convergence */
+#define SCVOD_REG_CONVERGED 1
+#define SCVOD_REG_DEGENERATE 2
+typedef struct scvod_register_params {
+    int32_t max_iterations; /* 1 .. 64                                                                        */
+    int32_t min_corr;       /* >= 6: fewer correspondences make the scan DEGENERATE                           */
+    int32_t mode;           /* SCVOD_REG_POINT / SCVOD_REG_PLANE                                              */
+    int32_t reserved;       /* 0                                                                              */
+    float max_dist;         /* > 0, <= 256 (map target: <= 0.99f * leaf)                                      */
+    float max_range;        /* > 0; +inf: no range gate                                                       */
+    double eps_rot;         /* >= 0, radians                                                                  */
+    double eps_trans;       /* >= 0, metres                                                                   */
+    double lambda;          /* >= 0: Levenberg damping of the diagonal                                        */
+    double pivot_eps;       /* >= 0                                                                           */
+    const uint8_t* use256;  /* [256] host bytes over the label byte, read before the call returns; NULL: all  */
+} scvod_register_params;
+/* max_iterations 10, min_corr 30, POINT, max_dist 0.19, max_range 80, eps_rot 1e-6, eps_trans 1e-5, lambda 0, pivot_eps 1e-9, use256
+ * NULL.  This project's values, untuned and NOT from real data. */
+void scvod_register_params_default(scvod_register_params* p);
+/* What the three calls below refuse before a device is touched, as a host-only function: SCVOD_ERR_INVALID for max_iterations outside
+ * 1 .. 64, min_corr < 6, an unknown mode, reserved != 0, max_dist not in (0, 256], max_range not > 0, a negative or NaN eps_rot,
+ * eps_trans, lambda or pivot_eps; with leaf > 0 (a map target): max_dist > 0.99f * leaf or plane mode; with leaf == 0 (a cloud
+ * target): plane mode without normals (has_normals == 0); a d_src_xyzi that is not 16-byte aligned.  params NULL: the defaults. */
+int scvod_register_check(const scvod_register_params* params, float leaf, int32_t has_normals, const void* d_src_xyzi);
+typedef struct scvod_register_record { /* 64 bytes, one per scan */
+    int32_t status;       /* SCVOD_REG_*                                                                     */
+    int32_t iterations;   /* accumulate + solve rounds this scan took part in                                */
+    int64_t n_corr;       /* correspondences of the last accumulation                                        */
+    double sum_r2;        /* its sum of squared residuals (the int64 sum / 2^20)                             */
+    double last_omega;    /* |omega| and |v| of the last step (0 for a DEGENERATE round)                     */
+    double last_v;
+    int32_t skip_nan, skip_range, skip_label, skip_no_corr, skip_normal; /* of the last accumulation         */
+    int32_t reserved;     /* 0                                                                               */
+} scvod_register_record;
+/* Against the static map (both kinds), point-to-point.  The candidate rule is the query's: the nearest decoded representative among
+ * the own cell and the 26 around it (csrc/scvod_mapprobe.h, shared with the query and the filter), ties to the smaller key, the
+ * select table honoured (labelled maps only) -- a scan's correspondences of iteration 0 are the points whose d_nn_key != ~0 in
+ * scvod_map_query with the same poses, radius = max_dist and select table.  Only reads the table: no record, no counter and no scratch
+ * of the accumulate, query, filter or component calls moves.
+ *   d_xyzi [h_scan_offsets[n_scans]][4], 16-byte aligned; d_labels one byte per point or NULL (then use256 is not read)
+ *   d_pose_out [n_scans][12] doubles, 8-byte aligned; d_records [n_scans] scvod_register_record, 8-byte aligned; both required
+ * Stream-ordered: max_iterations rounds of {k_reg_accumulate, k_reg_solve} are enqueued and the call returns; it synchronises only to
+ * grow its scratch (grow-only, the map's own, a few hundred bytes per scan: scvod_map_register_scratch_bytes reports it), for poses or
+ * offsets that differ from the previous call's, and behind a call in flight on another stream.  params NULL: the defaults. */
+int scvod_map_register(scvod_map* map, const void* d_xyzi, const int32_t* h_scan_offsets, int32_t n_scans, const float* h_poses,
+                       const uint8_t* d_labels, const scvod_register_params* params, const uint8_t* h_select256, double* d_pose_out,
+                       void* d_records, void* stream);
+/* The same for the input cloud of the ctx's last batch, obtained as scvod_batch_map_query obtains it.  d_labels is typically the output
+ * of scvod_batch_point_labels with a use256 that leaves out SCVOD_PT_DYNAMIC, so that moving objects do not pull the pose.
+ * SCVOD_ERR_STATE without a processed batch; stream NULL = the stream of the ctx's last batch call. */
+int scvod_batch_map_register(scvod_ctx* ctx, scvod_map* map, const float* h_poses, const uint8_t* d_labels, const scvod_register_params* params,
+                             const uint8_t* h_select256, double* d_pose_out, void* d_records, void* stream);
+/* h_out8 = {scans, CONVERGED, MAX_ITERATIONS, DEGENERATE, correspondences of the last accumulations, iterations summed over the scans,
+ * points skipped in the last accumulations, source points} of the last call.  Synchronises that call's stream.  SCVOD_ERR_STATE before
+ * the first call. */
+int scvod_map_register_stats(scvod_map* map, int64_t* h_out8);
+int64_t scvod_map_register_scratch_bytes(const scvod_map* map);
+/* Against a cloud: d_tgt_xyz [n_tgt][3] packed floats (finite) in the frame the poses map into, d_tgt_normals [n_tgt][3] or NULL (plane
+ * mode requires them).  The grid is the shared one of the nearest-neighbour stages (csrc/scvod_grid.h) as scvod_nn_radius_search sizes
+ * it: cell edge max(max_dist, 0.2f), widened to max_dist / 0.98f when max_dist * max_dist > (0.99f * edge)^2 so that the 27 cells hold
+ * every point within max_dist; origin 0; the 27-cell probe, ties to the lowest index.  It is built once per call and reused by every
+ * iteration.  Scratch: grow-only, the ctx's own (scvod_register_scratch_bytes); scvod_arena_bytes does not move.  n_tgt == 0 is legal
+ * (every scan DEGENERATE).  Otherwise as scvod_map_register; stream NULL = the ctx's stream. */
+int scvod_register_device(scvod_ctx* ctx, const void* d_src_xyzi, const int32_t* h_scan_offsets, int32_t n_scans, const float* h_poses,
+                          const uint8_t* d_labels, const float* d_tgt_xyz, const float* d_tgt_normals, int32_t n_tgt,
+                          const scvod_register_params* params, double* d_pose_out, void* d_records, void* stream);
+int scvod_register_stats(scvod_ctx* ctx, int64_t* h_out8);
+int64_t scvod_register_scratch_bytes(scvod_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
