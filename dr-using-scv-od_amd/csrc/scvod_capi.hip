@@ -18,6 +18,7 @@
 #include "scvod_kernels.h"
 #include "scvod_chain.h"
 extern "C" void scvod__register_free(void* state);  // scvod_register.hip
+extern "C" void scvod__normals_free(void* state);   // scvod_normals.hip
 
 using namespace scvod;
 
@@ -233,6 +234,9 @@ struct scvod_ctx {
     // the pose refinement against a cloud (scvod_register_device, scvod_register.hip): the state of that unit (its grow-only block, the
     // staged poses and offsets), made by the first call; not part of the arena
     void* reg_state = nullptr;
+    // the surface normals of a cloud (scvod_normals_device, scvod_normals.hip): the state of that unit (its grow-only block, the event
+    // behind its last call), made by the first call; not part of the arena
+    void* nrm_state = nullptr;
     uint64_t types_serial = 0;        // counts the scvod_batch_cluster_types calls of this ctx
     uint64_t obj_lists_types_serial = 0;  // ... at the table call whose lists the scratch holds (the class mask reads the class bytes)
     // the objects linked into tracks (scvod_object_tracks_device / scvod_batch_object_tracks, scvod_tracks.hip): a grow-only block (pose
@@ -1401,6 +1405,12 @@ extern "C" void** scvod__ctx_register_slot(scvod_ctx* c, int* device, void** own
     *own_stream = (void*)c->stream;
     return &c->reg_state;
 }
+// scvod_normals.hip: the same for its state
+extern "C" void** scvod__ctx_normals_slot(scvod_ctx* c, int* device, void** own_stream) {
+    *device = c->device;
+    *own_stream = (void*)c->stream;
+    return &c->nrm_state;
+}
 extern "C" int scvod__ctx_fail(scvod_ctx* c, int code, const char* msg) { return fail(c, code, "%s", msg); }
 
 extern "C" {
@@ -1601,6 +1611,7 @@ void scvod_destroy(scvod_ctx* c) {
     if (c->esf_counters) hipFree(c->esf_counters);
     if (c->esf_ev) hipEventDestroy(c->esf_ev);
     scvod__register_free(c->reg_state);
+    scvod__normals_free(c->nrm_state);
     if (c->ov.buf) hipFree(c->ov.buf);
     if (c->ov_counters) hipFree(c->ov_counters);
     if (c->trk.buf) hipFree(c->trk.buf);

@@ -219,6 +219,7 @@ extern "C" int scvod__ctx_view(scvod_ctx* ctx, scvod::Arena* arena, int* device,
                                int* max_scan_pts, int* batch_mode, int* num_min_pts);
 extern "C" void* scvod__ctx_stream(scvod_ctx* ctx, void* stream);
 extern "C" void** scvod__ctx_register_slot(scvod_ctx* ctx, int* device, void** own_stream);
+extern "C" void** scvod__ctx_normals_slot(scvod_ctx* ctx, int* device, void** own_stream);
 extern "C" int scvod__ctx_fail(scvod_ctx* ctx, int code, const char* msg);
 extern "C" void scvod__register_free(void* state);  // scvod_register.hip: frees what a reg_state slot holds (NULL: nothing)
 extern "C" int scvod__ctx_ensure_lists(scvod_ctx* ctx, void* stream);  // ground_idx / nonground_idx / rejected_src of a lean batch, before their reader

@@ -1574,5 +1574,81 @@ SCVOD_HD int reg_solve_update(const long long* s, long long min_corr, double lam
     return (on < eps_rot && vn < eps_trans) ? kRegConverged : kRegGo;
 }
 
+// ---- surface normals of a cloud (scvod_normals.hip), defined once.  Not from the reference. ----
+// The neighbourhood of a query q is every usable cloud point p with fp32 d = (ex*ex + ey*ey) + ez*ez < radius*radius, e = p - q one
+// fp32 subtraction per component (q itself when it is a point of the cloud: d == 0).  Ten int64 words per query: the count k, the
+// sums of e_a (3) and of e_a e_b (6: xx, xy, xz, yy, yz, zz).  A term is the fp64 product of the fp32 offsets (48 significant bits:
+// exact), times 2^30, rounded to nearest (ties to even): integer sums do not depend on the order of the neighbours.
+//
+// The scale.  radius <= 4 bounds |e_a| by 4 (a rounding above it), a product by 2^4, a scaled term by 2^34; a cloud has at most 2^28
+// points: |sum| <= 2^28 * (2^34 + 1) < 2^63.  The rounding of a term is 2^-31, below the fp32 rounding of an offset of 2^-7 m.
+constexpr int kNrmWords = 10;
+constexpr double kNrmScale = 1073741824.0;  // 2^30
+constexpr float kNrmMaxCoord = 1.0e6f;      // a coordinate beyond it (or not finite) keeps a point out: its cell index stays an int
+
+// a point that may be a neighbour or a query (NaN fails the comparison, an infinity exceeds the bound)
+SCVOD_HD bool nrm_usable(float x, float y, float z) { return fabs_f(x) <= kNrmMaxCoord && fabs_f(y) <= kNrmMaxCoord && fabs_f(z) <= kNrmMaxCoord; }
+// x * 2^30 rounded to nearest, ties to even, for |x| < 2^21 (reg_fix's expression at this scale)
+SCVOD_HD long long nrm_fix(double x) {
+    const double y = x * kNrmScale;
+    return (long long)(d2u(y + 6755399441055744.0) & 0xfffffffffffffull) - (1ll << 51);
+}
+// the candidate p against the query q: true, and the ten words moved, iff p is inside the radius (r2 = radius * radius in fp32)
+SCVOD_HD bool nrm_add(float px, float py, float pz, float qx, float qy, float qz, float r2, long long* s) {
+    const float ex = px - qx, ey = py - qy, ez = pz - qz;
+    const float d = (ex * ex + ey * ey) + ez * ez;
+    if (!(d < r2)) return false;
+    const double x = (double)ex, y = (double)ey, z = (double)ez;
+    s[0] += 1;
+    s[1] += nrm_fix(x);
+    s[2] += nrm_fix(y);
+    s[3] += nrm_fix(z);
+    s[4] += nrm_fix(x * x);
+    s[5] += nrm_fix(x * y);
+    s[6] += nrm_fix(x * z);
+    s[7] += nrm_fix(y * y);
+    s[8] += nrm_fix(y * z);
+    s[9] += nrm_fix(z * z);
+    return true;
+}
+// The sums of a query to {nx, ny, nz, curvature}: mean and covariance of the offsets in fp64, narrowed to float, then the solver and the
+// curvature expression of point_normal_f32 (one eigen specification).  NaN everywhere below min_neighbours; a zero covariance gives
+// the NaN eigen33_min_f32 gives.
+SCVOD_HD void normal_finish(const long long* s, int min_neighbours, float out[4]) {
+    if (s[0] < (long long)min_neighbours) {
+        const float nan = u2f(0x7fc00000u);
+        out[0] = out[1] = out[2] = out[3] = nan;
+        return;
+    }
+    const double k = (double)s[0];
+    const double mx = (double)s[1] / kNrmScale / k, my = (double)s[2] / kNrmScale / k, mz = (double)s[3] / kNrmScale / k;
+    float cov[9];
+    cov[0] = (float)((double)s[4] / kNrmScale / k - mx * mx);
+    cov[1] = (float)((double)s[5] / kNrmScale / k - mx * my);
+    cov[2] = (float)((double)s[6] / kNrmScale / k - mx * mz);
+    cov[4] = (float)((double)s[7] / kNrmScale / k - my * my);
+    cov[5] = (float)((double)s[8] / kNrmScale / k - my * mz);
+    cov[8] = (float)((double)s[9] / kNrmScale / k - mz * mz);
+    cov[3] = cov[1];
+    cov[6] = cov[2];
+    cov[7] = cov[5];
+    float ev, v[3];
+    eigen33_min_f32(cov, &ev, v);
+    out[0] = v[0];
+    out[1] = v[1];
+    out[2] = v[2];
+    const float eig_sum = (cov[0] + cov[4]) + cov[8];
+    out[3] = eig_sum != 0.f ? fabs_f(ev / eig_sum) : 0.f;
+}
+// pcl::flipNormalTowardsViewpoint: the normal n of the query q is negated iff it points away from the viewpoint v (a NaN normal stays)
+SCVOD_HD void normal_flip(const float* v, float qx, float qy, float qz, float* n) {
+    const float dot = ((v[0] - qx) * n[0] + (v[1] - qy) * n[1]) + (v[2] - qz) * n[2];
+    if (dot < 0.f) {
+        n[0] = -n[0];
+        n[1] = -n[1];
+        n[2] = -n[2];
+    }
+}
+
 }  // namespace scvod
 #endif  // SCVOD_MATH_H_

@@ -315,6 +315,15 @@ REGISTER_RECORD_DTYPE = np.dtype([("status", "i4"), ("iterations", "i4"), ("n_co
 REGISTER_STATS = ("scans", "converged", "max_iterations", "degenerate", "correspondences", "iterations", "skipped", "points")
 
 
+class NormalParams(C.Structure):
+    """scvod_normal_params (16 bytes)"""
+    _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+NORMALS_STATS = ("queries", "finite", "below_min", "nonfinite_queries", "cloud_left_out", "largest_k", "sum_k", "zero")
+NORMALS_QUERY_ORDER, NORMALS_ENTRY_ORDER, NORMALS_WAVE_BLOCKS = 1, 2, 4  # scvod_set_normals_variant
+
+
 class ScanResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_points", "n_ground", "n_nonground", "n_dropped", "n_apri", "n_rejected",
                                           "n_voxels", "n_patches")] + \
@@ -567,6 +576,13 @@ def load_lib():
         "scvod_register_device": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, i32, C.POINTER(RegisterParams), vp, vp, vp]),
         "scvod_register_stats": (C.c_int, [vp, vp]),
         "scvod_register_scratch_bytes": (i64, [vp]),
+        "scvod_normal_params_default": (None, [C.POINTER(NormalParams)]),
+        "scvod_normals_check": (C.c_int, [C.POINTER(NormalParams), i32, i64, i32, i64, vp, vp, i32]),
+        "scvod_normals_device": (C.c_int, [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, C.POINTER(NormalParams), vp, vp, vp, vp, vp]),
+        "scvod_normals_stats": (C.c_int, [vp, vp]),
+        "scvod_normals_scratch_bytes": (i64, [vp]),
+        "scvod_map_points_normals": (C.c_int, [vp, vp, C.POINTER(NormalParams), vp, vp, vp, vp, vp, i64, vp, vp]),
+        "scvod_set_normals_variant": (C.c_int, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # raises AttributeError if a declared symbol is not exported
@@ -623,6 +639,8 @@ EXPORTED_SYMBOLS = ["scvod_params_default", "scvod_pw_params_default", "scvod_gr
                     "scvod_register_params_default", "scvod_register_check", "scvod_map_register", "scvod_batch_map_register",
                     "scvod_map_register_stats", "scvod_map_register_scratch_bytes", "scvod_register_device", "scvod_register_stats",
                     "scvod_register_scratch_bytes",
+                    "scvod_normal_params_default", "scvod_normals_check", "scvod_normals_device", "scvod_normals_stats",
+                    "scvod_normals_scratch_bytes", "scvod_map_points_normals", "scvod_set_normals_variant",
                     "scvod_esf_params_default", "scvod_esf_device", "scvod_batch_object_esf", "scvod_esf_stats", "scvod_esf_scratch_bytes",
                     "scvod_esf_fold10", "scvod_feature_row21"]
 
@@ -666,6 +684,27 @@ def _register_outputs(n_scans, device):
     dev = torch.device("cuda", device)
     return (torch.empty((max(n_scans, 1), 12), dtype=torch.float64, device=dev)[:n_scans],
             torch.empty((max(n_scans, 1) * 64,), dtype=torch.uint8, device=dev)[:64 * n_scans])
+
+
+def normal_params_default(**kw):
+    """scvod_normal_params with this project's (untuned) defaults -- radius 0.5, min_neighbours 5 -- overridden by keyword"""
+    p = NormalParams()
+    load_lib().scvod_normal_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def normals_check(params=None, cloud_stride=3, n_cloud=0, query_stride=0, n_query=0, seg_offsets=None, viewpoints=None, n_segments=None):
+    """scvod_normals_check: the status (0 or SCVOD_ERR_INVALID) the normals calls would return before touching a device"""
+    seg = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int32)
+    view = None if viewpoints is None else np.ascontiguousarray(viewpoints, np.float32)
+    if n_segments is None:
+        n_segments = 0 if seg is None else len(seg) - 1
+    return int(load_lib().scvod_normals_check(C.byref(params) if params is not None else None, int(cloud_stride), int(n_cloud), int(query_stride),
+                                              int(n_query), None if seg is None else seg.ctypes.data_as(C.c_void_p),
+                                              None if view is None else view.ctypes.data_as(C.c_void_p), int(n_segments)))
 
 
 def eval_params_default(voxelsize=None, dynamic_classes=None):
@@ -1613,6 +1652,55 @@ class Ctx:
     def register_scratch_bytes(self):
         return int(self.lib.scvod_register_scratch_bytes(self.h))
 
+    # ---- surface normals of a cloud (include/scvod.h: scvod_normals_device) ----
+    def normals_device(self, d_cloud, d_query=None, params=None, seg_offsets=None, viewpoints=None, want=("curvature",), stream=None):
+        """torch CUDA float32 tensors in: the cloud [m, 3 or 4] and the queries [n, 3 or 4] (None: the cloud itself).  seg_offsets
+        [n_segments + 1] with viewpoints [n_segments, 3] orient the normals.  dict(normals float32 [n, 3] -- what register_device takes as
+        d_tgt_normals -- and, as `want` names them, curvature float32 [n], count int32 [n], sums int64 [n, 10]) on the device,
+        stream-ordered"""
+        import torch
+        assert d_cloud.is_contiguous() and d_cloud.dim() == 2 and d_cloud.dtype == torch.float32
+        assert d_query is None or (d_query.is_contiguous() and d_query.dim() == 2 and d_query.dtype == torch.float32)
+        m = int(d_cloud.shape[0])
+        n = m if d_query is None else int(d_query.shape[0])
+        dev = d_cloud.device
+        out = dict(normals=torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev))
+        if "curvature" in want:
+            out["curvature"] = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
+        if "count" in want:
+            out["count"] = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+        if "sums" in want:
+            out["sums"] = torch.empty((max(n, 1), 10), dtype=torch.int64, device=dev)
+        seg = None if seg_offsets is None else np.ascontiguousarray(seg_offsets, np.int32)
+        view = None if viewpoints is None else np.ascontiguousarray(viewpoints, np.float32).reshape(-1, 3)
+        assert (seg is None) == (view is None) and (seg is None or len(view) == len(seg) - 1)
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        # a query cloud of no rows has no storage, and a NULL d_query would mean the self form: one row that is never read stands in
+        q_arg = d_query if d_query is None or n else torch.zeros((1, int(d_query.shape[1])), dtype=torch.float32, device=dev)
+        self._chk(self.lib.scvod_normals_device(self.h, ptr(d_cloud) if m else None, int(d_cloud.shape[1]), m, ptr(q_arg),
+                                                0 if d_query is None else int(d_query.shape[1]), n,
+                                                None if seg is None else seg.ctypes.data_as(C.c_void_p),
+                                                None if view is None else view.ctypes.data_as(C.c_void_p), 0 if seg is None else len(seg) - 1,
+                                                C.byref(params) if params is not None else None, ptr(out["normals"]), ptr(out.get("curvature")),
+                                                ptr(out.get("count")), ptr(out.get("sums")), C.c_void_p(stream) if stream else None))
+        return {k: v[:n] for k, v in out.items()}
+
+    def normals_stats(self):
+        """NORMALS_STATS of the last normals call on this ctx, the map form included (synchronises its stream)"""
+        o = (C.c_int64 * 8)()
+        self._chk(self.lib.scvod_normals_stats(self.h, o))
+        return dict(zip(NORMALS_STATS, (int(v) for v in o)))
+
+    def normals_scratch_bytes(self):
+        return int(self.lib.scvod_normals_scratch_bytes(self.h))
+
+    def set_normals_variant(self, variant=0):
+        """development switch: NORMALS_QUERY_ORDER or NORMALS_ENTRY_ORDER (0: the default arm), plus NORMALS_WAVE_BLOCKS"""
+        self._chk(self.lib.scvod_set_normals_variant(self.h, int(variant)))
+
     # ---- evaluation against labelled truth on the device (include/scvod.h: scvod_evaluate_device ...) ----
     @staticmethod
     def _xyz(t):
@@ -2505,6 +2593,32 @@ class StaticMap:
         o = (C.c_int64 * 8)()
         self._chk(self.lib.scvod_map_component_visibility_stats(self.h, o))
         return dict(zip(CMPVIS_STATS, (int(v) for v in o)))
+
+    def points_normals(self, ctx, params=None, select=None, with_labels=False, cap=None, stream=None):
+        """scvod_map_points_normals: dict(xyzi float32 [n, 4], xyz float32 [n, 3] packed -- ready for Ctx.register_device --, normals
+        float32 [n, 3], curvature float32 [n] and, labelled maps with with_labels, labels uint8 [n]) device tensors, row i the same cell,
+        the order unspecified.  select: see _table256 (labelled maps only).  cap None: the map's count.  Errors are the ctx's"""
+        import torch
+        n0 = max(self.count(stream), 1) if cap is None else int(cap)
+        dev = torch.device("cuda", self.device)
+        xyzi = torch.empty((max(n0, 1), 4), dtype=torch.float32, device=dev)
+        nrm = torch.empty((max(n0, 1), 3), dtype=torch.float32, device=dev)
+        cur = torch.empty((max(n0, 1),), dtype=torch.float32, device=dev)
+        lab = torch.empty((max(n0, 1),), dtype=torch.uint8, device=dev) if with_labels else None
+        n = C.c_int64()
+        k, pk = self._table256(select)
+        ctx._chk(self.lib.scvod_map_points_normals(ctx.h, self.h, C.byref(params) if params is not None else None, pk, C.c_void_p(xyzi.data_ptr()),
+                                                   None if lab is None else C.c_void_p(lab.data_ptr()), C.c_void_p(nrm.data_ptr()),
+                                                   C.c_void_p(cur.data_ptr()), n0, C.byref(n), C.c_void_p(stream or 0)))
+        n = int(n.value)
+        out = dict(xyzi=xyzi[:n], normals=nrm[:n], curvature=cur[:n])
+        if lab is not None:
+            out["labels"] = lab[:n]
+        # the points are complete (the call synchronised behind them); the packed copy is finished before this returns, so a register
+        # call on any stream may read it.  The normals are stream-ordered on the call's stream
+        out["xyz"] = xyzi[:n, :3].contiguous()
+        torch.cuda.current_stream(dev).synchronize()
+        return out
 
     def points(self, stream=None):
         """(xyzi float32 [n, 4], records int64 [n, 2]) device tensors, same (unspecified) order"""

@@ -2085,6 +2085,80 @@ int scvod_register_device(scvod_ctx* ctx, const void* d_src_xyzi, const int32_t*
 int scvod_register_stats(scvod_ctx* ctx, int64_t* h_out8);
 int64_t scvod_register_scratch_bytes(scvod_ctx* ctx);
 
+/* ---- surface normals and curvature of a cloud or of the static map's points (opt-in: nothing runs or is allocated unless these are
+ *      called; csrc/scvod_normals.hip) ----
+ * Reference analogue: none for an arbitrary cloud (SSC::intensityCalibrationByCurvature runs pcl::NormalEstimationOMP with the k nearest
+ * points of one scan; that stage is scvod_set_intensity_calibration).  The definition is this project's; it is
+ * what SCVOD_REG_PLANE of scvod_register_device needs of its target.  Defined once, in csrc/scvod_math.h (nrm_*, normal_finish):
+ *   neighbours  of a query q: every cloud point p with fp32 d = (ex*ex + ey*ey) + ez*ez < radius * radius, e = p - q one fp32
+ *               subtraction per component.  q itself is a neighbour when it is a point of the cloud (d == 0).  Radius based, not kNN:
+ *               the set does not depend on any order
+ *   left out    and counted: a cloud point with a NaN or infinite coordinate or |c| > 1e6 is never a neighbour; such a query gets NaN
+ *   sums        ten int64 words per query: the count k, the sums of e_a (x, y, z) and of e_a * e_b (xx, xy, xz, yy, yz, zz).  A term
+ *               is the fp64 product of the fp32 offsets (exact), times 2^30, rounded to nearest (ties to even): the sums do not depend
+ *               on the order of the points, the launch geometry or the run.  No sum can overflow with radius <= 4 and at most 2^28
+ *               cloud points; anything beyond is refused
+ *   finish      fp64: m_a = S_a / 2^30 / k, c_ab = S_ab / 2^30 / k - m_a * m_b; narrowed to float; the normal is the eigenvector of
+ *               the smallest eigenvalue by the solver of the intensity calibration and the region growing (one eigen specification),
+ *               the curvature |eigenvalue / ((c_xx + c_yy) + c_zz)|, 0 for a zero trace.  k < min_neighbours: NaN normal and
+ *               curvature.  A zero covariance gives the solver's NaN normal; plane-mode registration skips and counts such normals
+ *   orientation optional: queries h_seg_offsets[s] .. h_seg_offsets[s + 1] see the viewpoint h_viewpoints[3 s ..]; a normal is negated
+ *               iff fp32 ((vx - qx) * nx + (vy - qy) * ny) + (vz - qz) * nz < 0 (pcl::flipNormalTowardsViewpoint).  n_segments == 0:
+ *               the solver's sign stays (the plane residual of the registration does not depend on it)
+ * The grid is the shared one of the nearest-neighbour stages (csrc/scvod_grid.h) as scvod_nn_radius_search sizes it: cell edge
+ * max(radius, 0.2f), widened to radius / 0.98f when radius * radius > (0.99f * edge)^2 so that the 27 cells hold every point within
+ * the radius; origin 0.  As for that search, the neighbourhood is exactly the one defined above while |c| <= 25000 * edge on every axis;
+ * beyond it (up to 1e6) a neighbour near the radius may be missed.  Every point counts once, however many of the 27 cells share a
+ * bucket.  Device and host agree bit for bit (tests/helpers/normals_ref.cpp runs the same functions over an exhaustive loop).
+ * One call sees one cloud: a batch of scans in their sensor frames needs the world-frame export (scvod_batch_export_points with poses)
+ * or one call per scan.  Per-segment neighbourhoods are out of scope; the segments only choose the viewpoint. */
+typedef struct scvod_normal_params {
+    float radius;           /* > 0, <= 4                                                                      */
+    int32_t min_neighbours; /* >= 3: a query with fewer neighbours (itself included) gets NaN                 */
+    int32_t flags;          /* 0                                                                              */
+    int32_t reserved;       /* 0                                                                              */
+} scvod_normal_params;
+/* radius 0.5, min_neighbours 5.  This project's values, untuned and NOT from real data. */
+void scvod_normal_params_default(scvod_normal_params* p);
+/* What the calls below refuse before a device is touched, as a host-only function: SCVOD_ERR_INVALID for a radius not in (0, 4],
+ * min_neighbours < 3, flags or reserved != 0, a cloud_stride other than 3 or 4, a query_stride other than 3, 4 or 0 (0: the self
+ * form), n_cloud < 0 or > 2^28, n_query < 0 or > 2^31 - 1, n_segments < 0, offsets or viewpoints with n_segments == 0, viewpoints
+ * without offsets or offsets without viewpoints, offsets that do not start at 0, decrease or do not end at n_query.  params NULL: the
+ * defaults. */
+int scvod_normals_check(const scvod_normal_params* params, int32_t cloud_stride, int64_t n_cloud, int32_t query_stride, int64_t n_query,
+                        const int32_t* h_seg_offsets, const float* h_viewpoints, int32_t n_segments);
+/* d_cloud [n_cloud][cloud_stride] floats (xyz first; stride 3 or 4), d_query [n_query][query_stride] or NULL: the queries are the
+ * cloud (then n_query == n_cloud and query_stride is not read).  d_normals [n_query][3] packed floats -- exactly what
+ * scvod_register_device takes as d_tgt_normals; d_curvature [n_query], d_count [n_query] int32 (k) and d_sums [n_query][10] int64
+ * are optional (NULL).  A query that is not finite gets NaN, k 0 and zero sums.  n_cloud == 0 or n_query == 0 is legal.
+ * Stream-ordered (stream NULL = the ctx's stream): k_nrm_keep, the grid build and k_nrm_accumulate are enqueued and the call returns;
+ * the host arrays are copied before it does.  It synchronises only to grow its scratch (grow-only, the ctx's own:
+ * scvod_normals_scratch_bytes; the grid's work area, a keep byte per cloud point, eight counter words, the segment tables --
+ * scvod_arena_bytes and every other stage's scratch do not move).  A call on another stream of the same ctx is ordered behind the
+ * last one on the device (an event), not on the host: the calls of one ctx share the scratch and run one after the other. */
+int scvod_normals_device(scvod_ctx* ctx, const float* d_cloud, int32_t cloud_stride, int32_t n_cloud, const float* d_query, int32_t query_stride,
+                         int32_t n_query, const int32_t* h_seg_offsets, const float* h_viewpoints, int32_t n_segments,
+                         const scvod_normal_params* params, float* d_normals, float* d_curvature, int32_t* d_count, int64_t* d_sums, void* stream);
+/* h_out8 = {queries, finite normals, queries below min_neighbours, queries that are not finite, cloud points left out, largest k, sum
+ * of k, 0} of the last call (the map form included).  Synchronises that call's stream.  SCVOD_ERR_STATE before the first call. */
+int scvod_normals_stats(scvod_ctx* ctx, int64_t* h_out8);
+/* bytes of device scratch the normals hold on this ctx (0 before the first call) */
+int64_t scvod_normals_scratch_bytes(scvod_ctx* ctx);
+/* The static map as points with their normals: scvod_map_points (a plain map) or scvod_map_points_labelled (a labelled map; only
+ * there h_select256 and d_labels are legal) into d_xyzi [cap][4], 16-byte aligned, followed by the self form above with stride 4 into
+ * d_normals [cap][3] and d_curvature [cap] (optional).  Row i of every output is the same cell; the order is unspecified.  It
+ * synchronises `stream` and reports *n_out and SCVOD_ERR_CAPACITY exactly as those two calls do (nothing is written at or behind cap,
+ * and no normal at all); the normals are then stream-ordered behind the points (stream NULL = the ctx's stream).  Only the export
+ * counters of the map move, as in those calls; the scratch is the ctx's (scvod_normals_scratch_bytes).  Errors are reported on the
+ * ctx (scvod_last_error).  The packed [n][3] target scvod_register_device wants is a copy of the first three columns of d_xyzi.
+ * scvod_map_register keeps refusing plane mode: the map's normals go through scvod_register_device. */
+int scvod_map_points_normals(scvod_ctx* ctx, scvod_map* map, const scvod_normal_params* params, const uint8_t* h_select256, void* d_xyzi,
+                             uint8_t* d_labels, float* d_normals, float* d_curvature, int64_t cap, int64_t* n_out, void* stream);
+/* Development switch behind profiles/normals_cost.txt and the tests, never needed for a result: the low two bits choose the arm of the
+ * self form (0: the default; 1: a thread per query in the caller's order; 2: a thread per grid entry, so that the lanes of a wave share
+ * buckets), bit 2 launches workgroups of 64 threads in place of 256.  The outputs are identical. */
+int scvod_set_normals_variant(scvod_ctx* ctx, int32_t variant);
+
 #ifdef __cplusplus
 }
 #endif
